@@ -2,15 +2,29 @@
 """bench.py — forward+backward passes/sec of the minidiff hot path on MI355X.
 
     python bench.py --gpus N --steps K --warmup W [--workload cfg2|cfg3|cfg4|cfg5] [--lazy] [--graph]
+                    [--dump-outputs DIR] [--full]
 
 Metric (BASELINE.json): forward+backward passes/sec on the 4096x4096 fp32 matmul
 graph. At N = 1 the headline workload is configs[1] (cfg2): C = A @ B;
 C.backward() — 3 GEMMs (NN, NT, TN), 412,316,860,416 FLOP per sweep, inputs
-resident in HBM. After the headline's timed region the same process runs the other
-BASELINE configs (cfg3 eager / lazy, cfg4 eager / lazy, cfg5) and reports them
-under "secondary" — value, ms per sweep and the roofline of their dominant
-kernels from HIP events — so that one driver run carries the HBM-bound numbers
-too (`--no-secondary` skips them).
+resident in HBM.
+
+A plain run does only what the headline needs: set-up, pre-roll and W warm-up sweeps,
+the K timed sweeps (the dominant kernel priced from HIP events attached to its own
+dispatch inside them), `--dump-outputs` if given, the line. Everything else runs only
+with `--full`: after the headline's timed region the same process then times the NumPy
+oracle (`cpu_baseline`) and checks the gradients against it, runs ten single
+synchronised sweeps and a detail pass with every kernel bracketed, and runs the other
+BASELINE configs (cfg3 eager / lazy, cfg4 eager / lazy, cfg5) and reports them under
+"secondary" — value, ms per sweep and the roofline of their dominant kernels from HIP
+events — so that one driver run carries the HBM-bound numbers too (`--no-secondary`,
+`--no-cpu-baseline` skip parts of it).
+
+`--dump-outputs DIR` writes, after the timed region, what the last timed sweep computed —
+the forward output (`out.npy`) and the leaf gradients (`<leaf>_grad.npy`) — in float32
+(float64 where the sweep computes in float64). An array of more than 16 MB is written as
+a fixed sample of 16 MB: the elements at `dump_sample_index(size)` (seed 0, sorted,
+flattened), so that two builds given the same arguments compare output for output.
 
 With N > 1 (one rank per GPU) the headline stays the metric's own workload, cfg2, data-parallel
 the way north_star asks: every rank owns its own 4096 independent batch rows A_r (per-GPU work fixed:
@@ -18,8 +32,8 @@ the way north_star asks: every rank owns its own 4096 independent batch rows A_r
 all-reduce per sweep, sent in row panels that leave while the weight-gradient GEMM is still running.
 `value` = N x sweeps/s, so value(N) / (N x value(1)) is the scaling efficiency against the driver's N = 1
 run; `single_gpu_value` is the same sweep timed on ONE GPU in the same job (no collective), and
-`tensors_per_s` = 4096 x value (batch rows through forward+backward per second). After the headline the
-same job runs BASELINE's configs[3] (cfg4: ONE global batch of 8192 rows split over the ranks, strong
+`tensors_per_s` = 4096 x value (batch rows through forward+backward per second). With `--full`, after the
+headline the same job runs BASELINE's configs[3] (cfg4: ONE global batch of 8192 rows split over the ranks, strong
 scaling, bucket [W.grad || b.grad] all-reduced) and reports it as flat keys `cfg4_strong_*` together with
 its own single-GPU figure; `--workload cfg4` makes it the headline instead.
 
@@ -30,8 +44,8 @@ At N > 1 the gradient all-reduce must run on the library's own RCCL communicator
 ("rccl-direct"); anything else is an error unless --allow-torch-comm is given.
 
 ONE JSON line on stdout (rank 0), under 2 KB: `roofline` prices the dominant kernel from
-HIP events attached to the kernel's own dispatch inside the timed region and carries, as
-FLAT scalar keys, the figures of the other BASELINE configs (cfgN_*); `cpu_baseline` times
+HIP events attached to the kernel's own dispatch inside the timed region and carries (--full), as
+FLAT scalar keys, the figures of the other BASELINE configs (cfgN_*); `cpu_baseline` (--full) times
 the NumPy oracle (the reference's arithmetic) on this host's cores for every config. The
 full per-kernel detail goes to bench_detail.json (next to this file) and to stderr.
 """
@@ -62,9 +76,14 @@ def parse():
     ap.add_argument("--workload", default=None, choices=["cfg2", "cfg3", "cfg4", "cfg5"],
                     help="default: cfg2 on one GPU (BASELINE's headline), cfg4 on several (BASELINE's batch-sharded config)")
     ap.add_argument("--size", type=int, default=0, help="override the problem size (debug)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="only the headline workload")
-    ap.add_argument("--force-secondary", action="store_true", help="run the other configs even with --size (tests: toy sizes on the CPU double)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the CPU baseline and gradient check, single-sweep and per-kernel detail passes and the other configs "
+                         "(default: the headline workload alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed sweep computed to DIR/<name>.npy (float32 / float64, at most 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline and the gradient check")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: only the headline workload")
+    ap.add_argument("--force-secondary", action="store_true", help="--full: run the other configs even with --size (tests: toy sizes on the CPU double)")
     ap.add_argument("--lazy", action="store_true",
                     help="opt-in lazy fusion of elementwise chains (minidiff_amd/lazy.py); default is eager")
     ap.add_argument("--graph", action="store_true",
@@ -344,6 +363,34 @@ def grad_linf_rel(device_grads, oracle_grads):
         r = ref.reshape(-1).astype(np.float64)
         out[name] = float(np.max(np.abs(d.astype(np.float64) - r)) / max(np.max(np.abs(r)), 1e-300))
     return out
+
+
+DUMP_SAMPLE_BYTES = 16 * MIB    # --dump-outputs: per array; a larger one is written as a fixed sample of this size
+DUMP_LIMIT_BYTES = 64 * MIB
+
+
+def dump_sample_index(size, itemsize=4):
+    """The elements of a flattened output of `size` elements that --dump-outputs writes when the whole array would pass
+    DUMP_SAMPLE_BYTES: seeded (0), sorted and distinct, so that every run and every build picks the same ones."""
+    return np.unique(np.random.default_rng(0).integers(0, size, DUMP_SAMPLE_BYTES // itemsize))
+
+
+def dump_outputs(outputs, grad_names, directory):
+    """What one sweep hands its caller — the forward output and the gradients of its leaves — copied to the host after the timed
+    region and written as DIR/<name>.npy in float32 (float64 where the sweep computes in float64)."""
+    arrays = {"out": outputs["out"]}
+    for name in grad_names:
+        arrays[name + "_grad"] = outputs[name].grad
+    os.makedirs(directory, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        a = np.asarray(t.as_numpy())
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32, copy=False)
+        if a.nbytes > DUMP_SAMPLE_BYTES:
+            a = a.reshape(-1)[dump_sample_index(a.size, a.itemsize)]
+        total += a.nbytes
+        np.save(os.path.join(directory, name + ".npy"), a)
+    assert total <= DUMP_LIMIT_BYTES, total
 
 
 PREROLL = {"cfg2": 12, "cfg3": 20, "cfg4": 10, "cfg5": 40}
@@ -703,8 +750,9 @@ def main(entry=None):
         lib.comm_count(C.byref(n))
         return int(n.value)
 
-    def run(workload, lazy, steps, warmup, graph=False, size=0, keep=None, solo=False, want_grads=False):
-        """One workload: pre-roll, W warm-up sweeps, K timed sweeps between barriers, max over ranks.
+    def run(workload, lazy, steps, warmup, graph=False, size=0, keep=None, solo=False, want_grads=False, dump_dir=None):
+        """One workload: pre-roll, W warm-up sweeps, K timed sweeps between barriers, max over ranks (--full: then the single
+        sweeps, the detail pass and the collective alone). `dump_dir`: --dump-outputs of the last timed sweep.
         `keep`: dict carrying (state, step) between the eager and the lazy run of one workload.
         `solo` (N > 1 jobs): every rank runs the UN-sharded workload on its own GPU with no collective, and the time is the
         calling rank's own — the same-job N = 1 figure of the workload the N > 1 headline is quoted on."""
@@ -737,8 +785,9 @@ def main(entry=None):
                            overlap=os.environ.get("MDHIP_DP_OVERLAP", "1") != "0")
 
         def sweep():
-            step()
+            out = step()
             sync()
+            return out
 
         # untimed pre-roll before the W warm-up sweeps: the first ~15 ms of work after process start run
         # at ramping clocks and grow the allocator cache (W <= 2 alone measured 7 % low on cfg2)
@@ -839,9 +888,10 @@ def main(entry=None):
                     "cfg3": set() if lazy else {"multiply"}}[workload]
         timer.only = dominant
         timer.enabled = not graph and not segmented and bool(dominant)
+        outputs = None
         t0 = time.perf_counter()
         for _ in range(steps):
-            run_one()
+            outputs = run_one()
         lib.sync()
         if torch is not None and torch.cuda.is_available():
             torch.cuda.synchronize()
@@ -855,10 +905,12 @@ def main(entry=None):
         kernel_ms = timer.collect()
         ms_per_step = elapsed / steps * 1e3
         timer.only = None
+        if dump_dir and rank == 0 and outputs is not None:
+            dump_outputs(outputs, GRAD_NAMES[workload], dump_dir)
         # SURVEY 8d also asks for the median and the minimum of single sweeps: ten more sweeps, each synchronised at its
         # end (outside the timed region: a per-sweep sync costs the overlap between consecutive sweeps)
         single = []
-        if not graph:   # (eager sweeps also in segmented mode: what one sweep costs with Python dispatch in it)
+        if args.full and not graph:   # (eager sweeps also in segmented mode: what one sweep costs with Python dispatch in it)
             for _ in range(10):
                 barrier()
                 t1 = time.perf_counter()
@@ -866,7 +918,7 @@ def main(entry=None):
                 lib.sync()
                 single.append((time.perf_counter() - t1) * 1e3)
             single.sort()
-        if not graph and workload in ("cfg3", "cfg4"):   # detail pass: every kernel of the sweep bracketed, outside the timed region
+        if args.full and not graph and workload in ("cfg3", "cfg4"):   # detail pass: every kernel of the sweep bracketed, outside the timed region
             timer.enabled = True
             for _ in range(min(steps, 5)):
                 sweep()
@@ -883,7 +935,7 @@ def main(entry=None):
 
         # the collective alone (un-overlapped, outside the timed region): time and bus bandwidth
         allreduce_ms = busbw = None
-        if comm is not None and sync.active:
+        if args.full and comm is not None and sync.active:
             import ctypes as C
             grads = [p.grad for p in sync.params]
             buf = sync.bucket if sync.bucket is not None else grads[0]._data
@@ -948,10 +1000,11 @@ def main(entry=None):
         nd.set_lazy(prev_lazy)
         return res
 
-    check_grads = rank == 0 and world == 1 and not args.no_cpu_baseline
-    head = run(args.workload, args.lazy, args.steps, args.warmup, graph=args.graph, size=args.size, want_grads=check_grads)
+    check_grads = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline
+    head = run(args.workload, args.lazy, args.steps, args.warmup, graph=args.graph, size=args.size, want_grads=check_grads,
+               dump_dir=args.dump_outputs)
     head_grads = head.pop("_grads", None)
-    event_overhead_ms = timer.empty_bracket_ms()
+    event_overhead_ms = timer.empty_bracket_ms() if args.full else None
     # N > 1: the same job also times the headline workload on ONE GPU (every rank on its own card, no collective; rank 0's
     # figure) — the N = 1 value its scaling is judged against, from the same boxes and the same clocks
     def solo_run(workload, lazy):
@@ -967,7 +1020,7 @@ def main(entry=None):
         lib.empty_cache()
         return s
 
-    solo = solo_run(args.workload, args.lazy) if world > 1 and not args.graph else None
+    solo = solo_run(args.workload, args.lazy) if args.full and world > 1 and not args.graph else None
 
     # ---- CPU leg (rank 0, N = 1): the NumPy engine on the same seeds, once per WORKLOAD — its passes/s (the reported baseline)
     # and its gradients, against which every device run of that workload (eager and lazy) is compared norm-wise
@@ -989,7 +1042,7 @@ def main(entry=None):
 
     # ---- the other BASELINE configs, same process, after the headline's timed region -------------------
     secondary = None
-    if not args.no_secondary and not args.graph and (not args.size or args.force_secondary or os.environ.get("MDHIP_BENCH_HOST_COMM") == "1"):
+    if args.full and not args.no_secondary and not args.graph and (not args.size or args.force_secondary or os.environ.get("MDHIP_BENCH_HOST_COMM") == "1"):
         secondary = {}
         gc.collect()
         lib.empty_cache()
@@ -1081,7 +1134,7 @@ def main(entry=None):
             "dtype": "f32", "data": "synthetic",
             "config": cfg, "roofline": roof, "cpu_baseline": cpu,
             # the metric's second half: max over every gradient of every config run, norm-wise against the NumPy engine
-            # on the same seeds (bar 1e-5 for fp32). None when the CPU leg is skipped (N > 1, --no-cpu-baseline).
+            # on the same seeds (bar 1e-5 for fp32). None when the CPU leg is skipped (no --full, N > 1, --no-cpu-baseline).
             "grad_linf_rel_max": linf_max,
         }
         if "tensors_per_s" in head:

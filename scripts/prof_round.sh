@@ -10,7 +10,7 @@ export TMPDIR=/tmp
 run() {  # name, bench flags
   name=$1; shift
   d=$out/ks_$name
-  rocprofv3 --kernel-trace --stats --output-format csv -d $d -- python3 bench.py --no-secondary --no-cpu-baseline --steps 20 --warmup 3 "$@" > $out/${RTAG:-r4}_bench_${name}_under_rocprof.log 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $d -- python3 bench.py --full --no-secondary --no-cpu-baseline --steps 20 --warmup 3 "$@" > $out/${RTAG:-r4}_bench_${name}_under_rocprof.log 2>&1
   cp $(find $d -name '*kernel_stats.csv' | head -1) $out/${RTAG:-r4}_${name}_kernel_stats.csv
   # min / median beside the mean, and the timed region apart from the cold pre-roll + warm-up sweeps (bench.py: PREROLL + 3 warm-up,
   # 20 timed, then 10 single synchronised sweeps [+ 5 detail sweeps for cfg3 / cfg4])
@@ -38,5 +38,5 @@ pmc cfg4_lazy --workload cfg4 --lazy
 pmc cfg3_lazy --workload cfg3 --lazy
 pmc cfg3 --workload cfg3
 pmc cfg2 --workload cfg2
-python3 bench.py > $out/${RTAG:-r4}_bench_default.json 2> $out/${RTAG:-r4}_bench_default.err
+python3 bench.py --full > $out/${RTAG:-r4}_bench_default.json 2> $out/${RTAG:-r4}_bench_default.err
 echo all done

@@ -10,7 +10,7 @@ mkdir -p $out
 port=29541
 for r in 0 1; do
   RANK=$r LOCAL_RANK=0 WORLD_SIZE=2 MASTER_ADDR=127.0.0.1 MASTER_PORT=$port MDHIP_DEVICE=0 MDHIP_BENCH_HOST_COMM=1 HSA_ENABLE_IPC_MODE_LEGACY=0 \
-    timeout -k 10 500 python3 bench.py --gpus 2 --steps 4 --warmup 1 --no-cpu-baseline --detail $out/detail.json "$@" > $out/rank$r.out 2> $out/rank$r.err &
+    timeout -k 10 500 python3 bench.py --gpus 2 --steps 4 --warmup 1 --full --no-cpu-baseline --detail $out/detail.json "$@" > $out/rank$r.out 2> $out/rank$r.err &
   pids[$r]=$!
 done
 rc=0

@@ -1,32 +1,26 @@
-"""Runs in a subprocess (minidiff parses sys.argv at import). Runs the random forward+backward
-programs of tests/fuzz_tape.py through the UNMODIFIED reference — `numpy`: on its own NumPy backend;
-`plugin`: with `--backend minidiff_amd.plugin` bound to the CPU test double — and pickles outputs,
-gradients (second order every fourth case) or the exception type of each case."""
+"""Runs in a subprocess (it claims the module name `minidiff`). Runs the random forward+backward
+programs of tests/fuzz_tape.py through the tape on the plug-in backend class
+(minidiff_amd.plugin.hip_backend) bound to the CPU test double, and pickles outputs, gradients
+(second order every fourth case) or the exception type of each case — the form
+tests/golden/make_dropin_golden.py records for the reference's NumPy backend.
+    dropin_fuzz_script.py N_CASES SEED OUT_PATH      (MDHIP_LAZY=1: fused chains)"""
 import os
 import pickle
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = os.environ.get("MINIDIFF_REFERENCE", "/root/reference")
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
-sys.path.insert(0, REF)
 
-which, n_cases, seed, out_path = sys.argv[1], int(sys.argv[2]), int(sys.argv[3]), sys.argv[4]
-if which == "plugin":
-    from minidiff_amd import _capi
-    _capi.use_library(os.path.join(ROOT, "oracle", "_build", "libmdhip_host.so"))
-    sys.argv = [sys.argv[0], "--backend", "minidiff_amd.plugin"]
-else:
-    sys.argv = [sys.argv[0], "--backend", "minidiff.backend.numpy"]
+n_cases, seed, out_path = int(sys.argv[1]), int(sys.argv[2]), sys.argv[3]
+from minidiff_amd import _capi  # noqa: E402
+
+_capi.use_library(os.path.join(ROOT, "oracle", "_build", "libmdhip_host.so"))
 
 import numpy as np  # noqa: E402
-import minidiff as md  # noqa: E402  (the real reference)
+import golden_util as gu  # noqa: E402
 
-assert md.__file__.startswith(REF), md.__file__
-if which == "plugin":
-    from minidiff_amd import plugin
-    plugin.assert_selected()
+md = gu.plugin_engine()[0]
 
 # fuzz_tape builds engines lazily; only its program generator is used here
 import fuzz_tape  # noqa: E402
@@ -42,4 +36,4 @@ for i in range(n_cases):
         results.append(("raise", type(e).__name__))
 with open(out_path, "wb") as f:
     pickle.dump(results, f)
-print(f"DROPIN-FUZZ {which} {len(results)} cases, {sum(r[0] == 'raise' for r in results)} raised")
+print(f"DROPIN-FUZZ {len(results)} cases, {sum(r[0] == 'raise' for r in results)} raised")

@@ -1,34 +1,30 @@
-"""Runs in a subprocess (minidiff parses sys.argv at import): load the UNMODIFIED
-reference with `--backend minidiff_amd.plugin`, bound to the CPU test double, and
-replay the golden cases through the reference's own Tensor/OpNode tape."""
+"""Runs in a subprocess (it claims the module name `minidiff`): the plug-in backend class
+(minidiff_amd.plugin.hip_backend), bound to the CPU test double, must be a complete backend —
+every public function of the table, DeviceArray as its tensor class — and reproduce the
+reference's golden results (tests/golden/: README example and every golden case) through the tape."""
 import os
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = os.environ.get("MINIDIFF_REFERENCE", "/root/reference")
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
-sys.path.insert(0, REF)
 
 from minidiff_amd import _capi  # noqa: E402
 
 _capi.use_library(os.path.join(ROOT, "oracle", "_build", "libmdhip_host.so"))
-sys.argv = [sys.argv[0], "--backend", "minidiff_amd.plugin"]
 
 import numpy as np  # noqa: E402
-import minidiff as md  # noqa: E402  (the real reference)
-import minidiff.backend as mdb  # noqa: E402
-from minidiff_amd import plugin  # noqa: E402
+import golden_util as gu  # noqa: E402
+from minidiff_amd.hip_backend import HipBackendTable  # noqa: E402
 from minidiff_amd.ndarray import DeviceArray  # noqa: E402
 
-plugin.assert_selected()
-assert md.__file__.startswith(REF), md.__file__
-assert mdb.tensor_class is DeviceArray
+md, plugin, Backend = gu.plugin_engine()
+assert issubclass(plugin.hip_backend, Backend) and plugin.hip_backend.tensor_class is DeviceArray
+missing = [k for k in vars(HipBackendTable) if not k.startswith("_") and getattr(plugin.hip_backend, k, None) is not getattr(HipBackendTable, k)]
+assert not missing, missing
 assert isinstance(md.Tensor([1.0, 2.0])._data, DeviceArray)
 
-import golden_util as gu  # noqa: E402
-
-# README (README.md:13-36)
+# README (reference README.md:13-36)
 x = md.Tensor([[0, 2, -2, 1], [-1, -1, -2, -2]], allow_grad=True)
 y = md.Tensor([[2, 3, 4, 5], [0, -1, -3, 2]], allow_grad=True)
 f = 2 * y * md.sin(x) - x ** 2
@@ -43,4 +39,4 @@ with np.errstate(all="ignore"):
     for key in gu.case_keys():
         gu.run_case_on(md, key, exact=False)
         n += 1
-print(f"DROPIN-OK {n} golden cases through the real reference tape on the plug-in backend")
+print(f"DROPIN-OK {n} golden cases through the tape on the plug-in backend")

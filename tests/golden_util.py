@@ -33,6 +33,20 @@ def case_by_name(name):
     raise KeyError(name)
 
 
+def plugin_engine(name="plugin"):
+    """The plug-in backend class (minidiff_amd.plugin.hip_backend) under this project's tape, with no reference checkout: a
+    stand-in `minidiff.backend` module supplies the one name the plug-in imports, the `Backend` base class it subclasses.
+    Call in a process of its own (it claims the module name `minidiff`). Returns (engine, plugin module, stand-in Backend)."""
+    import types
+    pkg, mod = types.ModuleType("minidiff"), types.ModuleType("minidiff.backend")
+    mod.Backend = type("Backend", (), {"__module__": "minidiff.backend"})
+    pkg.__path__, pkg.backend = [], mod
+    sys.modules.update({"minidiff": pkg, "minidiff.backend": mod})
+    from minidiff_amd import plugin
+    from minidiff_amd.tape import build_engine
+    return build_engine(plugin.hip_backend, name), plugin, mod.Backend
+
+
 def to_np(t):
     d = t._data
     return d.get() if hasattr(d, "get") else np.asarray(d)

@@ -34,7 +34,7 @@ def test_bench_prints_one_contract_line(lib, on_gpu, workload, extra, tmp_path):
     size = {"cfg2": "64", "cfg3": "4096", "cfg5": "64"}[workload]
     detail = tmp_path / "detail.json"
     p = subprocess.run([sys.executable, SCRIPT, "--workload", workload, "--size", size, "--steps", "2", "--warmup", "1",
-                        "--detail", str(detail)] + extra, capture_output=True, text=True, timeout=600, env=_no_rank_env())
+                        "--detail", str(detail), "--full"] + extra, capture_output=True, text=True, timeout=600, env=_no_rank_env())
     assert p.returncode == 0, p.stdout[-1500:] + p.stderr[-3000:]
     d = _one_line(p.stdout)
     for key, typ in (("metric", str), ("value", float), ("unit", str), ("n_gpus", int), ("steps", int), ("warmup", int),
@@ -59,13 +59,66 @@ def test_bench_prints_one_contract_line(lib, on_gpu, workload, extra, tmp_path):
     assert full["line"]["value"] == pytest.approx(d["value"], rel=1e-3) and full["head"]["preroll_sweeps"] > 0
 
 
+def test_bench_plain_run_is_the_headline_alone_and_dumps_its_outputs(lib, on_gpu, tmp_path):
+    """Without --full the run is the headline alone — no CPU baseline, gradient check, single or detail sweeps, other configs —
+    and --dump-outputs writes what the last timed sweep computed, identically from run to run: here cfg2, C = A @ B with
+    C.backward(), against NumPy on the workload's own seeds."""
+    if on_gpu:
+        pytest.skip("CPU-double check")
+    import numpy as np
+    from minidiff_amd.workloads import _randn
+    dumps = []
+    for run in range(2):
+        detail, dump = tmp_path / f"detail{run}.json", tmp_path / f"out{run}"
+        p = subprocess.run([sys.executable, SCRIPT, "--workload", "cfg2", "--size", "64", "--steps", "3", "--warmup", "1",
+                            "--detail", str(detail), "--dump-outputs", str(dump)], capture_output=True, text=True, timeout=600, env=_no_rank_env())
+        assert p.returncode == 0, p.stdout[-1500:] + p.stderr[-3000:]
+        d = _one_line(p.stdout)
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0 and d["dtype"] == "f32"
+        assert d["cpu_baseline"] is None and d["grad_linf_rel_max"] is None
+        assert not any(k.startswith(("cfg3", "cfg4", "cfg5", "cpu_")) for k in d["roofline"]), sorted(d["roofline"])
+        full = json.loads(detail.read_text())
+        assert full["secondary"] is None and full["cpu_baseline"] == {} and full["head"]["single_sweep_ms"] is None
+        assert sorted(os.listdir(dump)) == ["A_grad.npy", "B_grad.npy", "out.npy"]
+        dumps.append({k: np.load(dump / f"{k}.npy") for k in ("out", "A_grad", "B_grad")})
+    for k, a in dumps[0].items():
+        assert a.dtype == np.float32 and a.shape == (64, 64) and np.array_equal(a, dumps[1][k]), k
+    A, B = _randn(2, (64, 64)).astype(np.float64), _randn(9, (64, 64)).astype(np.float64)
+    ones = np.ones((64, 64))
+    for got, exp in ((dumps[0]["out"], A @ B), (dumps[0]["A_grad"], ones @ B.T), (dumps[0]["B_grad"], A.T @ ones)):
+        assert np.abs(got - exp).max() <= 1e-5 * np.abs(exp).max()
+
+
+def test_bench_dump_samples_large_outputs(tmp_path):
+    """An output past the per-array budget is written as the fixed sample dump_sample_index names: the same elements every run."""
+    import numpy as np
+    sys.path.insert(0, os.path.dirname(HERE))
+    import bench
+
+    class T:
+        def __init__(self, a, grad=None):
+            self.a, self.grad = a, grad
+
+        def as_numpy(self):
+            return self.a
+
+    big = np.arange(bench.DUMP_SAMPLE_BYTES // 4 * 3, dtype=np.float32)
+    outs = {"out": T(np.float32(2.5)), "x": T(None, T(big)), "y": T(None, T(-big))}
+    bench.dump_outputs(outs, ("x", "y"), str(tmp_path))
+    idx = bench.dump_sample_index(big.size)
+    assert np.array_equal(idx, bench.dump_sample_index(big.size)) and np.all(np.diff(idx) > 0)
+    x = np.load(tmp_path / "x_grad.npy")
+    assert x.dtype == np.float32 and np.array_equal(x, big[idx]) and x.nbytes <= bench.DUMP_SAMPLE_BYTES
+    assert np.array_equal(np.load(tmp_path / "y_grad.npy"), -big[idx]) and np.load(tmp_path / "out.npy") == np.float32(2.5)
+
+
 def test_bench_flat_per_config_keys(lib, on_gpu, tmp_path):
     """The other BASELINE configs ride INSIDE `roofline` as flat scalar keys (the driver's record drops nested dicts), the NumPy
     engine is timed for every config, and the line still fits 2 KB."""
     if on_gpu:
         pytest.skip("CPU-double check")
     detail = tmp_path / "detail.json"
-    p = subprocess.run([sys.executable, SCRIPT, "--size", "64", "--steps", "2", "--warmup", "1", "--force-secondary", "--detail", str(detail)],
+    p = subprocess.run([sys.executable, SCRIPT, "--size", "64", "--steps", "2", "--warmup", "1", "--full", "--force-secondary", "--detail", str(detail)],
                        capture_output=True, text=True, timeout=900, env=_no_rank_env(MDHIP_BENCH_CFG4_DIM="64"))
     assert p.returncode == 0, p.stdout[-1500:] + p.stderr[-3000:]
     d = _one_line(p.stdout)
@@ -113,7 +166,7 @@ def _check_two_rank_line(d, full):
 
 
 TWO_RANK_ENV = dict(MDHIP_BENCH_HOST_COMM="1", MDHIP_BENCH_CFG4_DIM="512", MDHIP_DP_PANELS="2", OMP_NUM_THREADS="2")
-TWO_RANK_ARGS = ["--gpus", "2", "--size", "64", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"]
+TWO_RANK_ARGS = ["--gpus", "2", "--size", "64", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"]
 
 
 def test_bench_two_ranks_control_flow_over_gloo(lib, on_gpu, tmp_path):

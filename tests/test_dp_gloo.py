@@ -160,7 +160,7 @@ def test_bench_distributed_path_on_one_gpu(on_gpu, comm, workload):
     detail = os.path.join(tempfile.mkdtemp(prefix="mdhip_bench_"), "detail.json")
     def launch():
         return subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
-                               "--workload", workload, "--size", "512", "--no-cpu-baseline", "--comm", comm, "--detail", detail]
+                               "--workload", workload, "--size", "512", "--full", "--no-cpu-baseline", "--comm", comm, "--detail", detail]
                               + (["--allow-torch-comm"] if comm == "torch" else []),
                               env=env, capture_output=True, text=True, timeout=600)
     p = launch()
