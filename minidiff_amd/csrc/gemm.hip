@@ -35,6 +35,8 @@
 #include <stdlib.h>
 
 #include <algorithm>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include <hip/hip_ext.h>
@@ -1026,354 +1028,6 @@ __global__ void __launch_bounds__(MD_BLOCK) k_gemm_splitk_sum(const float *__res
   }
 }
 
-// 64 B of zeros in device memory for the ragged direct-to-LDS kernels (GemmArgs::zero); allocated once, never freed
-static const float *md_zero_block() {
-  static const float *z = [] {
-    void *p = nullptr;
-    if (hipMalloc(&p, 64) != hipSuccess || hipMemset(p, 0, 64) != hipSuccess) return (const float *)nullptr;
-    return (const float *)p;
-  }();
-  return z;
-}
-
-// Three LDS buffers (DMA two k-tiles ahead, counted vmcnt at the k-tile boundary) for the 128-row direct-to-LDS tiles: when the grid
-// gives a CU one block at most — the third buffer's 32 KiB cost nothing then, and such grids (2048^3, the 1024-row shards of an 8-rank
-// cfg4, the all-reduce panels) are the ones whose k-tile (1.7 us) is about one DMA round trip: 2048^3 NN 132.9 -> 139.0, NT 132.7 ->
-// 140.1 TFLOP/s (profiles/r3_gemm_nbuf_ab.log). Larger grids keep two buffers and two blocks per CU. option gemm_nbuf = 2 / 3 forces
-// (A/B runs, exactness tests).
-static bool md_gemm_nbuf3(int64_t blocks, int64_t K, int bk) {
-  if (K < 2 * bk) return false;
-  if (const int64_t f = md_opt(MD_OPT_GEMM_NBUF)) return f == 3;
-  return blocks <= MD_NUM_CUS;
-}
-
-// Launch of a main GEMM kernel: with events attached (mdhip_event_attach_next, bench.py) the dispatch itself carries the start / stop
-// timestamps — no marker packets around the kernel.
-static void md_gemm_launch(void (*kernel)(GemmArgs), dim3 grid, int threads, const GemmArgs &ga) {
-  hipEvent_t e0, e1;
-  if (md_prof_take(&e0, &e1)) hipExtLaunchKernelGGL(kernel, grid, dim3((unsigned)threads), 0, md_stream(), e0, e1, 0, ga);
-  else hipLaunchKernelGGL(kernel, grid, dim3((unsigned)threads), 0, md_stream(), ga);
-}
-
-// diagnostic only (MDHIP_GEMM_STAMP=1): one persistent stamp buffer; what the last stamped launch wrote is printed at exit
-struct StampDump {
-  static constexpr size_t kMax = 8192;
-  unsigned long long *dev = nullptr;
-  int bm = 0, bn = 0, bk = 0;
-  size_t blocks = 0;
-  static StampDump &get() { static StampDump d; return d; }
-  unsigned long long *buffer() {
-    if (!dev) (void)hipMalloc((void **)&dev, kMax * 16);
-    return dev;
-  }
-  void note(int m, int n, int k, size_t b) { bm = m; bn = n; bk = k; blocks = b; }
-  ~StampDump() {
-    if (!dev || !blocks) return;
-    std::vector<unsigned long long> h(blocks * 2);
-    if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(h.data(), dev, h.size() * 8, hipMemcpyDeviceToHost) != hipSuccess) return;
-    std::vector<double> ghz, us;
-    for (size_t b = 0; b < blocks; ++b)
-      if (h[2 * b + 1]) { ghz.push_back((double)h[2 * b] / (double)h[2 * b + 1] * 0.1); us.push_back((double)h[2 * b + 1] * 0.01); }
-    std::sort(ghz.begin(), ghz.end());
-    std::sort(us.begin(), us.end());
-    if (!ghz.empty())
-      fprintf(stderr, "[mdhip] last gemm %dx%dx%d: in-kernel clock median %.3f GHz (min %.3f, max %.3f) over %zu blocks; block main loop median %.1f us (min %.1f, p10 %.1f, p90 %.1f, max %.1f)\n",
-              bm, bn, bk, ghz[ghz.size() / 2], ghz.front(), ghz.back(), ghz.size(), us[us.size() / 2], us.front(), us[us.size() / 10], us[us.size() * 9 / 10], us.back());
-  }
-};
-
-template <int BM, int BN, int BK, int WM, int WN, bool A_KC, bool B_KC, int SCHED = 0, int EPI = 0>
-static int launch_cfg(GemmArgs ga, int64_t batch, bool edge) {
-  ga.tiles_m = (int)((ga.M + BM - 1) / BM);
-  ga.tiles_n = (int)((ga.N + BN - 1) / BN);
-  ga.vec_ok = edge ? 0 : 1;  // `edge` on entry = operands not 16-B aligned
-  {
-    const int sh = (int)md_opt(MD_OPT_GEMM_SUPER);
-    ga.super_h = (sh > 1 && ga.tiles_m >= sh && ga.tiles_n >= 8) ? sh : 0;
-  }
-  const bool aligned = !edge;   // (on entry `edge` only says whether the operands are 16-B aligned)
-  edge = edge || (ga.M % BM) || (ga.N % BN) || (ga.K % BK);
-  if constexpr (EPI != 0) {  // whole aligned tiles only; the caller falls back to the plain product otherwise
-    if (edge || batch != 1) return MDHIP_EVALUE;
-    dim3 grid((unsigned)(ga.tiles_m * ga.tiles_n), 1, 1);
-    md_gemm_launch(k_gemm_f32_mfma<BM, BN, BK, WM, WN, A_KC, B_KC, false, false, SCHED, EPI>, grid, 64 * WM * WN, ga);
-    return MD_LAUNCH_CHECK("matmul(f32 mfma, bias+relu epilogue)");
-  }
-  // split-K: a grid that cannot give every CU a block (skinny M or N with a long K, e.g. a
-  // 64 x 4096 batch through a 4096 x 4096 layer) is widened along k; >= 512 k per split
-  const int64_t tiles = (int64_t)ga.tiles_m * ga.tiles_n * batch;
-  int64_t splits = 1;
-  const int splitk_mode = (int)md_opt(MD_OPT_GEMM_SPLITK);
-  if (splitk_mode && BM == 64 && BN == 64 && tiles < MD_NUM_CUS && ga.K >= 1024) {  // (pick_cfg sends such shapes to 64x64)
-    splits = (2 * MD_NUM_CUS + tiles - 1) / tiles;
-    if (splits > ga.K / 512) splits = ga.K / 512;
-    if (splits > 256) splits = 256;   // (64 until round 4: a single 64 x 64 output under k = 10^6 ran on 64 blocks, 13 TFLOP/s)
-  }
-  ga.k_chunk = ga.K;
-  ga.c_split = 0;
-  void *partial = nullptr;
-  GemmArgs out = ga;
-  if (splits > 1) {
-    ga.k_chunk = ((ga.K + splits - 1) / splits + BK - 1) / BK * BK;
-    splits = (ga.K + ga.k_chunk - 1) / ga.k_chunk;
-    MD_TRY(mdhip_alloc((size_t)(splits * batch * ga.M * ga.N) * sizeof(float), &partial));
-    ga.C = (float *)partial;
-    ga.c_bs = ga.M * ga.N; ga.c_ms = ga.N; ga.c_ns = 1;
-    ga.c_split = batch * ga.M * ga.N;
-    edge = edge || (ga.k_chunk % BK) || (ga.K % ga.k_chunk % BK);
-  }
-  dim3 grid((unsigned)(ga.tiles_m * ga.tiles_n), (unsigned)splits, (unsigned)batch);
-  if constexpr (BM == 64 && BN == 64) {
-    if (splits > 1) {
-      if (edge) k_gemm_f32_mfma<BM, BN, BK, WM, WN, A_KC, B_KC, true, true><<<grid, 64 * WM * WN, 0, md_stream()>>>(ga);
-      else k_gemm_f32_mfma<BM, BN, BK, WM, WN, A_KC, B_KC, false, true><<<grid, 64 * WM * WN, 0, md_stream()>>>(ga);
-    }
-  }
-  const bool stamp = md_opt(MD_OPT_GEMM_STAMP) == 1;
-  if (stamp && splits == 1 && !edge && (size_t)grid.x * grid.z <= StampDump::kMax) {
-    ga.stamp = StampDump::get().buffer();   // persistent: no sync behind the launch, the LAST launch's stamps are printed at exit
-    StampDump::get().note(BM, BN, BK, (size_t)grid.x * grid.z);
-  }
-  if (splits == 1) {
-    bool ragged_dma = false;
-    if constexpr (!A_KC && !B_KC && SCHED != 0 && BK >= 32) {
-      // ragged TN: still direct to LDS when every 16-B piece lies wholly inside or outside the operands (M, N multiples of 4)
-      ragged_dma = edge && aligned && md_opt(MD_OPT_GEMM_GLDS) != 0 && ga.a_ms == 1 && ga.b_ns == 1 && !ga.stamp && (ga.M % 4 == 0 || ga.pad_m) && (ga.N % 4 == 0 || ga.pad_n) && ga.a_ks > 0 && ga.b_ks > 0 &&
-                   (ga.zero = md_zero_block()) != nullptr;
-      if (ragged_dma) {
-        // whole k-tiles on the 128-row tiles: predicated lanes + scalar-base addresses (4100 x 4096 x 4100: 104-108 -> 112-124 TFLOP/s);
-        // the 256x256 tile keeps the select form — the predicate's branch around each DMA splits its one scheduling region
-        // (4000^3: 133-137 against 130 with the predicate)
-        // (the predicated form builds its addresses from 32-bit lane offsets: operand strides below 2^26 elements, as in the whole-tile branch)
-        if (ga.K % BK == 0 && BM <= 128 && ga.a_ks < (1ll << 26) && ga.b_ks < (1ll << 26)) md_gemm_launch(k_gemm_f32_tn_glds<BM, BN, BK, WM, WN, 2>, grid, 64 * WM * WN, ga);
-        else md_gemm_launch(k_gemm_f32_tn_glds<BM, BN, BK, WM, WN, 1>, grid, 64 * WM * WN, ga);
-      }
-    }
-    if (ragged_dma) {
-    } else if (edge) md_gemm_launch(k_gemm_f32_mfma<BM, BN, BK, WM, WN, A_KC, B_KC, true>, grid, 64 * WM * WN, ga);
-    else {
-      bool glds = false;
-      if constexpr (!A_KC && !B_KC && SCHED != 0 && BK >= 32) {
-        // TN with whole aligned tiles and 32-deep k-tiles: both operands go direct to LDS (option gemm_glds = 0 keeps the
-        // register-staged kernel: A/B runs). Same-box A/B, profiles/r2_gemm_glds_ab.log: 256x256x32 at
-        // 4096^3 140.1 -> 141.9 TFLOP/s, the 8-wave 128x128x32 at 2048^3 119.0 -> 127.8; the 16-deep 256x128 tile LOSES
-        // (135.7 -> 130.8: its k-tile is too short for a one-tile-ahead DMA) and keeps its registers.
-        glds = md_opt(MD_OPT_GEMM_GLDS) != 0 && ga.a_ms == 1 && ga.b_ns == 1 && !ga.stamp && ga.a_ks > 0 && ga.b_ks > 0 && ga.a_ks < (1ll << 26) && ga.b_ks < (1ll << 26);   // (32-bit lane offsets)
-        if (glds) {
-          if constexpr (3 * (BM + BN) * BK * 4 <= 128 * 1024) {
-            if (md_gemm_nbuf3((int64_t)grid.x * grid.z, ga.K, BK)) {
-              md_gemm_launch(k_gemm_f32_tn_glds<BM, BN, BK, WM, WN, 0, 3>, grid, 64 * WM * WN, ga);
-              return MD_LAUNCH_CHECK("matmul(f32 mfma, direct-to-LDS TN, 3 buffers)");
-            }
-          }
-          md_gemm_launch(k_gemm_f32_tn_glds<BM, BN, BK, WM, WN>, grid, 64 * WM * WN, ga);
-        }
-      }
-      if (!glds) md_gemm_launch(k_gemm_f32_mfma<BM, BN, BK, WM, WN, A_KC, B_KC, false, false, SCHED>, grid, 64 * WM * WN, ga);
-    }
-  }
-  if (splits > 1) {
-    k_gemm_splitk_sum<<<md_grid_for(batch * ga.M * ga.N), MD_BLOCK, 0, md_stream()>>>((const float *)partial, (int)splits, batch, ga.M, ga.N,
-                                                                                   out.C, out.c_bs, out.c_ms, out.c_ns);
-    int rc = MD_LAUNCH_CHECK("matmul(f32 mfma, split-k)");
-    mdhip_free(partial);
-    return rc;
-  }
-  return MD_LAUNCH_CHECK("matmul(f32 mfma)");
-}
-
-// (128x128x32, 8-wave 256x128 and 256x256 tiles were measured and dropped: profiles/r1_gemm_tile_ab.log, r2_gemm_small_grid_ab.log)
-enum { CFG_128x128x16 = 0, CFG_64x64x16, CFG_128x64x16, CFG_256x128x16, CFG_256x256x32, CFG_128x128x32, CFG_128x64x32, CFG_128x128_W8, CFG_COUNT };
-
-// `est` (optional): the model's time for the chosen tile, in units of 512 K / 1e12 seconds (rounds x BM x BN / TFLOP/s)
-static int pick_cfg(const GemmArgs &ga, int64_t batch, bool vector_staged, bool dma_ok = false, double *est = nullptr) {
-  if (est) *est = 64.0 * 64.0 / 120.0;   // (the early returns: one round of the small tile, split-K or not)
-  {  // experiments / exactness tests only (option gemm_cfg)
-    const int64_t v = md_opt(MD_OPT_GEMM_CFG);
-    if (v >= 0 && v < CFG_COUNT) return (int)v;
-  }
-  // Cost model over the production tiles: a CU works through ceil(tiles / CUs) tiles of BM*BN outputs at the rate measured
-  // for that tile on full grids (profiles/r1_gemm_tile_ab.log, r2_gemm_small_grid_ab.log, r2_gemm_glds_ab.log) — big tiles
-  // win on efficiency, small tiles on the partial last round of a grid that does not divide evenly (4097 rows: 3 rounds of
-  // 256x128 against 17 of 64x64, i.e. 0.80x the time). `dma_ok`: operands aligned for the direct-to-LDS kernels, which
-  // take whole tiles and 32-deep k-tiles only; their rates apply to the candidates that divide the problem.
-  if (((ga.M + 63) / 64) * ((ga.N + 63) / 64) * batch < MD_NUM_CUS && ga.K >= 1024) return CFG_64x64x16;  // split-K candidates
-  struct Cand { int cfg, bm, bn; double tf, tf_dma; };   // tf_dma = 0: no direct-to-LDS form of this tile
-  static const Cand cands[] = {{CFG_256x256x32, 256, 256, 0.0, 149.0}, {CFG_256x128x16, 256, 128, 139.0, 0.0}, {CFG_128x128x16, 128, 128, 133.0, 143.0},
-                               {CFG_128x128_W8, 128, 128, 133.0, 143.5}, {CFG_128x64x16, 128, 64, 126.0, 0.0}, {CFG_64x64x16, 64, 64, 120.0, 0.0}};
-  static const Cand cands_tn[] = {{CFG_256x256x32, 256, 256, 140.0, 150.0}, {CFG_256x128x16, 256, 128, 138.0, 0.0}, {CFG_128x128x32, 128, 128, 132.0, 146.0},
-                                  {CFG_128x128_W8, 128, 128, 134.0, 146.0}, {CFG_128x64x32, 128, 64, 126.7, 138.0}, {CFG_64x64x16, 64, 64, 120.0, 0.0}};
-  int best = CFG_64x64x16;
-  double best_t = 1e300;
-  for (int ci = 0; ci < 6; ++ci) {
-    const Cand &c = vector_staged ? cands_tn[ci] : cands[ci];
-    const bool dma = dma_ok && c.tf_dma > 0.0;   // (ragged sizes run the same kernels with zero-filled edges: launch_mfma checks what they need)
-    const double tf = dma ? c.tf_dma : c.tf;
-    if (tf <= 0.0) continue;
-    const int64_t tiles = ((ga.M + c.bm - 1) / c.bm) * ((ga.N + c.bn - 1) / c.bn) * batch;
-    const double rounds = (double)((tiles + MD_NUM_CUS - 1) / MD_NUM_CUS);
-    double t = rounds * c.bm * c.bn / tf;
-    // a lone four-wave block per CU (one wave per SIMD) cannot keep the matrix pipe fed — except the 256x256 tile, whose
-    // rate was measured that way (16 MFMAs per step and wave), and the eight-wave tile
-    // (and the four-wave 128x128x32 direct-to-LDS tile of the TN layout: 127 against 119 TFLOP/s for the eight-wave one at 2048^3)
-    if (tiles <= MD_NUM_CUS && c.cfg != CFG_128x128_W8 && c.cfg != CFG_256x256x32 && !(vector_staged && dma && c.cfg == CFG_128x128x32)) t /= 0.8;
-    if (c.cfg == CFG_256x256x32 && tiles < MD_NUM_CUS) continue;   // (half-empty chip: never the best choice)
-    // the register-staged kernel's guarded edge variant runs ~15 % below its whole-tile rate (4000^3: 112-115 against 133-139);
-    // the direct-to-LDS kernels pay nothing for a ragged edge (zero-filled DMA lanes)
-    if (!dma && ((ga.M % c.bm) || (ga.N % c.bn) || (ga.K % 16))) t /= 0.85;
-    if (t < best_t * 0.999) { best_t = t; best = c.cfg; }   // ties go to the larger tile (listed first)
-  }
-  if (est && best_t < 1e299) *est = best_t;
-  return best;
-}
-
-// NN / NT with whole aligned tiles: the direct-to-LDS kernel for k-contiguous operands (k_gemm_f32_kc_glds); -1 = not applicable
-template <int BM, int BN, int WM, int WN, bool B_KC, int EPI = 0, int BK = 32>
-static int launch_kc_glds(GemmArgs ga, int64_t batch, bool edge) {
-  if (edge || ga.a_ks != 1 || (B_KC ? ga.b_ks != 1 : ga.b_ns != 1)) return -1;
-  // (the per-lane part of a DMA address is a 32-bit byte offset of up to 15 rows / 3 k-rows: strides below 2^26 elements)
-  if (ga.a_ms >= (1ll << 26) || (B_KC ? ga.b_ns : ga.b_ks) >= (1ll << 26) || ga.a_ms < 0 || ga.b_ns < 0 || ga.b_ks < 0) return -1;
-  const bool ragged = (ga.M % BM) || (ga.N % BN) || (ga.K % BK);
-  if (ragged) {   // every 16-B piece wholly inside or outside the operands: K (k-contiguous operands) and N (NN's B) multiples of 4
-    if (EPI != 0 || (ga.K % 4) || (!B_KC && (ga.N % 4)) || (ga.zero = md_zero_block()) == nullptr) return -1;
-  }
-  ga.tiles_m = (int)((ga.M + BM - 1) / BM);
-  ga.tiles_n = (int)((ga.N + BN - 1) / BN);
-  const int sh = (int)md_opt(MD_OPT_GEMM_SUPER);
-  ga.super_h = (sh > 1 && ga.tiles_m >= sh && ga.tiles_n >= 8) ? sh : 0;
-  dim3 grid((unsigned)(ga.tiles_m * ga.tiles_n), 1, (unsigned)batch);
-  const bool stamp = md_opt(MD_OPT_GEMM_STAMP) == 1;
-  if (stamp && (size_t)grid.x * grid.z <= StampDump::kMax) {
-    ga.stamp = StampDump::get().buffer();
-    StampDump::get().note(BM, BN, BK, (size_t)grid.x * grid.z);
-  }
-  if constexpr (EPI == 0) {
-    if (ragged) {
-      if (ga.K % BK == 0 && BM <= 128) md_gemm_launch(k_gemm_f32_kc_glds<BM, BN, BK, WM, WN, B_KC, 0, 2>, grid, 64 * WM * WN, ga);   // (as in launch_cfg's TN branch)
-      else md_gemm_launch(k_gemm_f32_kc_glds<BM, BN, BK, WM, WN, B_KC, 0, 1>, grid, 64 * WM * WN, ga);
-      return MD_LAUNCH_CHECK("matmul(f32 mfma, direct-to-LDS, ragged)");
-    }
-  }
-  if constexpr (EPI == 0 && BM <= 128) {
-    if (md_gemm_nbuf3((int64_t)grid.x * grid.z, ga.K, BK)) {
-      if constexpr (!B_KC) {
-        if (ga.c_vec_rows) {
-          md_gemm_launch(k_gemm_f32_kc_glds<BM, BN, BK, WM, WN, B_KC, 0, 0, 3, true>, grid, 64 * WM * WN, ga);
-          return MD_LAUNCH_CHECK("matmul(f32 mfma, direct-to-LDS, 3 buffers, C^T stores)");
-        }
-      }
-      md_gemm_launch(k_gemm_f32_kc_glds<BM, BN, BK, WM, WN, B_KC, 0, 0, 3>, grid, 64 * WM * WN, ga);
-      return MD_LAUNCH_CHECK("matmul(f32 mfma, direct-to-LDS, 3 buffers)");
-    }
-  }
-  if constexpr (EPI == 0 && !B_KC) {
-    if (ga.c_vec_rows) {
-      md_gemm_launch(k_gemm_f32_kc_glds<BM, BN, BK, WM, WN, B_KC, 0, 0, 2, true>, grid, 64 * WM * WN, ga);
-      return MD_LAUNCH_CHECK("matmul(f32 mfma, direct-to-LDS, C^T stores)");
-    }
-  }
-  md_gemm_launch(k_gemm_f32_kc_glds<BM, BN, BK, WM, WN, B_KC, EPI>, grid, 64 * WM * WN, ga);
-  return MD_LAUNCH_CHECK("matmul(f32 mfma, direct-to-LDS)");
-}
-
-template <bool A_KC, bool B_KC>
-static bool md_gemm_dma_ok(const GemmArgs &ga, bool edge) {
-  // direct-to-LDS kernels: aligned operands whose vector axis has stride 1 (option gemm_glds = 0 keeps
-  // the register-staged kernels: A/B runs and tests)
-  return md_opt(MD_OPT_GEMM_GLDS) != 0 && !edge && !ga.stamp && (A_KC ? ga.a_ks == 1 : ga.a_ms == 1) && (B_KC ? ga.b_ks == 1 : ga.b_ns == 1) &&
-         (A_KC || !B_KC) &&   // (A row-contiguous with B k-contiguous — "TT" — has no such kernel: HipExec::gemm swaps it into NN)
-         // sizes the tiles do not divide: every 16-B piece must lie wholly inside or outside its operand
-         ((A_KC || B_KC) ? ga.K % 4 == 0 : true) && (A_KC || ga.M % 4 == 0 || ga.pad_m) && (B_KC || ga.N % 4 == 0 || ga.pad_n);
-}
-
-template <bool A_KC, bool B_KC>
-static int launch_mfma(const GemmArgs &ga, int64_t batch, bool edge) {
-  const bool dma_ok = md_gemm_dma_ok<A_KC, B_KC>(ga, edge);
-  const int cfg = pick_cfg(ga, batch, !A_KC && !B_KC, dma_ok);
-  if constexpr (A_KC) {
-    if (dma_ok) {
-      int rc = -1;
-      if (cfg == CFG_256x256x32) rc = launch_kc_glds<256, 256, 2, 2, B_KC>(ga, batch, edge);
-      else if (cfg == CFG_128x128_W8) rc = launch_kc_glds<128, 128, 2, 4, B_KC>(ga, batch, edge);   // (64-deep k-tiles: no gain, before and after the addressing change)
-      else if (cfg == CFG_128x128x32 || cfg == CFG_128x128x16) rc = launch_kc_glds<128, 128, 2, 2, B_KC>(ga, batch, edge);
-      if (rc >= 0) return rc;
-    }
-  }
-  switch (cfg) {
-    case CFG_64x64x16: return launch_cfg<64, 64, 16, 2, 2, A_KC, B_KC, 0>(ga, batch, edge);   // (2 MFMAs per step: nothing to interleave with; measured 6 % slower)
-    case CFG_128x64x16: return launch_cfg<128, 64, 16, 2, 2, A_KC, B_KC, 1>(ga, batch, edge);
-    case CFG_256x128x16: return launch_cfg<256, 128, 16, 2, 2, A_KC, B_KC, 1>(ga, batch, edge);
-    // deeper k-tiles for the small tiles of the TN layout: a k-tile of a small tile is too short to cover the
-    // global-load latency of the tile staged two ahead (2048^3 TN: 106 -> 117 TFLOP/s); the k-contiguous
-    // layouts are held back by their transposing LDS stores instead and gain nothing from it
-    case CFG_128x128x32:
-      if constexpr (!A_KC && !B_KC) return launch_cfg<128, 128, 32, 2, 2, A_KC, B_KC, 1>(ga, batch, edge);
-      else return launch_cfg<128, 128, 16, 2, 2, A_KC, B_KC, 1>(ga, batch, edge);
-    case CFG_128x64x32:
-      if constexpr (!A_KC && !B_KC) return launch_cfg<128, 64, 32, 2, 2, A_KC, B_KC, 1>(ga, batch, edge);
-      else return launch_cfg<128, 64, 16, 2, 2, A_KC, B_KC, 1>(ga, batch, edge);
-    case CFG_256x256x32:  // both operands staged with vector LDS stores (TN): one block per CU, half the barriers
-      if constexpr (!A_KC && !B_KC) return launch_cfg<256, 256, 32, 2, 2, A_KC, B_KC, 1>(ga, batch, edge);
-      else return launch_cfg<256, 128, 16, 2, 2, A_KC, B_KC, 1>(ga, batch, edge);
-    // eight waves on ONE 128x128 tile: two waves per SIMD from a single block per CU — for grids of about one tile per CU
-    // (2048^3, the 1024-row shards of cfg4 at 8 ranks), where the four-wave tiles either leave every SIMD one wave
-    // (128x128) or pay for twice the operand traffic (two 128x64 blocks): 2048^3 109-114 -> 118-123 TFLOP/s,
-    // 1024x4096x4096 114-118 -> 122-126 (profiles/r2_gemm_small_grid_ab.log)
-    case CFG_128x128_W8:
-      if constexpr (!A_KC && !B_KC) return launch_cfg<128, 128, 32, 2, 4, A_KC, B_KC, 1>(ga, batch, edge);
-      else return launch_cfg<128, 128, 16, 2, 4, A_KC, B_KC, 1>(ga, batch, edge);
-    default: return launch_cfg<128, 128, 16, 2, 2, A_KC, B_KC, 1>(ga, batch, edge);
-  }
-}
-
-
-// A product whose M and / or N are a few rows past a multiple of the big tile (x.T of a 4097-column matrix: 4097 x 4096 x 4100)
-// pays for its ragged edge with a whole extra ROUND of tiles in a single launch (17 x 17 tiles of 256^2 for 256.3 tiles of work), or
-// runs everything on small tiles. Peeled instead: the aligned main block [0, Mm) x [0, Nm) on the whole-tile kernels, the bottom strip
-// [Mm, M) x [0, N) and the right strip [0, Mm) x [Nm, N) as two small products (thin strips take the split-K route) — three launches
-// on one stream writing disjoint parts of C. Chosen by the same cost model as the tiles, when it beats the single launch by > 3 %.
-template <bool A_KC, bool B_KC>
-static int launch_mfma_peeled(const GemmArgs &ga, int64_t batch, bool edge) {
-  const int mode = (int)md_opt(MD_OPT_GEMM_PEEL);   // 0 never, 1 by the model, 2 whenever there is an edge to peel
-  const int64_t G = 256;
-  const int64_t Mm = ga.M / G * G, Nm = ga.N / G * G, Mr = ga.M - Mm, Nr = ga.N - Nm;
-  if (mode == 0 || edge || ga.stamp || (Mr == 0 && Nr == 0) || Mm == 0 || Nm == 0 || ga.K % 32 || ga.bias) return launch_mfma<A_KC, B_KC>(ga, batch, edge);
-  auto sub = [&](int64_t m0, int64_t m1, int64_t n0, int64_t n1) {
-    GemmArgs x = ga;
-    x.A = ga.A + m0 * ga.a_ms; x.B = ga.B + n0 * ga.b_ns; x.C = ga.C + m0 * ga.c_ms + n0 * ga.c_ns;
-    x.M = m1 - m0; x.N = n1 - n0;
-    if (x.c_vec_rows && (x.M % 4 || ((uintptr_t)x.C & 15))) x.c_vec_rows = 0;
-    return x;
-  };
-  const GemmArgs main_blk = sub(0, Mm, 0, Nm), bottom = sub(Mm, ga.M, 0, ga.N), right = sub(0, Mm, Nm, ga.N);
-  auto al16 = [](const void *p) { return ((uintptr_t)p & 15) == 0; };
-  if (!al16(bottom.A) || !al16(right.B)) return launch_mfma<A_KC, B_KC>(ga, batch, edge);   // (cannot happen for aligned operands: Mm, Nm are multiples of 256)
-  if (mode == 1) {
-    double t_one = 0, t_main = 0, t_b = 0, t_r = 0;
-    pick_cfg(ga, batch, !A_KC && !B_KC, md_gemm_dma_ok<A_KC, B_KC>(ga, edge), &t_one);
-    pick_cfg(main_blk, batch, !A_KC && !B_KC, md_gemm_dma_ok<A_KC, B_KC>(main_blk, edge), &t_main);
-    if (Mr) pick_cfg(bottom, batch, !A_KC && !B_KC, md_gemm_dma_ok<A_KC, B_KC>(bottom, edge), &t_b);
-    if (Nr) pick_cfg(right, batch, !A_KC && !B_KC, md_gemm_dma_ok<A_KC, B_KC>(right, edge), &t_r);
-    const double launch = 6e-6 * 1e12 / (512.0 * (double)ga.K);   // ~6 us per extra launch (prologue / epilogue of a lone small kernel), in model units
-    // the ragged single launch runs ~8 % under the model (4097 x 4096 x 4100: 112 TFLOP/s measured against 123 modelled)
-    if (t_main + t_b + t_r + launch * ((Mr != 0) + (Nr != 0)) > 0.97 * (t_one / 0.92)) return launch_mfma<A_KC, B_KC>(ga, batch, edge);
-  }
-  auto strip = [&](const GemmArgs &x) {   // a strip of up to eight rows / columns is a skinny product (skinny.hip: one read of the big operand)
-    MdGemm sg;
-    sg.batch = batch; sg.M = x.M; sg.N = x.N; sg.K = x.K;
-    sg.a = x.A; sg.b = x.B; sg.c = x.C;
-    sg.a_bs = x.a_bs; sg.a_ms = x.a_ms; sg.a_ks = x.a_ks;
-    sg.b_bs = x.b_bs; sg.b_ks = x.b_ks; sg.b_ns = x.b_ns;
-    sg.c_bs = x.c_bs; sg.c_ms = x.c_ms; sg.c_ns = x.c_ns;
-    const int rc = md_gemm_skinny(sg, MDHIP_F32);
-    return rc >= 0 ? rc : launch_mfma<A_KC, B_KC>(x, batch, edge);
-  };
-  int rc = launch_mfma<A_KC, B_KC>(main_blk, batch, edge);
-  if (rc == MDHIP_OK && Mr) rc = strip(bottom);
-  if (rc == MDHIP_OK && Nr) rc = strip(right);
-  return rc;
-}
-
 
 // ======================= f64: v_mfma_f64_16x16x4_f64 ===========================================
 // Same staging scheme as the f32 kernel (k-major LDS double buffer, registers hold the tile in
@@ -1653,233 +1307,590 @@ __global__ void __launch_bounds__(256, 2) k_gemm_f64_tn_glds(GemmArgs64 g) {
     }
 }
 
-template <int BM, int BN, bool A_KC, bool B_KC>
-static int launch_f64(GemmArgs64 ga, int64_t batch, bool edge) {
-  constexpr int BK = 16;
-  ga.tiles_m = (int)((ga.M + BM - 1) / BM);
-  ga.tiles_n = (int)((ga.N + BN - 1) / BN);
-  ga.vec_ok = edge ? 0 : 1;
-  edge = edge || (ga.M % BM) || (ga.N % BN) || (ga.K % BK);
-  dim3 grid((unsigned)(ga.tiles_m * ga.tiles_n), 1, (unsigned)batch);
-  if (edge) k_gemm_f64_mfma<BM, BN, BK, 2, 2, A_KC, B_KC, true><<<grid, 256, 0, md_stream()>>>(ga);
-  else k_gemm_f64_mfma<BM, BN, BK, 2, 2, A_KC, B_KC, false><<<grid, 256, 0, md_stream()>>>(ga);
-  return MD_LAUNCH_CHECK("matmul(f64 mfma)");
-}
-template <bool A_KC, bool B_KC>
-static int launch_f64_pick(const GemmArgs64 &ga, int64_t batch, bool edge) {
-  const int64_t t128 = ((ga.M + 127) / 128) * ((ga.N + 127) / 128) * batch;
-  if constexpr (!A_KC && !B_KC) {   // TN: both operands row-contiguous -> direct to LDS (k_gemm_f64_tn_glds)
-    const int64_t lim = 1ll << 25;
-    if (md_opt(MD_OPT_GEMM_GLDS) != 0 && !edge && ga.a_ms == 1 && ga.b_ns == 1 && ga.M % 128 == 0 && ga.N % 128 == 0 && ga.K % 16 == 0 && ga.K >= 32 &&
-        t128 >= MD_NUM_CUS && ga.a_ks > 0 && ga.b_ks > 0 && ga.a_ks < lim && ga.b_ks < lim) {
-      GemmArgs64 g2 = ga;
-      g2.tiles_m = (int)(ga.M / 128);
-      g2.tiles_n = (int)(ga.N / 128);
-      dim3 grid((unsigned)(g2.tiles_m * g2.tiles_n), 1, (unsigned)batch);
-      k_gemm_f64_tn_glds<<<grid, 256, 0, md_stream()>>>(g2);
-      return MD_LAUNCH_CHECK("matmul(f64 mfma, direct-to-LDS)");
-    }
-  }
-  if (t128 >= 2 * MD_NUM_CUS) return launch_f64<128, 128, A_KC, B_KC>(ga, batch, edge);
-  return launch_f64<64, 64, A_KC, B_KC>(ga, batch, edge);
+// ======================= host side: plan, then run ===============================================================================
+// plan_gemm lists what a product will run — repacks, kernel launches (layout, tile, staging, buffers, grid, arguments), split-order
+// sums, hand-offs to skinny.hip (which decides for itself: the steps behind a hand-off run when it declines), the generic kernel —
+// and the temporaries, allocating and launching nothing (the cached md_zero_block aside). run_plan allocates, launches, frees.
+
+// 64 B of zeros in device memory for the ragged direct-to-LDS kernels (GemmArgs::zero); allocated once, never freed
+static const float *md_zero_block() {
+  static const float *z = [] {
+    void *p = nullptr;
+    if (hipMalloc(&p, 64) != hipSuccess || hipMemset(p, 0, 64) != hipSuccess) return (const float *)nullptr;
+    return (const float *)p;
+  }();
+  return z;
 }
 
-struct HipExec {
-  template <class T> static int gemm(const MdGemm &g_in) {
-    if (g_in.batch > 65535) return md_fail(MDHIP_EVALUE, "matmul: batch extent %lld exceeds 65535", (long long)g_in.batch);
-    if constexpr (md_same<T, float>::value || md_same<T, double>::value || md_same<T, int32_t>::value || md_same<T, int64_t>::value) {
-      // both sides thin and k long (np.dot of two vectors): k cut over the chip, fixed-order sum of the block partials (skinny.hip)
-      const int rc = md_gemm_longk(g_in, md_dtype_of<T>::value);
-      if (rc >= 0) return rc;
-    }
-    if constexpr (md_same<T, float>::value || md_same<T, double>::value) {
-      // a thin side (matrix x vector, a few columns / rows): HBM-bound streaming kernels (skinny.hip)
-      const int rc = md_gemm_skinny(g_in, md_same<T, float>::value ? MDHIP_F32 : MDHIP_F64);
-      if (rc >= 0) return rc;
-    }
-    if constexpr (md_same<T, float>::value) {
-      // A product whose output is a few dozen 128 x 128 tiles under a LONG k (the weight gradient of a 1000-wide layer over a
-      // 300,000-row batch: 64 tiles, a quarter of the chip, 32-52 TFLOP/s): k is cut into 2-4 ranges that run as the BATCH of one
-      // launch of the ordinary kernels (a range is a batch entry: a_bs / b_bs step along k, c_bs from partial to partial), a short
-      // second launch takes what the equal ranges leave over, and the partials are added in range order (k_gemm_splitk_sum).
-      const int64_t t128 = ((g_in.M + 127) / 128) * ((g_in.N + 127) / 128), t64 = ((g_in.M + 63) / 64) * ((g_in.N + 63) / 64);
-      // (both sides at most 2048: the row panels dp.GradSync cuts a wide weight gradient into — 512 x 4096 — keep the plain product's
-      // summation order, so panelled and un-panelled gradients stay bit-identical)
-      if (md_opt(MD_OPT_GEMM_SPLITK) && g_in.batch == 1 && t64 >= MD_NUM_CUS && t128 <= MD_NUM_CUS / 2 && g_in.M <= 2048 && g_in.N <= 2048 && g_in.K >= 4096 &&
-          g_in.K >= 2 * (g_in.M > g_in.N ? g_in.M : g_in.N)) {
-        int64_t splits = MD_NUM_CUS / t128;
-        if (splits > 4) splits = 4;
-        const int64_t k_chunk = g_in.K / splits / 32 * 32, k_rem = g_in.K - splits * k_chunk;
-        if (splits >= 2 && k_chunk >= 1024) {
-          const int64_t parts = splits + (k_rem > 0 ? 1 : 0);
-          void *partial = nullptr;
-          MD_TRY(mdhip_alloc((size_t)(parts * g_in.M * g_in.N) * sizeof(float), &partial));
-          MdGemm g2 = g_in;
-          g2.batch = splits;
-          g2.K = k_chunk;
-          g2.a_bs = k_chunk * g_in.a_ks;
-          g2.b_bs = k_chunk * g_in.b_ks;
-          g2.c = partial;
-          g2.c_bs = g_in.M * g_in.N; g2.c_ms = g_in.N; g2.c_ns = 1;
-          int rc = gemm<float>(g2);
-          if (rc == MDHIP_OK && k_rem > 0) {
-            MdGemm g3 = g2;
-            g3.batch = 1;
-            g3.K = k_rem;
-            g3.a = (const float *)g_in.a + splits * k_chunk * g_in.a_ks;
-            g3.b = (const float *)g_in.b + splits * k_chunk * g_in.b_ks;
-            g3.c = (float *)partial + splits * g_in.M * g_in.N;
-            rc = gemm<float>(g3);
-          }
-          if (rc == MDHIP_OK) {
-            k_gemm_splitk_sum<<<md_grid_for(g_in.M * g_in.N), MD_BLOCK, 0, md_stream()>>>((const float *)partial, (int)parts, 1, g_in.M, g_in.N, (float *)g_in.c,
-                                                                                     g_in.c_bs, g_in.c_ms, g_in.c_ns);
-            rc = MD_LAUNCH_CHECK("matmul(f32, k ranges as a batch)");
-          }
-          mdhip_free(partial);
-          return rc;
-        }
-      }
-    }
-    MdGemm g = g_in;
-    bool c_rows_unit = false;
-    if constexpr (md_same<T, float>::value) {
-      // "TT" (A^T B^T of two row-major arrays: A unit-stride along m, B along k) has no kernel of its own: C^T = B'A' is the NN
-      // product of the two STORAGES (B' = N x K k-contiguous, A' = K x M row-contiguous), so it runs on the NN direct-to-LDS
-      // kernels with the operands swapped and C addressed through swapped strides; the epilogue then holds four consecutive
-      // elements of a C row per lane and stores them as one 16-B vector (c_vec_rows)
-      if (md_opt(MD_OPT_GEMM_TT_SWAP) != 0 && g.a_ms == 1 && g.a_ks != 1 && g.b_ks == 1 && g.b_ns != 1 && g.M > 1 && g.N > 1 && g.K > 1) {
-        g.a = g_in.b; g.b = g_in.a;
-        g.M = g_in.N; g.N = g_in.M;
-        g.a_bs = g_in.b_bs; g.a_ms = g_in.b_ns; g.a_ks = g_in.b_ks;
-        g.b_bs = g_in.a_bs; g.b_ks = g_in.a_ks; g.b_ns = g_in.a_ms;
-        g.c_ms = g_in.c_ns; g.c_ns = g_in.c_ms;
-        c_rows_unit = g.c_ms == 1 && (g.c_ns & 3) == 0 && (g.c_bs & 3) == 0 && ((uintptr_t)g.c & 15) == 0 && g.M % 4 == 0;
-      }
-      // each operand must have a unit stride along k or along its other axis
-      const bool a_kc = g.a_ks == 1 || g.K == 1, a_mc = g.a_ms == 1 || g.M == 1;
-      const bool b_kc = g.b_ks == 1 || g.K == 1, b_nc = g.b_ns == 1 || g.N == 1;
-      const bool big = g.M * g.N >= 64 * 64 && g.K >= 8;
-      if (big && (a_kc || a_mc) && (b_kc || b_nc) && g.M * g.N < (1ll << 40)) {
-        GemmArgs ga{};  // (zero: no epilogue outputs, no diagnostic stamps)
-        ga.A = (const float *)g.a; ga.B = (const float *)g.b; ga.C = (float *)g.c;
-        ga.M = g.M; ga.N = g.N; ga.K = g.K;
-        ga.a_bs = g.a_bs; ga.a_ms = g.a_ms; ga.a_ks = g.a_ks;
-        ga.b_bs = g.b_bs; ga.b_ks = g.b_ks; ga.b_ns = g.b_ns;
-        ga.c_bs = g.c_bs; ga.c_ms = g.c_ms; ga.c_ns = g.c_ns;
-        ga.tiles_m = ga.tiles_n = 0;  // set per tile config
-        ga.c_vec_rows = c_rows_unit ? 1 : 0;
-        // prefer the layout that allows 16-B loads; A_KC means "vectorise A along k"
-        const bool A_KC = a_kc && !(a_mc && g.a_ks != 1), B_KC = b_kc && !(b_nc && g.b_ks != 1);
-        auto al16 = [](const void *p) { return ((uintptr_t)p & 15) == 0; };
-        bool edge = !al16(g.a) || !al16(g.b);
-        // the vector axis' partner stride must keep rows 16-B aligned
-        edge = edge || ((A_KC ? g.a_ms : g.a_ks) & 3) || ((B_KC ? g.b_ns : g.b_ks) & 3) || (g.a_bs & 3) || (g.b_bs & 3);
-        // Misaligned operands of a LARGE product (an odd leading dimension: x.T of a 4097-column matrix; a view that starts
-        // off a 16-B boundary): one strided copy into an aligned buffer whose rows are padded to a multiple of four elements,
-        // then the direct-to-LDS kernels — 4097 x 4096 x 4100 TN ran at 71 TFLOP/s on the register-staged edge kernel
-        // (DESIGN §9.1). Worth it when the product is >= 50x the copy (2 M N K flop against 8 bytes per copied element).
-        void *tmp_a = nullptr, *tmp_b = nullptr;
-        const bool repack_on = md_opt(MD_OPT_GEMM_REPACK) != 0;
-        if (edge && repack_on && g.batch == 1 && (A_KC || B_KC ? g.K % 4 == 0 : true) && g.M >= 256 && g.N >= 256 && g.K >= 256 && !ga.stamp) {
-          const bool a_bad = !al16(g.a) || ((A_KC ? g.a_ms : g.a_ks) & 3), b_bad = !al16(g.b) || ((B_KC ? g.b_ns : g.b_ks) & 3);
-          auto repack = [](const float *src, int64_t rows, int64_t cols, int64_t row_stride, void **tmp, int64_t *ld) -> int {
-            // rows x cols, unit stride along cols -> rows x ld (ld = cols rounded up to 4; the padding stays unwritten)
-            *ld = (cols + 3) & ~(int64_t)3;
-            MD_TRY(mdhip_alloc((size_t)(rows * *ld) * sizeof(float), tmp));
-            if (rows <= 65535 * 4) {   // (a row per blockIdx.y group: no div / mod per element — the generic strided copy took 89 us for 4096 x 4097)
-              const dim3 grid((unsigned)((cols + 1023) / 1024), (unsigned)((rows + 3) / 4));
-              k_repack_rows<<<grid, 256, 0, md_stream()>>>(src, rows, cols, row_stride, (float *)*tmp, *ld);
-              return MD_LAUNCH_CHECK("matmul(repack)");
-            }
-            mdhip_array sd{}, dd{};
-            sd.data = const_cast<float *>(src); sd.dtype = MDHIP_F32; sd.ndim = 2; sd.shape[0] = rows; sd.shape[1] = cols; sd.strides[0] = row_stride; sd.strides[1] = 1;
-            dd = sd; dd.data = *tmp; dd.strides[0] = *ld;
-            return mdhip_unary(MDHIP_U_COPY, &sd, &dd);
-          };
-          int rc = MDHIP_OK;
-          if (a_bad) {
-            int64_t ld;
-            if (A_KC) { rc = repack(ga.A, g.M, g.K, g.a_ms, &tmp_a, &ld); ga.a_ms = ld; }
-            else { rc = repack(ga.A, g.K, g.M, g.a_ks, &tmp_a, &ld); ga.a_ks = ld; ga.pad_m = 1; }
-            if (rc == MDHIP_OK) ga.A = (const float *)tmp_a;
-          }
-          if (rc == MDHIP_OK && b_bad) {
-            int64_t ld;
-            if (B_KC) { rc = repack(ga.B, g.N, g.K, g.b_ns, &tmp_b, &ld); ga.b_ns = ld; }
-            else { rc = repack(ga.B, g.K, g.N, g.b_ks, &tmp_b, &ld); ga.b_ks = ld; ga.pad_n = 1; }
-            if (rc == MDHIP_OK) ga.B = (const float *)tmp_b;
-          }
-          if (rc != MDHIP_OK) {
-            if (tmp_a) mdhip_free(tmp_a);
-            if (tmp_b) mdhip_free(tmp_b);
-            return rc;
-          }
-          edge = false;
-        }
-        int rc;
-        if (A_KC && B_KC) rc = launch_mfma_peeled<true, true>(ga, g.batch, edge);
-        else if (A_KC && !B_KC) rc = launch_mfma_peeled<true, false>(ga, g.batch, edge);
-        else if (!A_KC && B_KC) rc = launch_mfma_peeled<false, true>(ga, g.batch, edge);
-        else rc = launch_mfma_peeled<false, false>(ga, g.batch, edge);
-        if (tmp_a) mdhip_free(tmp_a);   // stream-ordered: the next user of the block runs after the product
-        if (tmp_b) mdhip_free(tmp_b);
-        return rc;
-      }
-    }
-    if constexpr (md_same<T, double>::value) {
-      const bool a_kc = g.a_ks == 1 || g.K == 1, a_mc = g.a_ms == 1 || g.M == 1;
-      const bool b_kc = g.b_ks == 1 || g.K == 1, b_nc = g.b_ns == 1 || g.N == 1;
-      const int f64_mfma = (int)md_opt(MD_OPT_GEMM_F64_MFMA);
-      if (f64_mfma && g.M * g.N >= 64 * 64 && g.K >= 8 && (a_kc || a_mc) && (b_kc || b_nc) && g.M * g.N < (1ll << 40)) {
-        GemmArgs64 ga;
-        ga.A = (const double *)g.a; ga.B = (const double *)g.b; ga.C = (double *)g.c;
-        ga.M = g.M; ga.N = g.N; ga.K = g.K;
-        ga.a_bs = g.a_bs; ga.a_ms = g.a_ms; ga.a_ks = g.a_ks;
-        ga.b_bs = g.b_bs; ga.b_ks = g.b_ks; ga.b_ns = g.b_ns;
-        ga.c_bs = g.c_bs; ga.c_ms = g.c_ms; ga.c_ns = g.c_ns;
-        ga.tiles_m = ga.tiles_n = 0;
-        const bool A_KC = a_kc && !(a_mc && g.a_ks != 1), B_KC = b_kc && !(b_nc && g.b_ks != 1);
-        auto al16 = [](const void *p) { return ((uintptr_t)p & 15) == 0; };
-        bool edge = !al16(g.a) || !al16(g.b);
-        edge = edge || ((A_KC ? g.a_ms : g.a_ks) & 1) || ((B_KC ? g.b_ns : g.b_ks) & 1) || (g.a_bs & 1) || (g.b_bs & 1);
-        if (A_KC && B_KC) return launch_f64_pick<true, true>(ga, g.batch, edge);
-        if (A_KC && !B_KC) return launch_f64_pick<true, false>(ga, g.batch, edge);
-        if (!A_KC && B_KC) return launch_f64_pick<false, true>(ga, g.batch, edge);
-        return launch_f64_pick<false, false>(ga, g.batch, edge);
-      }
-    }
-    dim3 grid((unsigned)((g.N + 15) / 16), (unsigned)((g.M + 15) / 16), (unsigned)g.batch);
-    if (grid.y > 65535) return md_fail(MDHIP_EVALUE, "matmul: M too large for the generic kernel");
-    k_gemm_generic<T><<<grid, 256, 0, md_stream()>>>(g);
-    return MD_LAUNCH_CHECK("matmul(generic)");
+// Three LDS buffers (DMA two k-tiles ahead, counted vmcnt at the k-tile boundary) for the 128-row direct-to-LDS tiles: when the grid
+// gives a CU one block at most — the third buffer's 32 KiB cost nothing then, and such grids (2048^3, the 1024-row shards of an 8-rank
+// cfg4, the all-reduce panels) are the ones whose k-tile (1.7 us) is about one DMA round trip: 2048^3 NN 132.9 -> 139.0, NT 132.7 ->
+// 140.1 TFLOP/s (profiles/r3_gemm_nbuf_ab.log). Larger grids keep two buffers and two blocks per CU. option gemm_nbuf = 2 / 3 forces
+// (A/B runs, exactness tests).
+static bool md_gemm_nbuf3(int64_t blocks, int64_t K, int bk) {
+  if (K < 2 * bk) return false;
+  if (const int64_t f = md_opt(MD_OPT_GEMM_NBUF)) return f == 3;
+  return blocks <= MD_NUM_CUS;
+}
+
+// Launch of a main GEMM kernel: with events attached (mdhip_event_attach_next, bench.py) the dispatch itself carries the start / stop
+// timestamps — no marker packets around the kernel.
+static void md_gemm_launch(void (*kernel)(GemmArgs), dim3 grid, int threads, const GemmArgs &ga) {
+  hipEvent_t e0, e1;
+  if (md_prof_take(&e0, &e1)) hipExtLaunchKernelGGL(kernel, grid, dim3((unsigned)threads), 0, md_stream(), e0, e1, 0, ga);
+  else hipLaunchKernelGGL(kernel, grid, dim3((unsigned)threads), 0, md_stream(), ga);
+}
+
+// diagnostic only (MDHIP_GEMM_STAMP=1): one persistent stamp buffer; what the last stamped launch wrote is printed at exit
+struct StampDump {
+  static constexpr size_t kMax = 8192;
+  unsigned long long *dev = nullptr;
+  int bm = 0, bn = 0, bk = 0;
+  size_t blocks = 0;
+  static StampDump &get() { static StampDump d; return d; }
+  unsigned long long *buffer() {
+    if (!dev) (void)hipMalloc((void **)&dev, kMax * 16);
+    return dev;
+  }
+  void note(int m, int n, int k, size_t b) { bm = m; bn = n; bk = k; blocks = b; }
+  ~StampDump() {
+    if (!dev || !blocks) return;
+    std::vector<unsigned long long> h(blocks * 2);
+    if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(h.data(), dev, h.size() * 8, hipMemcpyDeviceToHost) != hipSuccess) return;
+    std::vector<double> ghz, us;
+    for (size_t b = 0; b < blocks; ++b)
+      if (h[2 * b + 1]) { ghz.push_back((double)h[2 * b] / (double)h[2 * b + 1] * 0.1); us.push_back((double)h[2 * b + 1] * 0.01); }
+    std::sort(ghz.begin(), ghz.end());
+    std::sort(us.begin(), us.end());
+    if (!ghz.empty())
+      fprintf(stderr, "[mdhip] last gemm %dx%dx%d: in-kernel clock median %.3f GHz (min %.3f, max %.3f) over %zu blocks; block main loop median %.1f us (min %.1f, p10 %.1f, p90 %.1f, max %.1f)\n",
+              bm, bn, bk, ghz[ghz.size() / 2], ghz.front(), ghz.back(), ghz.size(), us[us.size() / 2], us.front(), us[us.size() / 10], us[us.size() * 9 / 10], us.back());
   }
 };
+
+// ---- the f32 tiles -------------------------------------------------------------------------------------------------------------------
+// (128x128x32, 8-wave 256x128 and 256x256 tiles were measured and dropped: profiles/r1_gemm_tile_ab.log, r2_gemm_small_grid_ab.log)
+enum { CFG_128x128x16 = 0, CFG_64x64x16, CFG_128x64x16, CFG_256x128x16, CFG_256x256x32, CFG_128x128x32, CFG_128x64x32, CFG_128x128_W8, CFG_COUNT };
+struct Tile { int bm, bn, bk, wm, wn; };
+// Per CFG and layout family ([0]: NN, NT, TT; [1]: TN): the register-staged tile, its direct-to-LDS form (bm = 0: none) and the
+// model's full-grid rates in TFLOP/s (profiles/r1_gemm_tile_ab.log, r2_gemm_small_grid_ab.log, r2_gemm_glds_ab.log; both 0: not a
+// candidate). TN's small tiles take 32-deep k-tiles to cover the latency of the tile staged two ahead (2048^3 TN: 106 -> 117); the
+// k-contiguous layouts, held back by their transposing LDS stores, gain nothing. 16-deep 256x128 loses direct to LDS (135.7 -> 130.8).
+// W8: eight waves on ONE 128x128 tile, two per SIMD from one block per CU, for grids of about one tile per CU: 2048^3 109-114 ->
+// 118-123 TFLOP/s, 1024x4096x4096 114-118 -> 122-126 (profiles/r2_gemm_small_grid_ab.log).
+struct TileCfg { Tile reg[2], dma[2]; double tf[2], tf_dma[2]; };
+constexpr TileCfg kTiles[CFG_COUNT] = {
+    /* 128x128x16 */ {{{128, 128, 16, 2, 2}, {128, 128, 16, 2, 2}}, {{128, 128, 32, 2, 2}, {}}, {133.0, 0.0}, {143.0, 0.0}},
+    /* 64x64x16   */ {{{64, 64, 16, 2, 2}, {64, 64, 16, 2, 2}}, {{}, {}}, {120.0, 120.0}, {0.0, 0.0}},
+    /* 128x64x16  */ {{{128, 64, 16, 2, 2}, {128, 64, 16, 2, 2}}, {{}, {}}, {126.0, 0.0}, {0.0, 0.0}},
+    /* 256x128x16 */ {{{256, 128, 16, 2, 2}, {256, 128, 16, 2, 2}}, {{}, {}}, {139.0, 138.0}, {0.0, 0.0}},
+    /* 256x256x32 */ {{{256, 128, 16, 2, 2}, {256, 256, 32, 2, 2}}, {{256, 256, 32, 2, 2}, {256, 256, 32, 2, 2}}, {0.0, 140.0}, {149.0, 150.0}},
+    /* 128x128x32 */ {{{128, 128, 16, 2, 2}, {128, 128, 32, 2, 2}}, {{128, 128, 32, 2, 2}, {128, 128, 32, 2, 2}}, {0.0, 132.0}, {0.0, 146.0}},
+    /* 128x64x32  */ {{{128, 64, 16, 2, 2}, {128, 64, 32, 2, 2}}, {{}, {128, 64, 32, 2, 2}}, {0.0, 126.7}, {0.0, 138.0}},
+    /* W8         */ {{{128, 128, 16, 2, 4}, {128, 128, 32, 2, 4}}, {{128, 128, 32, 2, 4}, {128, 128, 32, 2, 4}}, {133.0, 134.0}, {143.5, 146.0}},
+};
+// the order in which the model weighs the candidates: ties go to the larger tile (listed first)
+constexpr int kPickOrder[] = {CFG_256x256x32, CFG_256x128x16, CFG_128x128x16, CFG_128x128x32, CFG_128x128_W8, CFG_128x64x16, CFG_128x64x32, CFG_64x64x16};
+// a third LDS buffer for a direct-to-LDS tile (md_gemm_nbuf3): the 128-row tiles have room for it, 256x256 does not
+constexpr bool lds3_fits(Tile t) { return 3 * (t.bm + t.bn) * t.bk * 4 <= 128 * 1024; }
+
+// `est` (optional): the model's time for the chosen tile, in units of 512 K / 1e12 seconds (rounds x BM x BN / TFLOP/s)
+static int pick_cfg(int64_t M, int64_t N, int64_t K, int64_t batch, bool tn, bool dma_ok, double *est = nullptr) {
+  if (est) *est = 64.0 * 64.0 / 120.0;   // (the early returns: one round of the small tile, split-K or not)
+  {  // experiments / exactness tests only (option gemm_cfg)
+    const int64_t v = md_opt(MD_OPT_GEMM_CFG);
+    if (v >= 0 && v < CFG_COUNT) return (int)v;
+  }
+  // Cost model over the production tiles: a CU works through ceil(tiles / CUs) tiles of BM*BN outputs at the rate measured for that
+  // tile — big tiles win on efficiency, small tiles on the partial last round of a grid that does not divide evenly (4097 rows: 3
+  // rounds of 256x128 against 17 of 64x64, i.e. 0.80x the time). `dma_ok`: operands fit for the direct-to-LDS kernels
+  // (dma_priced), whose rates apply to the tiles that have such a form.
+  if (((M + 63) / 64) * ((N + 63) / 64) * batch < MD_NUM_CUS && K >= 1024) return CFG_64x64x16;  // split-K candidates
+  int best = CFG_64x64x16;
+  double best_t = 1e300;
+  for (const int cfg : kPickOrder) {
+    const TileCfg &c = kTiles[cfg];
+    const bool dma = dma_ok && c.tf_dma[tn] > 0.0;   // (ragged sizes run the same kernels with zero-filled edges: plan_mfma checks what they need)
+    const double tf = dma ? c.tf_dma[tn] : c.tf[tn];
+    if (tf <= 0.0) continue;
+    const Tile t = dma ? c.dma[tn] : c.reg[tn];
+    const int64_t tiles = ((M + t.bm - 1) / t.bm) * ((N + t.bn - 1) / t.bn) * batch;
+    double s = (double)((tiles + MD_NUM_CUS - 1) / MD_NUM_CUS) * t.bm * t.bn / tf;
+    // a lone four-wave block per CU (one wave per SIMD) cannot keep the matrix pipe fed — except the 256x256 tile, whose rate was
+    // measured that way (16 MFMAs per step and wave), and the eight-wave tile
+    // (and the four-wave 128x128x32 direct-to-LDS tile of the TN layout: 127 against 119 TFLOP/s for the eight-wave one at 2048^3)
+    if (tiles <= MD_NUM_CUS && cfg != CFG_128x128_W8 && cfg != CFG_256x256x32 && !(tn && dma && cfg == CFG_128x128x32)) s /= 0.8;
+    if (cfg == CFG_256x256x32 && tiles < MD_NUM_CUS) continue;   // (half-empty chip: never the best choice)
+    // the register-staged kernel's guarded edge variant runs ~15 % below its whole-tile rate (4000^3: 112-115 against 133-139);
+    // the direct-to-LDS kernels pay nothing for a ragged edge (zero-filled DMA lanes)
+    if (!dma && ((M % t.bm) || (N % t.bn) || (K % 16))) s /= 0.85;
+    if (s < best_t * 0.999) { best_t = s; best = cfg; }
+  }
+  if (est && best_t < 1e299) *est = best_t;
+  return best;
+}
+
+// ---- eligibility for the direct-to-LDS kernels -----------------------------------------------------------------------------------
+// a kernel for the layout (NN / NT: k_gemm_f32_kc_glds, TN: k_gemm_f32_tn_glds; "TT" has none, plan_f32 swaps it into NN) with unit
+// strides along the DMA'd vector axes; option gemm_glds = 0 keeps the register-staged kernels
+template <class GA> static bool dma_family(const GA &ga, bool a_kc, bool b_kc) {
+  return md_opt(MD_OPT_GEMM_GLDS) != 0 && (a_kc ? ga.a_ks == 1 : ga.a_ms == 1) && (b_kc ? ga.b_ks == 1 : ga.b_ns == 1) && (a_kc || !b_kc);
+}
+// every 16-B piece of a ragged tile lies wholly inside or outside its operand (or in a repack buffer's row padding: pad_m / pad_n)
+static bool dma_pieces_whole(const GemmArgs &ga, bool a_kc, bool b_kc) {
+  return ((a_kc || b_kc) ? ga.K % 4 == 0 : true) && (a_kc || ga.M % 4 == 0 || ga.pad_m) && (b_kc || ga.N % 4 == 0 || ga.pad_n);
+}
+// strides across the DMA'd rows: >= 0 (k-contiguous kernels) / > 0 (TN), and below `lim` where a lane's address part is a 32-bit byte
+// offset of up to 15 rows / 3 k-rows (kLane32 f32 elements)
+constexpr int64_t kLane32 = 1ll << 26;
+template <class GA> static bool dma_strides(const GA &ga, bool a_kc, bool b_kc, int64_t lim) {
+  if (a_kc) return ga.a_ms >= 0 && ga.b_ns >= 0 && ga.b_ks >= 0 && ga.a_ms < lim && (b_kc ? ga.b_ns : ga.b_ks) < lim;
+  return ga.a_ks > 0 && ga.b_ks > 0 && ga.a_ks < lim && ga.b_ks < lim;
+}
+// what the cost model prices at the DMA rates — without the stride limits, which only the launch checks (plan_mfma, plan_epi)
+static bool dma_priced(const GemmArgs &ga, bool a_kc, bool b_kc, bool aligned) {
+  return aligned && dma_family(ga, a_kc, b_kc) && dma_pieces_whole(ga, a_kc, b_kc);
+}
+// ---- the plan --------------------------------------------------------------------------------------------------------------------------
+enum { ST_REG, ST_DMA, ST_DMA_SELECT, ST_DMA_PRED };   // staging; the ragged DMA forms are the kernels' RAGGED = 1 (select) / 2 (predicated)
+enum { S_LONGK, S_SKINNY, S_REPACK, S_F32, S_SUM, S_F64, S_GENERIC };
+struct GemmStep {   // only the steps in use are initialised (GemmPlan::add)
+  int kind, dtype, cfg, staging, nbuf, splits, epi, skip;   // cfg: kTiles row (S_F64: 0 64x64, 1 128x128, 2 TN direct to LDS); skip: hand-off
+  bool a_kc, b_kc, edge, ct, stamp;                         // ct: C^T-vector stores (c_vec_rows); stamp: clock stamps (diagnostic)
+  Tile tile;
+  dim3 grid;
+  GemmArgs ga;
+  GemmArgs64 ga64;
+  MdGemm g;    // hand-offs, S_GENERIC: the product; S_REPACK: a -> c, rows x cols = M x N, a_ms / c_ms row strides; S_SUM: K partials at a
+  const char *what;
+};
+struct GemmPlan {
+  static constexpr int kMaxSteps = 24, kMaxTmp = 8;   // (k ranges: 2 sub-products x (main + sum + 2 strips x (hand-off + main + sum)) + sum + 2 hand-offs = 19)
+  GemmStep step[kMaxSteps];
+  int n = 0;
+  struct Tmp { size_t bytes; int first, last; } tmp[kMaxTmp];   // allocated before step `first`, freed after step `last` (-1: at the end)
+  int ntmp = 0;
+  GemmStep &add(int kind, const char *what = "") {
+    GemmStep &s = step[n++] = GemmStep{};
+    s.kind = kind; s.what = what; s.nbuf = 2; s.splits = 1;
+    return s;
+  }
+  // temporary t is planned as a HANDLE, (t + 1) << 56 plus a byte offset: above user space, aligned like the allocation (pointer
+  // arithmetic and alignment tests work on it); run_plan rebases it
+  void *temp(size_t bytes, int first = -1) {
+    tmp[ntmp] = {bytes, first < 0 ? n : first, -1};
+    return (void *)((uintptr_t)++ntmp << 56);
+  }
+  void release_after_last_step(const void *h) { tmp[((uintptr_t)h >> 56) - 1].last = n - 1; }
+};
+// Split-order sum of `parts` partial products (both split-K forms): C[b][m][n] = sum over the parts, then the partials are freed
+static void plan_sum(GemmPlan &p, const void *partial, int64_t parts, int64_t batch, int64_t M, int64_t N, void *c, int64_t c_bs, int64_t c_ms,
+                     int64_t c_ns, const char *what) {
+  p.add(S_SUM, what).g = MdGemm{batch, M, N, parts, partial, nullptr, c, 0, 0, 0, 0, 0, 0, c_bs, c_ms, c_ns};
+  p.release_after_last_step(partial);
+}
+// tile counts and the XCD-compact band height (option gemm_super) of a tile over the product; -> the grid's x extent
+static int64_t place(GemmArgs &ga, Tile t) {
+  ga.tiles_m = (int)((ga.M + t.bm - 1) / t.bm);
+  ga.tiles_n = (int)((ga.N + t.bn - 1) / t.bn);
+  const int sh = (int)md_opt(MD_OPT_GEMM_SUPER);
+  ga.super_h = (sh > 1 && ga.tiles_m >= sh && ga.tiles_n >= 8) ? sh : 0;
+  return (int64_t)ga.tiles_m * ga.tiles_n;
+}
+static bool md_gemm_stamped(int64_t blocks) { return md_opt(MD_OPT_GEMM_STAMP) == 1 && blocks <= (int64_t)StampDump::kMax; }
+// One f32 MFMA product: the tile, then the kernel that runs it.
+static void plan_mfma(GemmPlan &p, GemmArgs ga, int64_t batch, bool a_kc, bool b_kc, bool aligned) {
+  const bool tn = !a_kc && !b_kc, priced = dma_priced(ga, a_kc, b_kc, aligned);
+  const int cfg = pick_cfg(ga.M, ga.N, ga.K, batch, tn, priced);
+  GemmStep &s = p.add(S_F32, "matmul(f32 mfma)"); s.cfg = cfg; s.a_kc = a_kc; s.b_kc = b_kc;
+  // NN / NT: k_gemm_f32_kc_glds when the tile has that form and the strides suit its lane offsets. A ragged tile needs the zero block
+  // and, for NN, N a multiple of 4 (this kernel does not read a repacked B's padding: pad_n); otherwise the register-staged tile.
+  const Tile d = kTiles[cfg].dma[0];
+  if (a_kc && priced && d.bm && dma_strides(ga, true, b_kc, kLane32)) {
+    const bool ragged = (ga.M % d.bm) || (ga.N % d.bn) || (ga.K % d.bk);
+    if (!ragged || ((b_kc || ga.N % 4 == 0) && (ga.zero = md_zero_block()) != nullptr)) {
+      const int64_t blocks = place(ga, d) * batch;
+      s.tile = d; s.grid = dim3((unsigned)ga.tiles_m * ga.tiles_n, 1, (unsigned)batch);
+      s.stamp = md_gemm_stamped(blocks);
+      // whole k-tiles on the 128-row tiles: predicated lanes + scalar-base addresses (4100 x 4096 x 4100: 104-108 -> 112-124 TFLOP/s);
+      // the 256x256 tile keeps the select form — the predicate's branch around each DMA splits its one scheduling region
+      // (4000^3: 133-137 against 130 with the predicate)
+      if (ragged) s.staging = (ga.K % d.bk == 0 && d.bm <= 128) ? ST_DMA_PRED : ST_DMA_SELECT;
+      else { s.staging = ST_DMA; s.nbuf = lds3_fits(d) && md_gemm_nbuf3(blocks, ga.K, d.bk) ? 3 : 2; s.ct = !b_kc && ga.c_vec_rows; }
+      s.ga = ga;
+      return;
+    }
+  }
+  const Tile t = s.tile = kTiles[cfg].reg[tn];
+  const int64_t tiles = place(ga, t) * batch;
+  ga.vec_ok = aligned; ga.k_chunk = ga.K;
+  s.edge = !aligned || (ga.M % t.bm) || (ga.N % t.bn) || (ga.K % t.bk);
+  // in-kernel split-K: a grid that cannot give every CU a block (skinny M or N with a long K, e.g. a 64 x 4096 batch through a
+  // 4096 x 4096 layer) is widened along k over grid.y; >= 512 k per split (pick_cfg sends such shapes to 64x64)
+  if (md_opt(MD_OPT_GEMM_SPLITK) && t.bm == 64 && t.bn == 64 && tiles < MD_NUM_CUS && ga.K >= 1024) {
+    int64_t splits = (2 * MD_NUM_CUS + tiles - 1) / tiles;
+    if (splits > ga.K / 512) splits = ga.K / 512;
+    if (splits > 256) splits = 256;   // (64 until round 4: a single 64 x 64 output under k = 10^6 ran on 64 blocks, 13 TFLOP/s)
+    if (splits > 1) {
+      const int64_t n = batch * ga.M * ga.N;
+      ga.k_chunk = ((ga.K + splits - 1) / splits + t.bk - 1) / t.bk * t.bk;
+      splits = (ga.K + ga.k_chunk - 1) / ga.k_chunk;
+      s.edge = s.edge || (ga.k_chunk % t.bk) || (ga.K % ga.k_chunk % t.bk);
+      float *const c = ga.C;
+      const int64_t c_bs = ga.c_bs, c_ms = ga.c_ms, c_ns = ga.c_ns;
+      ga.C = (float *)p.temp((size_t)(splits * n) * sizeof(float), (int)(&s - p.step));   // (allocated before this launch)
+      ga.c_bs = ga.M * ga.N; ga.c_ms = ga.N; ga.c_ns = 1; ga.c_split = n;
+      s.splits = (int)splits; s.ga = ga;
+      s.grid = dim3((unsigned)ga.tiles_m * ga.tiles_n, (unsigned)splits, (unsigned)batch);
+      plan_sum(p, ga.C, splits, batch, ga.M, ga.N, c, c_bs, c_ms, c_ns, "matmul(f32 mfma, split-k)");
+      return;
+    }
+  }
+  s.grid = dim3((unsigned)ga.tiles_m * ga.tiles_n, 1, (unsigned)batch);
+  s.stamp = !s.edge && md_gemm_stamped(tiles);
+  if (tn && kTiles[cfg].dma[1].bm) {
+    if (s.edge) {
+      // ragged TN: still direct to LDS when every 16-B piece lies wholly inside or outside the operands; the select form takes any
+      // positive strides, the predicated one (as on the k-contiguous kernel) 32-bit lane offsets
+      if (aligned && dma_family(ga, false, false) && dma_pieces_whole(ga, false, false) && dma_strides(ga, false, false, INT64_MAX) &&
+          (ga.zero = md_zero_block()) != nullptr)
+        s.staging = (ga.K % t.bk == 0 && t.bm <= 128 && dma_strides(ga, false, false, kLane32)) ? ST_DMA_PRED : ST_DMA_SELECT;
+    } else if (dma_family(ga, false, false) && !s.stamp && dma_strides(ga, false, false, kLane32)) {
+      // whole tiles (stamped launches stay register-staged). Same-box A/B, profiles/r2_gemm_glds_ab.log: 256x256x32 at 4096^3
+      // 140.1 -> 141.9 TFLOP/s, the 8-wave 128x128x32 at 2048^3 119.0 -> 127.8
+      s.staging = ST_DMA;
+      s.nbuf = lds3_fits(t) && md_gemm_nbuf3(tiles, ga.K, t.bk) ? 3 : 2;
+    }
+  }
+  s.ga = ga;
+}
+// A product whose M and / or N are a few rows past a multiple of the big tile (x.T of a 4097-column matrix: 4097 x 4096 x 4100)
+// pays for its ragged edge with a whole extra ROUND of tiles in a single launch (17 x 17 tiles of 256^2 for 256.3 tiles of work), or
+// runs everything on small tiles. Peeled instead: the aligned main block [0, Mm) x [0, Nm) on the whole-tile kernels, the bottom strip
+// [Mm, M) x [0, N) and the right strip [0, Mm) x [Nm, N) as two small products (a strip of up to eight rows / columns is a skinny
+// product, skinny.hip; thin strips take the split-K route) — launches on one stream writing disjoint parts of C. Chosen by the same
+// cost model as the tiles, when it beats the single launch by > 3 %.
+static void plan_peeled(GemmPlan &p, const GemmArgs &ga, int64_t batch, bool a_kc, bool b_kc, bool aligned) {
+  const int mode = (int)md_opt(MD_OPT_GEMM_PEEL);   // 0 never, 1 by the model, 2 whenever there is an edge to peel
+  const int64_t G = 256;
+  const int64_t Mm = ga.M / G * G, Nm = ga.N / G * G, Mr = ga.M - Mm, Nr = ga.N - Nm;
+  if (mode == 0 || !aligned || (Mr == 0 && Nr == 0) || Mm == 0 || Nm == 0 || ga.K % 32) return plan_mfma(p, ga, batch, a_kc, b_kc, aligned);
+  auto sub = [&](int64_t m0, int64_t m1, int64_t n0, int64_t n1) {
+    GemmArgs x = ga;
+    x.A = ga.A + m0 * ga.a_ms; x.B = ga.B + n0 * ga.b_ns; x.C = ga.C + m0 * ga.c_ms + n0 * ga.c_ns;
+    x.M = m1 - m0; x.N = n1 - n0;
+    if (x.c_vec_rows && (x.M % 4 || ((uintptr_t)x.C & 15))) x.c_vec_rows = 0;
+    return x;
+  };
+  const GemmArgs main_blk = sub(0, Mm, 0, Nm), bottom = sub(Mm, ga.M, 0, ga.N), right = sub(0, Mm, Nm, ga.N);
+  if (((uintptr_t)bottom.A & 15) || ((uintptr_t)right.B & 15)) return plan_mfma(p, ga, batch, a_kc, b_kc, aligned);   // (cannot happen for aligned operands: Mm, Nm are multiples of 256)
+  if (mode == 1) {
+    auto est = [&](const GemmArgs &x) { double t = 0; pick_cfg(x.M, x.N, x.K, batch, !a_kc && !b_kc, dma_priced(x, a_kc, b_kc, aligned), &t); return t; };
+    const double launch = 6e-6 * 1e12 / (512.0 * (double)ga.K);   // ~6 us per extra launch (prologue / epilogue of a lone small kernel), in model units
+    // the ragged single launch runs ~8 % under the model (4097 x 4096 x 4100: 112 TFLOP/s measured against 123 modelled)
+    if (est(main_blk) + (Mr ? est(bottom) : 0) + (Nr ? est(right) : 0) + launch * ((Mr != 0) + (Nr != 0)) > 0.97 * (est(ga) / 0.92))
+      return plan_mfma(p, ga, batch, a_kc, b_kc, aligned);
+  }
+  plan_mfma(p, main_blk, batch, a_kc, b_kc, aligned);
+  for (const GemmArgs *x : {Mr ? &bottom : nullptr, Nr ? &right : nullptr}) {
+    if (!x) continue;
+    const int h = p.n;
+    GemmStep &s = p.add(S_SKINNY);
+    s.dtype = MDHIP_F32; s.g = MdGemm{batch, x->M, x->N, x->K, x->A, x->B, x->C, x->a_bs, x->a_ms, x->a_ks, x->b_bs, x->b_ks, x->b_ns, x->c_bs, x->c_ms, x->c_ns};
+    plan_mfma(p, *x, batch, a_kc, b_kc, aligned);
+    p.step[h].skip = p.n - h - 1;
+  }
+}
+// Operand layout (f32 and f64; vec: elements per 16 B). a_kc / b_kc: vectorise A / B along k, else along m / n; mfma: unit strides
+// and size fit the MFMA kernels; aligned: 16-B aligned operands whose vector axis' partner stride and batch steps keep rows aligned.
+struct GemmLayout { bool mfma, a_kc, b_kc, aligned; };
+static GemmLayout md_gemm_layout(const MdGemm &g, int vec) {
+  const bool a_kc = g.a_ks == 1 || g.K == 1, a_mc = g.a_ms == 1 || g.M == 1;
+  const bool b_kc = g.b_ks == 1 || g.K == 1, b_nc = g.b_ns == 1 || g.N == 1;
+  GemmLayout L{g.M * g.N >= 64 * 64 && g.K >= 8 && (a_kc || a_mc) && (b_kc || b_nc) && g.M * g.N < (1ll << 40), a_kc && !(a_mc && g.a_ks != 1),
+               b_kc && !(b_nc && g.b_ks != 1), false};
+  const int64_t m = vec - 1;
+  L.aligned = !((uintptr_t)g.a & 15) && !((uintptr_t)g.b & 15) && !((L.a_kc ? g.a_ms : g.a_ks) & m) && !((L.b_kc ? g.b_ns : g.b_ks) & m) &&
+              !(g.a_bs & m) && !(g.b_bs & m);
+  return L;
+}
+template <class GA> static void md_gemm_args(GA &ga, const MdGemm &g) {   // the product's operands and strides as kernel arguments
+  ga.A = (decltype(ga.A))g.a; ga.B = (decltype(ga.B))g.b; ga.C = (decltype(ga.C))g.c;
+  ga.M = g.M; ga.N = g.N; ga.K = g.K;
+  ga.a_bs = g.a_bs; ga.a_ms = g.a_ms; ga.a_ks = g.a_ks; ga.b_bs = g.b_bs; ga.b_ks = g.b_ks; ga.b_ns = g.b_ns; ga.c_bs = g.c_bs; ga.c_ms = g.c_ms; ga.c_ns = g.c_ns;
+}
+static void plan_generic(GemmPlan &p, const MdGemm &g, int dtype) { GemmStep &s = p.add(S_GENERIC, "matmul(generic)"); s.g = g; s.dtype = dtype; }
+// f32 past the hand-offs and the k ranges: TT swap, repack, peel, MFMA; the generic kernel for what the MFMA kernels do not take
+static void plan_f32(GemmPlan &p, const MdGemm &g_in) {
+  MdGemm g = g_in;
+  bool c_rows_unit = false;
+  // "TT" (A^T B^T of two row-major arrays: A unit-stride along m, B along k) has no kernel of its own: C^T = B'A' is the NN
+  // product of the two STORAGES (B' = N x K k-contiguous, A' = K x M row-contiguous), so it runs on the NN direct-to-LDS
+  // kernels with the operands swapped and C addressed through swapped strides; the epilogue then holds four consecutive
+  // elements of a C row per lane and stores them as one 16-B vector (c_vec_rows)
+  if (md_opt(MD_OPT_GEMM_TT_SWAP) != 0 && g.a_ms == 1 && g.a_ks != 1 && g.b_ks == 1 && g.b_ns != 1 && g.M > 1 && g.N > 1 && g.K > 1) {
+    g.a = g_in.b; g.b = g_in.a; g.M = g_in.N; g.N = g_in.M;
+    g.a_bs = g_in.b_bs; g.a_ms = g_in.b_ns; g.a_ks = g_in.b_ks; g.b_bs = g_in.a_bs; g.b_ks = g_in.a_ks; g.b_ns = g_in.a_ms;
+    g.c_ms = g_in.c_ns; g.c_ns = g_in.c_ms;
+    c_rows_unit = g.c_ms == 1 && (g.c_ns & 3) == 0 && (g.c_bs & 3) == 0 && ((uintptr_t)g.c & 15) == 0 && g.M % 4 == 0;
+  }
+  const GemmLayout L = md_gemm_layout(g, 4);
+  if (!L.mfma) return plan_generic(p, g, MDHIP_F32);
+  GemmArgs ga{};  // (zero: no epilogue outputs, no diagnostic stamps)
+  md_gemm_args(ga, g); ga.c_vec_rows = c_rows_unit ? 1 : 0;
+  bool aligned = L.aligned;
+  // Misaligned operands of a LARGE product (an odd leading dimension: x.T of a 4097-column matrix; a view that starts off a 16-B
+  // boundary): one strided copy into an aligned buffer whose rows are padded to a multiple of four elements, then the direct-to-LDS
+  // kernels — 4097 x 4096 x 4100 TN ran at 71 TFLOP/s on the register-staged edge kernel. Worth it when the product
+  // is >= 50x the copy (2 M N K flop against 8 bytes per copied element).
+  if (!aligned && md_opt(MD_OPT_GEMM_REPACK) != 0 && g.batch == 1 && (L.a_kc || L.b_kc ? g.K % 4 == 0 : true) && g.M >= 256 && g.N >= 256 && g.K >= 256) {
+    // rows x cols, unit stride along cols -> rows x ld (ld = cols rounded up to 4; the padding stays unwritten)
+    auto repack = [&](const float *src, int64_t rows, int64_t cols, int64_t row_stride, int64_t *ld) {
+      *ld = (cols + 3) & ~(int64_t)3;
+      void *dst = p.temp((size_t)(rows * *ld) * sizeof(float));
+      MdGemm &r = p.add(S_REPACK, "matmul(repack)").g;
+      r.a = src; r.c = dst; r.M = rows; r.N = cols; r.a_ms = row_stride; r.c_ms = *ld;
+      return (const float *)dst;
+    };
+    if (((uintptr_t)g.a & 15) || ((L.a_kc ? g.a_ms : g.a_ks) & 3))
+      ga.A = L.a_kc ? repack(ga.A, g.M, g.K, g.a_ms, &ga.a_ms) : (ga.pad_m = 1, repack(ga.A, g.K, g.M, g.a_ks, &ga.a_ks));
+    if (((uintptr_t)g.b & 15) || ((L.b_kc ? g.b_ns : g.b_ks) & 3))
+      ga.B = L.b_kc ? repack(ga.B, g.N, g.K, g.b_ns, &ga.b_ns) : (ga.pad_n = 1, repack(ga.B, g.K, g.N, g.b_ks, &ga.b_ks));
+    aligned = true;
+  }
+  plan_peeled(p, ga, g.batch, L.a_kc, L.b_kc, aligned);
+}
+// A product whose output is a few dozen 128 x 128 tiles under a LONG k (the weight gradient of a 1000-wide layer over a 300,000-row
+// batch: 64 tiles, a quarter of the chip, 32-52 TFLOP/s): k is cut into 2-4 ranges that run as the BATCH of one product (a_bs / b_bs
+// step along k, c_bs from partial to partial), a second product takes the remainder, the partials are added in range order. The
+// sub-products go to plan_f32: no hand-off can take them (t64 >= 256 with both sides <= 2048 puts both over 448: not long-k's <= 128,
+// not skinny's <= 8), nor the k ranges again (a batch of >= 2 ranges, a remainder k < 128).
+static bool plan_kranges(GemmPlan &p, const MdGemm &g) {
+  const int64_t t128 = ((g.M + 127) / 128) * ((g.N + 127) / 128), t64 = ((g.M + 63) / 64) * ((g.N + 63) / 64);
+  // (both sides at most 2048: the row panels dp.GradSync cuts a wide weight gradient into — 512 x 4096 — keep the plain product's
+  // summation order, so panelled and un-panelled gradients stay bit-identical)
+  if (!md_opt(MD_OPT_GEMM_SPLITK) || g.batch != 1 || t64 < MD_NUM_CUS || t128 > MD_NUM_CUS / 2 || g.M > 2048 || g.N > 2048 || g.K < 4096 ||
+      g.K < 2 * (g.M > g.N ? g.M : g.N))
+    return false;
+  const int64_t splits = std::min<int64_t>(MD_NUM_CUS / t128, 4);
+  const int64_t k_chunk = g.K / splits / 32 * 32, k_rem = g.K - splits * k_chunk;
+  if (splits < 2 || k_chunk < 1024) return false;
+  const int64_t parts = splits + (k_rem > 0 ? 1 : 0);
+  float *partial = (float *)p.temp((size_t)(parts * g.M * g.N) * sizeof(float));
+  MdGemm g2 = g;
+  g2.batch = splits; g2.K = k_chunk; g2.a_bs = k_chunk * g.a_ks; g2.b_bs = k_chunk * g.b_ks;
+  g2.c = partial; g2.c_bs = g.M * g.N; g2.c_ms = g.N; g2.c_ns = 1;
+  plan_f32(p, g2);
+  if (k_rem > 0) {
+    MdGemm g3 = g2;
+    g3.batch = 1; g3.K = k_rem;
+    g3.a = (const float *)g.a + splits * k_chunk * g.a_ks; g3.b = (const float *)g.b + splits * k_chunk * g.b_ks; g3.c = partial + splits * g.M * g.N;
+    plan_f32(p, g3);
+  }
+  plan_sum(p, partial, parts, 1, g.M, g.N, g.c, g.c_bs, g.c_ms, g.c_ns, "matmul(f32, k ranges as a batch)");
+  return true;
+}
+static void plan_f64(GemmPlan &p, const MdGemm &g) {
+  const GemmLayout L = md_gemm_layout(g, 2);
+  if (!md_opt(MD_OPT_GEMM_F64_MFMA) || !L.mfma) return plan_generic(p, g, MDHIP_F64);
+  GemmStep &s = p.add(S_F64, "matmul(f64 mfma)");
+  s.a_kc = L.a_kc; s.b_kc = L.b_kc;
+  GemmArgs64 &ga = s.ga64;
+  md_gemm_args(ga, g);
+  const int64_t t128 = ((g.M + 127) / 128) * ((g.N + 127) / 128) * g.batch;
+  // TN, whole 128 x 128 tiles on a full chip: both operands direct to LDS (k_gemm_f64_tn_glds)
+  if (!L.a_kc && !L.b_kc && L.aligned && dma_family(ga, false, false) && g.M % 128 == 0 && g.N % 128 == 0 && g.K % 16 == 0 && g.K >= 32 &&
+      t128 >= MD_NUM_CUS && dma_strides(ga, false, false, kLane32 / 2)) {
+    s.cfg = 2;
+    ga.tiles_m = (int)(g.M / 128);
+    ga.tiles_n = (int)(g.N / 128);
+  } else {
+    s.cfg = t128 >= 2 * MD_NUM_CUS ? 1 : 0;
+    const int64_t bm = s.cfg ? 128 : 64;
+    ga.tiles_m = (int)((g.M + bm - 1) / bm);
+    ga.tiles_n = (int)((g.N + bm - 1) / bm);
+    ga.vec_ok = L.aligned;
+    s.edge = !L.aligned || (g.M % bm) || (g.N % bm) || (g.K % 16);
+  }
+  s.grid = dim3((unsigned)(ga.tiles_m * ga.tiles_n), 1, (unsigned)g.batch);
+}
+static void plan_gemm(GemmPlan &p, const MdGemm &g, int dtype) {
+  // both sides thin and k long (np.dot of two vectors): k cut over the chip, fixed-order sum of the block partials (skinny.hip);
+  // a thin side (matrix x vector, a few columns / rows): HBM-bound streaming kernels (skinny.hip)
+  const int handoffs = dtype == MDHIP_F32 || dtype == MDHIP_F64 ? 2 : 1;
+  for (int h = 0; h < handoffs; ++h) {
+    GemmStep &s = p.add(h ? S_SKINNY : S_LONGK);
+    s.dtype = dtype; s.g = g;
+  }
+  if (dtype == MDHIP_F32 && !plan_kranges(p, g)) plan_f32(p, g);
+  else if (dtype == MDHIP_F64) plan_f64(p, g);
+  else if (dtype != MDHIP_F32) plan_generic(p, g, dtype);
+  for (int h = 0; h < handoffs; ++h) p.step[h].skip = p.n - h - 1;
+}
+// ---- run ---------------------------------------------------------------------------------------------------------------------------
+typedef void (*GemmKernel)(GemmArgs);
+template <class F> static auto with_layout(bool a_kc, bool b_kc, F &&f) {   // f(A_KC, B_KC) as std::bool_constant
+  if (a_kc) return b_kc ? f(std::true_type{}, std::true_type{}) : f(std::true_type{}, std::false_type{});
+  return b_kc ? f(std::false_type{}, std::true_type{}) : f(std::false_type{}, std::false_type{});
+}
+// (C^T stores exist for NN only: CT = !B_KC names the plain kernel for NT)
+template <int BM, int BN, int BK, int WM, int WN, bool B_KC> static GemmKernel kc_kernel(const GemmStep &s) {
+  if (s.epi) { if constexpr (!B_KC) return k_gemm_f32_kc_glds<BM, BN, BK, WM, WN, B_KC, 1>; else return nullptr; }
+  if (s.staging == ST_DMA_SELECT) return k_gemm_f32_kc_glds<BM, BN, BK, WM, WN, B_KC, 0, 1>;
+  if (s.staging == ST_DMA_PRED) return k_gemm_f32_kc_glds<BM, BN, BK, WM, WN, B_KC, 0, 2>;
+  if (s.nbuf == 3) {
+    if constexpr (!lds3_fits(Tile{BM, BN, BK, WM, WN})) return nullptr;
+    else return (!B_KC && s.ct) ? k_gemm_f32_kc_glds<BM, BN, BK, WM, WN, B_KC, 0, 0, 3, !B_KC> : k_gemm_f32_kc_glds<BM, BN, BK, WM, WN, B_KC, 0, 0, 3>;
+  }
+  return (!B_KC && s.ct) ? k_gemm_f32_kc_glds<BM, BN, BK, WM, WN, B_KC, 0, 0, 2, !B_KC> : k_gemm_f32_kc_glds<BM, BN, BK, WM, WN, B_KC>;
+}
+template <int BM, int BN, int BK, int WM, int WN> static GemmKernel tn_kernel(const GemmStep &s) {
+  if (s.staging == ST_DMA_SELECT) return k_gemm_f32_tn_glds<BM, BN, BK, WM, WN, 1>;
+  if (s.staging == ST_DMA_PRED) return k_gemm_f32_tn_glds<BM, BN, BK, WM, WN, 2>;
+  if (s.nbuf == 3) { if constexpr (lds3_fits(Tile{BM, BN, BK, WM, WN})) return k_gemm_f32_tn_glds<BM, BN, BK, WM, WN, 0, 3>; else return nullptr; }
+  return k_gemm_f32_tn_glds<BM, BN, BK, WM, WN>;
+}
+// The kernel of a planned f32 launch. Instantiates exactly what kTiles lists for the layout: nothing the plan cannot name.
+template <int CFG, bool A_KC, bool B_KC> static GemmKernel cfg_kernel(const GemmStep &s) {
+  constexpr bool TN = !A_KC && !B_KC;
+  constexpr Tile R = kTiles[CFG].reg[TN], D = kTiles[CFG].dma[TN];
+  constexpr int SCHED = R.bm == 64 ? 0 : 1;   // (the 64x64 tile has 2 MFMAs per step: nothing to interleave with; measured 6 % slower)
+  if (s.staging != ST_REG) {
+    if constexpr (D.bm != 0 && A_KC) return kc_kernel<D.bm, D.bn, D.bk, D.wm, D.wn, B_KC>(s);
+    else if constexpr (D.bm != 0 && TN) return tn_kernel<D.bm, D.bn, D.bk, D.wm, D.wn>(s);
+    else return nullptr;
+  }
+  if (s.splits > 1) {
+    if constexpr (R.bm == 64 && R.bn == 64) return s.edge ? k_gemm_f32_mfma<64, 64, 16, 2, 2, A_KC, B_KC, true, true> : k_gemm_f32_mfma<64, 64, 16, 2, 2, A_KC, B_KC, false, true>;
+    else return nullptr;
+  }
+  if (s.epi) { if constexpr (A_KC && !B_KC) return k_gemm_f32_mfma<R.bm, R.bn, R.bk, R.wm, R.wn, true, false, false, false, SCHED, 1>; else return nullptr; }
+  return s.edge ? k_gemm_f32_mfma<R.bm, R.bn, R.bk, R.wm, R.wn, A_KC, B_KC, true> : k_gemm_f32_mfma<R.bm, R.bn, R.bk, R.wm, R.wn, A_KC, B_KC, false, false, SCHED>;
+}
+template <bool A_KC, bool B_KC, int... C> static GemmKernel f32_kernel(const GemmStep &s, std::integer_sequence<int, C...>) {
+  GemmKernel k = nullptr;
+  ((s.cfg == C ? (void)(k = cfg_kernel<C, A_KC, B_KC>(s)) : (void)0), ...);
+  return k;
+}
+static GemmKernel f32_kernel(const GemmStep &s) {
+  return with_layout(s.a_kc, s.b_kc, [&](auto a, auto b) { return f32_kernel<decltype(a)::value, decltype(b)::value>(s, std::make_integer_sequence<int, CFG_COUNT>{}); });
+}
+static int run_step(const GemmStep &s, const void *const *tmp, int *skip) {
+  auto at = [&](auto q) {   // a planned pointer with its temporary's handle rebased
+    const uintptr_t u = (uintptr_t)q;
+    return (u >> 56) ? (decltype(q))((char *)tmp[(u >> 56) - 1] + (u & ((1ull << 56) - 1))) : q;
+  };
+  MdGemm g = s.g;
+  g.a = at(g.a); g.b = at(g.b); g.c = at(g.c);
+  switch (s.kind) {
+    case S_LONGK:
+    case S_SKINNY: {
+      const int rc = s.kind == S_LONGK ? md_gemm_longk(g, s.dtype) : md_gemm_skinny(g, s.dtype);
+      *skip = rc < 0 ? 0 : s.skip;
+      return rc < 0 ? MDHIP_OK : rc;
+    }
+    case S_REPACK: {
+      if (g.M <= 65535 * 4) {   // (a row per blockIdx.y group: no div / mod per element — the generic strided copy took 89 us for 4096 x 4097)
+        k_repack_rows<<<dim3((unsigned)((g.N + 1023) / 1024), (unsigned)((g.M + 3) / 4)), 256, 0, md_stream()>>>((const float *)g.a, g.M, g.N, g.a_ms, (float *)g.c, g.c_ms);
+        return MD_LAUNCH_CHECK(s.what);
+      }
+      mdhip_array sd{}, dd{};
+      sd.data = const_cast<void *>(g.a); sd.dtype = MDHIP_F32; sd.ndim = 2; sd.shape[0] = g.M; sd.shape[1] = g.N; sd.strides[0] = g.a_ms; sd.strides[1] = 1;
+      dd = sd; dd.data = g.c; dd.strides[0] = g.c_ms;
+      return mdhip_unary(MDHIP_U_COPY, &sd, &dd);
+    }
+    case S_F32: {
+      GemmArgs ga = s.ga;
+      ga.A = at(ga.A); ga.B = at(ga.B); ga.C = at(ga.C); ga.partial = at(ga.partial);
+      if (s.epi) ga.tickets = md_tickets();
+      const GemmKernel k = f32_kernel(s);
+      if (!k) return md_fail(MDHIP_ERUNTIME, "matmul: no kernel for the planned launch (cfg %d)", s.cfg);
+      if (s.stamp) ga.stamp = StampDump::get().buffer();   // persistent: no sync behind the launch, the LAST launch's stamps are printed at exit
+      if (s.stamp) StampDump::get().note(s.tile.bm, s.tile.bn, s.tile.bk, (size_t)s.grid.x * s.grid.z);
+      if (s.splits > 1) hipLaunchKernelGGL(k, s.grid, dim3(64u * s.tile.wm * s.tile.wn), 0, md_stream(), ga);   // (not the timed launch)
+      else md_gemm_launch(k, s.grid, 64 * s.tile.wm * s.tile.wn, ga);
+      return MD_LAUNCH_CHECK(s.what);
+    }
+    case S_SUM:
+      k_gemm_splitk_sum<<<md_grid_for(g.batch * g.M * g.N), MD_BLOCK, 0, md_stream()>>>((const float *)g.a, (int)g.K, g.batch, g.M, g.N, (float *)g.c,
+                                                                                         g.c_bs, g.c_ms, g.c_ns);
+      return MD_LAUNCH_CHECK(s.what);
+    case S_F64: {
+      auto k = with_layout(s.a_kc, s.b_kc, [&](auto a, auto b) -> void (*)(GemmArgs64) {
+        constexpr bool A = decltype(a)::value, B = decltype(b)::value;
+        if (s.cfg == 1) return s.edge ? k_gemm_f64_mfma<128, 128, 16, 2, 2, A, B, true> : k_gemm_f64_mfma<128, 128, 16, 2, 2, A, B, false>;
+        return s.edge ? k_gemm_f64_mfma<64, 64, 16, 2, 2, A, B, true> : k_gemm_f64_mfma<64, 64, 16, 2, 2, A, B, false>;
+      });
+      hipLaunchKernelGGL(s.cfg == 2 ? k_gemm_f64_tn_glds : k, s.grid, dim3(256), 0, md_stream(), s.ga64);
+      return MD_LAUNCH_CHECK(s.cfg == 2 ? "matmul(f64 mfma, direct-to-LDS)" : s.what);
+    }
+    case S_GENERIC: {
+      const dim3 grid((unsigned)((g.N + 15) / 16), (unsigned)((g.M + 15) / 16), (unsigned)g.batch);
+      if (grid.y > 65535) return md_fail(MDHIP_EVALUE, "matmul: M too large for the generic kernel");
+      switch (s.dtype) {
+        case MDHIP_F32: k_gemm_generic<float><<<grid, 256, 0, md_stream()>>>(g); break;
+        case MDHIP_F64: k_gemm_generic<double><<<grid, 256, 0, md_stream()>>>(g); break;
+        case MDHIP_I32: k_gemm_generic<int32_t><<<grid, 256, 0, md_stream()>>>(g); break;
+        default: k_gemm_generic<int64_t><<<grid, 256, 0, md_stream()>>>(g); break;
+      }
+      return MD_LAUNCH_CHECK(s.what);
+    }
+  }
+  return md_fail(MDHIP_ERUNTIME, "matmul: unknown plan step");
+}
+// Temporaries are allocated before their first step and freed (stream-ordered) after their last; a hand-off that takes its product
+// skips the steps it replaces.
+static int run_plan(const GemmPlan &p) {
+  void *tmp[GemmPlan::kMaxTmp] = {};
+  int rc = MDHIP_OK;
+  for (int i = 0; i < p.n && rc == MDHIP_OK; ++i) {
+    for (int t = 0; t < p.ntmp && rc == MDHIP_OK; ++t) if (p.tmp[t].first == i) rc = mdhip_alloc(p.tmp[t].bytes, &tmp[t]);
+    int skip = 0;
+    if (rc == MDHIP_OK) rc = run_step(p.step[i], tmp, &skip);
+    for (int t = 0; t < p.ntmp; ++t) if (p.tmp[t].last == i && tmp[t]) { mdhip_free(tmp[t]); tmp[t] = nullptr; }
+    i += skip;
+  }
+  for (int t = 0; t < p.ntmp; ++t) if (tmp[t]) mdhip_free(tmp[t]);
+  return rc;
+}
+struct HipExec {
+  template <class T> static int gemm(const MdGemm &g) {
+    if (g.batch > 65535) return md_fail(MDHIP_EVALUE, "matmul: batch extent %lld exceeds 65535", (long long)g.batch);
+    GemmPlan p; plan_gemm(p, g, md_dtype_of<T>::value);
+    return run_plan(p);
+  }
+};
+// mdhip_matmul_bias_relu_sum: the plain product's tile choice (and summation order: a mask recomputed from `a @ b + bias` agrees bit
+// for bit), restricted to tiles that divide the problem; the fused DMA kernel takes whole k-tiles only. false: not covered.
+static bool plan_epi(GemmPlan &p, GemmArgs ga) {
+  const bool priced = dma_priced(ga, true, false, true) && ga.K % 32 == 0;
+  const int cfg = pick_cfg(ga.M, ga.N, ga.K, 1, false, priced);
+  auto divides = [&](Tile t) { return t.bm && ga.M % t.bm == 0 && ga.N % t.bn == 0; };
+  const bool dma = priced && divides(kTiles[cfg].dma[0]);
+  if (dma && !dma_strides(ga, true, false, kLane32)) return false;   // (a tile chosen at its DMA rate does not fall back)
+  int row = dma ? cfg : -1;
+  // else the register-staged tile of the choice, then smaller ones: 128x128 after 256x128, 128x64 after all but 64x64, 64x64
+  for (const int c : {cfg, cfg == CFG_256x128x16 ? (int)CFG_128x128x16 : -1, cfg != CFG_64x64x16 ? (int)CFG_128x64x16 : -1, (int)CFG_64x64x16})
+    if (row < 0 && c >= 0 && divides(kTiles[c].reg[0])) row = c;
+  if (row < 0) return false;
+  const Tile t = dma ? kTiles[row].dma[0] : kTiles[row].reg[0];
+  const int64_t tiles = ((ga.M + t.bm - 1) / t.bm) * ((ga.N + t.bn - 1) / t.bn);
+  ga.sum_out = ga.partial;  // (the caller parked the 0-d result pointer here)
+  ga.partial = (float *)p.temp((size_t)tiles * sizeof(float));
+  GemmStep &s = p.add(S_F32, dma ? "matmul(f32 mfma, direct-to-LDS)" : "matmul(f32 mfma, bias+relu epilogue)");
+  s.cfg = row; s.a_kc = true; s.epi = 1; s.tile = t; s.staging = dma ? ST_DMA : ST_REG; s.grid = dim3((unsigned)tiles, 1, 1);
+  place(ga, t);
+  if (dma) s.stamp = md_gemm_stamped(tiles);
+  else ga.vec_ok = 1;
+  s.ga = ga;
+  return true;
+}
 
 }  // namespace
 
 extern "C" int mdhip_matmul(const mdhip_array *a, const mdhip_array *b, const mdhip_array *c) {
   return md_matmul_dispatch<HipExec>(a, b, c);
 }
-
-namespace {
-template <int BM, int BN, int WM = 2, int WN = 2, bool DMA = false> static int launch_epi(GemmArgs ga) {
-  const int64_t tiles = ((ga.M + BM - 1) / BM) * ((ga.N + BN - 1) / BN);
-  void *partial = nullptr;
-  MD_TRY(mdhip_alloc((size_t)tiles * sizeof(float), &partial));
-  ga.sum_out = ga.partial;  // (the caller parked the 0-d result pointer here)
-  ga.partial = (float *)partial;
-  ga.tickets = md_tickets();
-  int rc;
-  if constexpr (DMA) {
-    rc = launch_kc_glds<BM, BN, WM, WN, false, 1>(ga, 1, false);   // (the caller checked whole tiles and alignment)
-    if (rc < 0) rc = md_fail(MDHIP_EVALUE, "matmul_bias_relu_sum: shape not covered by the fused kernel");
-  }
-  else rc = launch_cfg<BM, BN, 16, WM, WN, true, false, BM == 64 ? 0 : 1, 1>(ga, 1, false);
-  mdhip_free(partial);
-  return rc;
-}
-}  // namespace
 
 // sum_out = sum(where(a @ b + bias > 0, a @ b + bias, 0)) and mask_out = (a @ b + bias > 0), one GEMM pass with the
 // elementwise tail and the reduction in its epilogue. MDHIP_EVALUE ("not fused") for anything but row-major f32
@@ -1913,19 +1924,7 @@ extern "C" int mdhip_matmul_bias_relu_sum(const mdhip_array *a, const mdhip_arra
   ga.bias = (const float *)bias->data;
   ga.mask = (uint8_t *)mask_out->data;
   ga.partial = (float *)sum_out->data;
-  // the plain kernel's tile choice (and with it the plain product's summation order: a mask recomputed from `a @ b + bias`
-  // agrees bit for bit), restricted to the tiles that divide the problem
-  const bool dma_ok = md_opt(MD_OPT_GEMM_GLDS) != 0 && K % 32 == 0;
-  const int cfg = pick_cfg(ga, 1, false, dma_ok);
-  if (dma_ok) {
-    if (cfg == CFG_256x256x32 && M % 256 == 0 && N % 256 == 0) return launch_epi<256, 256, 2, 2, true>(ga);
-    if (cfg == CFG_128x128_W8 && M % 128 == 0 && N % 128 == 0) return launch_epi<128, 128, 2, 4, true>(ga);
-    if ((cfg == CFG_128x128x16 || cfg == CFG_128x128x32) && M % 128 == 0 && N % 128 == 0) return launch_epi<128, 128, 2, 2, true>(ga);
-  }
-  if ((cfg == CFG_256x128x16 || cfg == CFG_256x256x32) && M % 256 == 0 && N % 128 == 0) return launch_epi<256, 128>(ga);
-  if (cfg == CFG_128x128_W8 && M % 128 == 0 && N % 128 == 0) return launch_epi<128, 128, 2, 4>(ga);
-  if (M % 128 == 0 && N % 128 == 0 && (cfg == CFG_128x128x16 || cfg == CFG_128x128x32 || cfg == CFG_256x128x16)) return launch_epi<128, 128>(ga);
-  if (M % 128 == 0 && N % 64 == 0 && cfg != CFG_64x64x16) return launch_epi<128, 64>(ga);
-  if (M % 64 == 0 && N % 64 == 0) return launch_epi<64, 64>(ga);
-  return md_fail(MDHIP_EVALUE, "matmul_bias_relu_sum: shape not covered by the fused kernel");
+  GemmPlan p;
+  if (!plan_epi(p, ga)) return md_fail(MDHIP_EVALUE, "matmul_bias_relu_sum: shape not covered by the fused kernel");
+  return run_plan(p);
 }

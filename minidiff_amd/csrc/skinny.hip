@@ -1,5 +1,5 @@
 // skinny.hip — matrix products with one THIN side: matrix x vector, vector x matrix, up to eight columns / rows, and the
-// bottom / right strips of a peeled ragged product (gemm.hip, launch_mfma_peeled).
+// bottom / right strips of a peeled ragged product (gemm.hip, plan_peeled).
 //
 // Serves reference minidiff/backend/numpy.py:84 (np.matmul) as called by minidiff/ops/definitions.py:487-492 when an operand is a
 // vector or a few columns wide. Such a product is HBM-bound — 2 flop per 4-byte element of the big operand, which is read exactly

@@ -290,7 +290,7 @@ def test_direct_to_lds_gemm_random_aligned_shapes(lib, on_gpu):
 def test_tt_products_run_as_the_swapped_nn_product(lib, on_gpu, mdopt):
     """x.T @ y.T of two row-major arrays ("TT") has no kernel of its own: C^T = y x is the NN product of the two storages, run on
     the direct-to-LDS NN kernels with C addressed through swapped strides and stored as 16-B vectors along rows (gemm.hip,
-    HipExec::gemm). Integer-valued operands: every product must EQUAL NumPy's and the register-staged TT kernel's
+    plan_f32). Integer-valued operands: every product must EQUAL NumPy's and the register-staged TT kernel's
     (option gemm_tt_swap = 0); whole tiles of every size class, three-buffer grids, batches, ragged sizes."""
     assert on_gpu
     from minidiff_amd import ndarray as nd
@@ -319,7 +319,7 @@ def test_tt_products_run_as_the_swapped_nn_product(lib, on_gpu, mdopt):
 def test_misaligned_operands_of_large_products_are_repacked(lib, on_gpu, mdopt):
     """Odd leading dimensions (x.T of a matrix with an odd column count) and views that start off a 16-byte boundary: large
     products copy such an operand once into an aligned, row-padded buffer and take the direct-to-LDS kernels (gemm.hip,
-    HipExec::gemm); the padding must never reach C. Integer-valued operands: the products must EQUAL NumPy's, in every layout,
+    plan_f32); the padding must never reach C. Integer-valued operands: the products must EQUAL NumPy's, in every layout,
     with the repack on and off."""
     assert on_gpu
     from minidiff_amd import ndarray as nd
@@ -356,7 +356,7 @@ def test_misaligned_operands_of_large_products_are_repacked(lib, on_gpu, mdopt):
 
 def test_peeled_ragged_products(lib, on_gpu, mdopt):
     """A product a few rows / columns past a multiple of 256 runs as an aligned main block on the whole-tile kernels plus a bottom
-    and a right strip (gemm.hip, launch_mfma_peeled). Forced here (option gemm_peel = 2) on every layout, with thin and fat strips,
+    and a right strip (gemm.hip, plan_peeled). Forced here (option gemm_peel = 2) on every layout, with thin and fat strips,
     batches, odd leading dimensions (repacked operands) and K that the peel refuses: integer-valued operands, the products must
     EQUAL NumPy's and the single-launch result (gemm_peel = 0)."""
     assert on_gpu

@@ -582,7 +582,7 @@ def test_mid_length_arg_rows_gpu(lib, on_gpu):
 @pytest.mark.gpu
 def test_few_tiles_long_k_products_gpu(lib, on_gpu):
     """A few dozen output tiles under a long k (the weight gradient of a 1000-wide layer over a large batch): k ranges run as the batch
-    of one launch, partials added in range order (csrc/gemm.hip HipExec::gemm). All three layouts, a k that does not divide (the
+    of one launch, partials added in range order (csrc/gemm.hip plan_kranges). All three layouts, a k that does not divide (the
     remainder launch), integer-valued operands exact, a strided destination."""
     assert on_gpu
     from minidiff_amd import ndarray as nd
