@@ -55,11 +55,14 @@ enum {
   MDHIP_I64 = 2,
   MDHIP_F32 = 3,
   MDHIP_F64 = 4,
-  MDHIP_NUM_DTYPES = 5, /* the COMPUTE dtypes: every arithmetic entry point takes these and only these */
+  MDHIP_NUM_DTYPES = 5, /* the COMPUTE dtypes: the tuned wide kernels compute in these */
   /* Storage-only dtypes — the other names of the reference table (numpy.py:188-200: float16, uint8/16/32/64, int8/16).
-   * Arrays of these types live in device memory and are moved by mdhip_h2d / mdhip_d2h and converted by mdhip_convert;
-   * arithmetic on them is promote -> compute in a wide type -> demote, decided on the host (what NumPy's own float16
-   * loops do; integer wrap-around falls out of the truncating conversion). */
+   * Arrays of these types live in device memory, are moved by mdhip_h2d / mdhip_d2h and converted by mdhip_convert, and are
+   * computed on DIRECTLY by mdhip_unary / mdhip_binary / mdhip_where / mdhip_reduce (each operand read in its own type, the
+   * arithmetic in the loop dtype's carrier: int32 / int64 / uint64 / float32) and by mdhip_matmul for the float16, int8 and
+   * uint8 triples. What no entry point takes (products of mixed or other narrow dtypes, mean / std) the host composes as
+   * promote -> compute in a wide type -> demote (what NumPy's own float16 loops do; integer wrap-around falls out of the
+   * truncating conversion). */
   MDHIP_I8 = 5,
   MDHIP_I16 = 6,
   MDHIP_U8 = 7,
@@ -258,7 +261,9 @@ int mdhip_var(const mdhip_array *x, const mdhip_array *out, int32_t axis, int64_
 /* C[b] = A[b] @ B[b]: A (batch.., M, K), B (batch.., K, N), C (batch.., M, N),
  * any strides (NN / NT / TN arrive as strided views: definitions.py:487-492).
  * Arrays are passed 3-D (batch, rows, cols); batch stride 0 broadcasts.
- * f32 and f64 run on MFMA; other dtypes take the generic kernel. */
+ * f32 and f64 run on MFMA; int32 / int64 take the generic kernel. Storage-only triples: float16 @ float16 -> float16
+ * (float32 accumulation, one rounding) and int8 @ int8 -> int8, uint8 @ uint8 -> uint8 (the low byte of the exact sum) run
+ * on the low-precision MFMA (gemm_narrow.hip); no other storage-only dtype is accepted. */
 int mdhip_matmul(const mdhip_array *a, const mdhip_array *b, const mdhip_array *c);
 /* GEMM with the elementwise tail and the reduction of BASELINE's MLP forward in its epilogue (lazy mode,
  * minidiff_amd/ndarray.py recognises the pattern): for row-major float32 a (M x K), b (K x N), bias (N)

@@ -46,6 +46,7 @@
 extern "C" int mdhip_alloc(size_t, void **);
 extern "C" int mdhip_unary(int, const mdhip_array *, const mdhip_array *);
 extern "C" int mdhip_free(void *);
+extern "C" int mdhip_convert(const mdhip_array *, const mdhip_array *);
 
 namespace {
 
@@ -1453,19 +1454,22 @@ static bool dma_priced(const GemmArgs &ga, bool a_kc, bool b_kc, bool aligned) {
 }
 // ---- the plan --------------------------------------------------------------------------------------------------------------------------
 enum { ST_REG, ST_DMA, ST_DMA_SELECT, ST_DMA_PRED };   // staging; the ragged DMA forms are the kernels' RAGGED = 1 (select) / 2 (predicated)
-enum { S_LONGK, S_SKINNY, S_REPACK, S_F32, S_SUM, S_F64, S_GENERIC };
+enum { S_LONGK, S_SKINNY, S_REPACK, S_F32, S_SUM, S_F64, S_GENERIC, S_NMFMA, S_NGENERIC, S_NCONV };   // S_N*: float16 / int8 / uint8
 struct GemmStep {   // only the steps in use are initialised (GemmPlan::add)
   int kind, dtype, cfg, staging, nbuf, splits, epi, skip;   // cfg: kTiles row (S_F64: 0 64x64, 1 128x128, 2 TN direct to LDS); skip: hand-off
+  int dtype_to;                                             // S_NCONV: the destination's dtype
   bool a_kc, b_kc, edge, ct, stamp;                         // ct: C^T-vector stores (c_vec_rows); stamp: clock stamps (diagnostic)
   Tile tile;
   dim3 grid;
   GemmArgs ga;
   GemmArgs64 ga64;
-  MdGemm g;    // hand-offs, S_GENERIC: the product; S_REPACK: a -> c, rows x cols = M x N, a_ms / c_ms row strides; S_SUM: K partials at a
+  MdGemm g;    // hand-offs, S_GENERIC, S_N*: the product; S_REPACK: a -> c, rows x cols = M x N, a_ms / c_ms row strides; S_SUM: K partials at a;
+               // S_NCONV: a (dtype) -> c (dtype_to), batch x M x N with strides a_bs / a_ms / a_ks and c_bs / c_ms / c_ns
   const char *what;
 };
 struct GemmPlan {
-  static constexpr int kMaxSteps = 24, kMaxTmp = 8;   // (k ranges: 2 sub-products x (main + sum + 2 strips x (hand-off + main + sum)) + sum + 2 hand-offs = 19)
+  static constexpr int kMaxSteps = 32, kMaxTmp = 12;   // (k ranges: 2 sub-products x (main + sum + 2 strips x (hand-off + main + sum)) + sum + 2 hand-offs = 19;
+                                                       // a widened narrow product: 3 conversions around that, 3 more temporaries)
   GemmStep step[kMaxSteps];
   int n = 0;
   struct Tmp { size_t bytes; int first, last; } tmp[kMaxTmp];   // allocated before step `first`, freed after step `last` (-1: at the end)
@@ -1717,7 +1721,7 @@ static void plan_f64(GemmPlan &p, const MdGemm &g) {
 static void plan_gemm(GemmPlan &p, const MdGemm &g, int dtype) {
   // both sides thin and k long (np.dot of two vectors): k cut over the chip, fixed-order sum of the block partials (skinny.hip);
   // a thin side (matrix x vector, a few columns / rows): HBM-bound streaming kernels (skinny.hip)
-  const int handoffs = dtype == MDHIP_F32 || dtype == MDHIP_F64 ? 2 : 1;
+  const int handoffs = dtype == MDHIP_F32 || dtype == MDHIP_F64 ? 2 : 1, h0 = p.n;   // (h0 > 0: the wide product of plan_widened)
   for (int h = 0; h < handoffs; ++h) {
     GemmStep &s = p.add(h ? S_SKINNY : S_LONGK);
     s.dtype = dtype; s.g = g;
@@ -1725,7 +1729,83 @@ static void plan_gemm(GemmPlan &p, const MdGemm &g, int dtype) {
   if (dtype == MDHIP_F32 && !plan_kranges(p, g)) plan_f32(p, g);
   else if (dtype == MDHIP_F64) plan_f64(p, g);
   else if (dtype != MDHIP_F32) plan_generic(p, g, dtype);
-  for (int h = 0; h < handoffs; ++h) p.step[h].skip = p.n - h - 1;
+  for (int h = h0; h < h0 + handoffs; ++h) p.step[h].skip = p.n - h - 1;
+}
+// ---- float16 / int8 / uint8 -------------------------------------------------------------------------------------------------------
+// What the MFMA kernels of gemm_narrow.hip take, per operand: a unit-stride k axis (the KC image; K a multiple of the 16-B chunk) or a
+// unit-stride row axis (the MN image; the rows a multiple of it), a 16-B aligned start, row / k-row and batch steps that are multiples of
+// 16 B, and eight rows' step within a 32-bit lane offset.
+struct NarrowLayout { bool ok, a_kc, b_kc, edge; };
+static NarrowLayout md_narrow_layout(const MdGemm &g, int esz) {
+  const int64_t epc = 16 / esz;
+  auto side = [&](const void *p, int64_t rows, int64_t rs, int64_t ks, int64_t bs, bool *kc) {
+    if (((uintptr_t)p & 15) || ((bs * esz) & 15)) return false;
+    int64_t step;
+    if (ks == 1 && g.K % epc == 0) { *kc = true; step = rs; }
+    else if (rs == 1 && rows % epc == 0) { *kc = false; step = ks; }
+    else return false;
+    return step > 0 && !((step * esz) & 15) && step * esz * 8 < (1ll << 31);
+  };
+  NarrowLayout L{false, false, false, false};
+  L.ok = side(g.a, g.M, g.a_ms, g.a_ks, g.a_bs, &L.a_kc) && side(g.b, g.N, g.b_ns, g.b_ks, g.b_bs, &L.b_kc);
+  L.edge = (g.M % 128) || (g.N % 128) || (g.K % (128 / esz));
+  return L;
+}
+// the shapes md_gemm_longk (skinny.hip) takes: few outputs under a long k
+static bool md_longk_shape(const MdGemm &g) {
+  const int64_t big = g.M > g.N ? g.M : g.N;
+  return g.M <= 128 && g.N <= 128 && (big <= 8 ? g.K >= 512 : (g.K >= 8192 && g.K >= 64 * big));
+}
+// The route the product had before it ran natively — convert both operands to the wide type (float32 / int32: the same bits of the
+// result), the wide plan with its hand-offs (skinny / long-k streaming kernels, split-k), convert the result back — for the shapes whose
+// wide kernels beat one launch of the narrow ones: thin or long-k products, unaligned operands of a large float16 product.
+static void plan_widened(GemmPlan &p, const MdGemm &g, int dtype, int wide) {
+  const size_t wsz = md_dtype_size(wide);
+  const int64_t ba = g.a_bs ? g.batch : 1, bb = g.b_bs ? g.batch : 1, M = g.M, N = g.N, K = g.K;
+  auto conv = [&](const void *src, int from, int64_t nb, int64_t rows, int64_t cols, int64_t bs, int64_t rs, int64_t cs, void *dst, int to,
+                  int64_t dbs, int64_t drs, int64_t dcs) {
+    GemmStep &s = p.add(S_NCONV, "matmul(narrow, conversion)");
+    s.dtype = from; s.dtype_to = to;
+    s.g = MdGemm{nb, rows, cols, 0, src, nullptr, dst, bs, rs, cs, 0, 0, 0, dbs, drs, dcs};
+  };
+  MdGemm w = g;
+  w.a = p.temp((size_t)(ba * M * K) * wsz);
+  conv(g.a, dtype, ba, M, K, g.a_bs, g.a_ms, g.a_ks, const_cast<void *>(w.a), wide, M * K, K, 1);
+  w.b = p.temp((size_t)(bb * K * N) * wsz);
+  conv(g.b, dtype, bb, K, N, g.b_bs, g.b_ks, g.b_ns, const_cast<void *>(w.b), wide, K * N, N, 1);
+  w.c = p.temp((size_t)(g.batch * M * N) * wsz);
+  w.a_bs = ba > 1 ? M * K : 0; w.a_ms = K; w.a_ks = 1;
+  w.b_bs = bb > 1 ? K * N : 0; w.b_ks = N; w.b_ns = 1;
+  w.c_bs = M * N; w.c_ms = N; w.c_ns = 1;
+  plan_gemm(p, w, wide);
+  conv(w.c, wide, g.batch, M, N, M * N, N, 1, g.c, dtype, g.c_bs, g.c_ms, g.c_ns);
+}
+// float16 / int8 / uint8: the MFMA kernels (gemm_narrow.hip) for what they take, unless the product is thin (<= 8 rows or columns: the
+// streaming kernels of skinny.hip after a conversion) or float16 of a few tiles under a long k (split-k in the wide plan); small or odd-stride
+// products on the generic narrow kernel; the rest the widened route.
+static void plan_narrow(GemmPlan &p, const MdGemm &g, int dtype) {
+  const int esz = dtype == MDHIP_F16 ? 2 : 1, wide = dtype == MDHIP_F16 ? MDHIP_F32 : MDHIP_I32;
+  const NarrowLayout L = md_narrow_layout(g, esz);
+  const int64_t blocks = ((g.M + 127) / 128) * ((g.N + 127) / 128) * g.batch;
+  // A float16 product of a few tiles runs its whole k loop on a few CUs (no k split: ~10.4 us per 1024 of k, whatever the tile
+  // count up to a full chip), the widened route splits k over the chip for ~25 us of fixed cost plus ~(1.6 + 0.5 tiles) us per 1024
+  // of k (fit to profiles/gemm_bench_narrow_few_tiles_before.txt, NN / NT / TN of 128^2 .. 1024^2 x 1024 .. 8192): the wide route when it
+  // is the faster one — 1 tile from k ~ 2.7 K, 4 tiles from ~3.4 K, 9 from ~5 K, never from 18 tiles on.
+  const double kk = (double)g.K / 1024.0;
+  const bool thin = g.M <= 8 || g.N <= 8, few_long = esz == 2 && kk * (8.8 - 0.5 * (double)blocks) > 22.5;
+  if (L.ok && g.K > 0 && !thin && !few_long && !(esz == 1 && md_longk_shape(g))) {
+    GemmStep &s = p.add(S_NMFMA, esz == 2 ? "matmul(f16 mfma)" : "matmul(i8 mfma)");
+    s.dtype = dtype; s.g = g; s.a_kc = L.a_kc; s.b_kc = L.b_kc; s.edge = L.edge;
+    return;
+  }
+  const bool small = g.K <= 512 && g.batch * g.M * g.N * g.K <= (1ll << 22);
+  // (int8 / uint8 ran on the generic int64 kernel before: the narrow one is the same loop on 1-byte loads; long-k shapes keep long-k)
+  if (g.K == 0 || small || (esz == 1 && !md_longk_shape(g))) {
+    GemmStep &s = p.add(S_NGENERIC, "matmul(narrow generic)");
+    s.dtype = dtype; s.g = g;
+    return;
+  }
+  plan_widened(p, g, dtype, wide);
 }
 // ---- run ---------------------------------------------------------------------------------------------------------------------------
 typedef void (*GemmKernel)(GemmArgs);
@@ -1824,6 +1904,21 @@ static int run_step(const GemmStep &s, const void *const *tmp, int *skip) {
       hipLaunchKernelGGL(s.cfg == 2 ? k_gemm_f64_tn_glds : k, s.grid, dim3(256), 0, md_stream(), s.ga64);
       return MD_LAUNCH_CHECK(s.cfg == 2 ? "matmul(f64 mfma, direct-to-LDS)" : s.what);
     }
+    case S_NMFMA: {
+      const void *zero = s.edge ? md_zero_block() : nullptr;
+      if (s.edge && !zero) return md_fail(MDHIP_EMEMORY, "matmul: zero block");
+      return md_gemm_narrow_mfma(g, s.dtype, s.a_kc, s.b_kc, s.edge, zero);
+    }
+    case S_NGENERIC: return md_gemm_narrow_generic(g, s.dtype);
+    case S_NCONV: {
+      mdhip_array sd{}, dd{};
+      sd.data = const_cast<void *>(g.a); sd.dtype = s.dtype; sd.ndim = 3;
+      sd.shape[0] = g.batch; sd.shape[1] = g.M; sd.shape[2] = g.N;
+      sd.strides[0] = g.a_bs; sd.strides[1] = g.a_ms; sd.strides[2] = g.a_ks;
+      dd = sd; dd.data = g.c; dd.dtype = s.dtype_to;
+      dd.strides[0] = g.c_bs; dd.strides[1] = g.c_ms; dd.strides[2] = g.c_ns;
+      return mdhip_convert(&sd, &dd);
+    }
     case S_GENERIC: {
       const dim3 grid((unsigned)((g.N + 15) / 16), (unsigned)((g.M + 15) / 16), (unsigned)g.batch);
       if (grid.y > 65535) return md_fail(MDHIP_EVALUE, "matmul: M too large for the generic kernel");
@@ -1857,6 +1952,12 @@ struct HipExec {
   template <class T> static int gemm(const MdGemm &g) {
     if (g.batch > 65535) return md_fail(MDHIP_EVALUE, "matmul: batch extent %lld exceeds 65535", (long long)g.batch);
     GemmPlan p; plan_gemm(p, g, md_dtype_of<T>::value);
+    return run_plan(p);
+  }
+  // float16 / int8 / uint8 (md_matmul_dispatch): the same planner, its narrow steps
+  static int gemm_narrow(const MdGemm &g, int dtype) {
+    if (g.batch > 65535) return md_fail(MDHIP_EVALUE, "matmul: batch extent %lld exceeds 65535", (long long)g.batch);
+    GemmPlan p; plan_narrow(p, g, dtype);
     return run_plan(p);
   }
 };

@@ -6,8 +6,9 @@ kernel, `mdhip_convert`). Elementwise arithmetic, `where` / `clip` and the reduc
 one launch that loads each operand in its own type, computes in the loop dtype's carrier (int32 / int64 / uint64 /
 float32: csrc/md_narrow.h) and stores in the result's type, 1.0x the algorithmic traffic — and so do the gathers / scatters
 by index arrays (csrc/index.hip: elements move by size; np.add.at wraps the integers and rounds float16 after every
-contribution, in index order, as NumPy's unbuffered loop does). The functions listed in COMPUTE
-below still go
+contribution, in index order, as NumPy's unbuffered loop does), and the products of the three pairs whose NumPy loop is the
+pair's own — float16 @ float16, int8 @ int8, uint8 @ uint8 (matmul / dot / tensordot: csrc/gemm_narrow.hip, the low-precision
+matrix cores). The functions listed in COMPUTE below, and the products of every other combination, still go
 
     promote to a wide device type  ->  the ordinary kernel  ->  demote to NumPy's result dtype
 
@@ -42,6 +43,9 @@ _MOVERS = {"concatenate", "stack", "tile", "repeat", "split"}
 # the statistics: NumPy's own first step is float64 (the sum runs in float64, each element converted first), so uint64 widens
 # straight to float64 there — the whole range, no detour through int64
 _STATS = {"mean", "std"}
+# products that run natively (mdhip_matmul takes float16 / int8 / uint8 triples) when both operands have one of these dtypes
+_PRODUCTS = {"matmul", "dot", "tensordot"}
+_NATIVE_PRODUCT = {np.dtype(np.float16), np.dtype(np.int8), np.dtype(np.uint8)}
 # functions whose integer results are the same BITS whether 64-bit operands are read signed or unsigned (sums of products wrap
 # mod 2**64 either way; "is it zero" does not look at the sign): uint64 rides in int64 with no range check there
 _BITS = {"matmul", "dot", "tensordot", "nonzero", "flatnonzero", "argwhere"}
@@ -90,6 +94,27 @@ def install(ns: dict):
         return False
 
     convert = ns["_convert"]
+
+    def native_product(args, kw) -> bool:
+        """Both operands arrays of ONE of the natively multiplied dtypes (and `out`, if any, of it too): no widening."""
+        if len(args) < 2:
+            return False
+        a, b = args[0], args[1]
+        if not isinstance(a, (DeviceArray, np.ndarray)) or not isinstance(b, (DeviceArray, np.ndarray)):
+            return False
+        dt = a.dtype
+        if dt not in _NATIVE_PRODUCT or b.dtype != dt:
+            return False
+        for x in args[2:]:
+            if has_narrow(x):
+                return False
+        for k, v in kw.items():
+            if k == "out" and v is not None:
+                if not isinstance(v, DeviceArray) or v.dtype != dt:
+                    return False
+            elif has_narrow(v):
+                return False
+        return True
 
     def dummy(x):
         if type(x) is DeviceArray or isinstance(x, np.ndarray):
@@ -153,6 +178,8 @@ def install(ns: dict):
             else:
                 if not kw or not any_narrow((), kw):
                     return fn(*args, **kw)
+            if name in _PRODUCTS and native_product(args, kw):
+                return fn(*args, **kw)
             # NumPy's own verdict on dtypes (and its exceptions) from one-element dummies
             dargs = [dummy(a) for a in args]
             dkw = {k: dummy(v) for k, v in kw.items()}
@@ -183,4 +210,5 @@ def install(ns: dict):
         return a
 
     ns["_narrow_inplace"] = inplace
+    ns["_native_product"] = lambda a, b: native_product((a, b), {})
     ns["_any_narrow"] = any_narrow

@@ -702,7 +702,7 @@ class DeviceArray(_fp.ArrayBase if _fp is not None else object):
     def __ipow__(self, o): return _inplace(np.power, _capi.B_POW, power, self, o)
 
     def __imatmul__(self, o):
-        if _any_narrow((self, o), None):
+        if _any_narrow((self, o), None) and not _native_product(self, o):
             return _narrow_inplace(np.matmul, matmul, self, o)
         res = matmul(self, o)
         if res.shape != self.shape:
