@@ -263,7 +263,9 @@ int mdhip_var(const mdhip_array *x, const mdhip_array *out, int32_t axis, int64_
  * Arrays are passed 3-D (batch, rows, cols); batch stride 0 broadcasts.
  * f32 and f64 run on MFMA; int32 / int64 take the generic kernel. Storage-only triples: float16 @ float16 -> float16
  * (float32 accumulation, one rounding) and int8 @ int8 -> int8, uint8 @ uint8 -> uint8 (the low byte of the exact sum) run
- * on the low-precision MFMA (gemm_narrow.hip); no other storage-only dtype is accepted. */
+ * on the low-precision MFMA (gemm_narrow.hip). Two triples keep the accumulator instead (np.matmul's dtype=): float16 @ float16 ->
+ * float32 and int8 @ int8 -> int32 (c has the wide dtype; the same kernels, stored without the final conversion). No other
+ * storage-only dtype and no other mixed triple is accepted (MDHIP_ETYPE). */
 int mdhip_matmul(const mdhip_array *a, const mdhip_array *b, const mdhip_array *c);
 /* GEMM with the elementwise tail and the reduction of BASELINE's MLP forward in its epilogue (lazy mode,
  * minidiff_amd/ndarray.py recognises the pattern): for row-major float32 a (M x K), b (K x N), bias (N)

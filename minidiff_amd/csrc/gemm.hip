@@ -1454,11 +1454,12 @@ static bool dma_priced(const GemmArgs &ga, bool a_kc, bool b_kc, bool aligned) {
 }
 // ---- the plan --------------------------------------------------------------------------------------------------------------------------
 enum { ST_REG, ST_DMA, ST_DMA_SELECT, ST_DMA_PRED };   // staging; the ragged DMA forms are the kernels' RAGGED = 1 (select) / 2 (predicated)
-enum { S_LONGK, S_SKINNY, S_REPACK, S_F32, S_SUM, S_F64, S_GENERIC, S_NMFMA, S_NGENERIC, S_NCONV };   // S_N*: float16 / int8 / uint8
+enum { S_LONGK, S_SKINNY, S_REPACK, S_F32, S_SUM, S_F64, S_GENERIC, S_NMFMA, S_NGENERIC, S_NCONV };   // S_N*: float16 / int8 / uint8 operands
 struct GemmStep {   // only the steps in use are initialised (GemmPlan::add)
   int kind, dtype, cfg, staging, nbuf, splits, epi, skip;   // cfg: kTiles row (S_F64: 0 64x64, 1 128x128, 2 TN direct to LDS); skip: hand-off
   int dtype_to;                                             // S_NCONV: the destination's dtype
-  bool a_kc, b_kc, edge, ct, stamp;                         // ct: C^T-vector stores (c_vec_rows); stamp: clock stamps (diagnostic)
+  bool a_kc, b_kc, edge, ct, stamp, wide;                   // ct: C^T-vector stores (c_vec_rows); stamp: clock stamps (diagnostic);
+                                                            // wide: S_NMFMA / S_NGENERIC store the carrier (float32 / int32 c)
   Tile tile;
   dim3 grid;
   GemmArgs ga;
@@ -1759,7 +1760,8 @@ static bool md_longk_shape(const MdGemm &g) {
 // The route the product had before it ran natively — convert both operands to the wide type (float32 / int32: the same bits of the
 // result), the wide plan with its hand-offs (skinny / long-k streaming kernels, split-k), convert the result back — for the shapes whose
 // wide kernels beat one launch of the narrow ones: thin or long-k products, unaligned operands of a large float16 product.
-static void plan_widened(GemmPlan &p, const MdGemm &g, int dtype, int wide) {
+// `keep_wide`: c has the wide type itself (plan_widen) — the wide plan writes straight into it, no conversion back.
+static void plan_widened(GemmPlan &p, const MdGemm &g, int dtype, int wide, bool keep_wide = false) {
   const size_t wsz = md_dtype_size(wide);
   const int64_t ba = g.a_bs ? g.batch : 1, bb = g.b_bs ? g.batch : 1, M = g.M, N = g.N, K = g.K;
   auto conv = [&](const void *src, int from, int64_t nb, int64_t rows, int64_t cols, int64_t bs, int64_t rs, int64_t cs, void *dst, int to,
@@ -1773,9 +1775,10 @@ static void plan_widened(GemmPlan &p, const MdGemm &g, int dtype, int wide) {
   conv(g.a, dtype, ba, M, K, g.a_bs, g.a_ms, g.a_ks, const_cast<void *>(w.a), wide, M * K, K, 1);
   w.b = p.temp((size_t)(bb * K * N) * wsz);
   conv(g.b, dtype, bb, K, N, g.b_bs, g.b_ks, g.b_ns, const_cast<void *>(w.b), wide, K * N, N, 1);
-  w.c = p.temp((size_t)(g.batch * M * N) * wsz);
   w.a_bs = ba > 1 ? M * K : 0; w.a_ms = K; w.a_ks = 1;
   w.b_bs = bb > 1 ? K * N : 0; w.b_ks = N; w.b_ns = 1;
+  if (keep_wide) return plan_gemm(p, w, wide);
+  w.c = p.temp((size_t)(g.batch * M * N) * wsz);
   w.c_bs = M * N; w.c_ms = N; w.c_ns = 1;
   plan_gemm(p, w, wide);
   conv(w.c, wide, g.batch, M, N, M * N, N, 1, g.c, dtype, g.c_bs, g.c_ms, g.c_ns);
@@ -1806,6 +1809,31 @@ static void plan_narrow(GemmPlan &p, const MdGemm &g, int dtype) {
     return;
   }
   plan_widened(p, g, dtype, wide);
+}
+// float16 @ float16 -> float32, int8 @ int8 -> int32 (`dtype`: the operands'): plan_narrow's choices with the carrier kept — the
+// wide-output MFMA / generic kernels of gemm_narrow.hip, or the widened route without its conversion back. The few-tile / long-k
+// cut-over is plan_narrow's fit (same k loop; the 4-byte C adds to the epilogue only): profiles/gemm_bench_widen_few_tiles.txt shows
+// no shape slower than the conversion route beyond its run-to-run spread, so it was kept. Option gemm_widen = 0: the route a caller had
+// before — convert both operands, the wide plan — for every product with a k.
+static void plan_widen(GemmPlan &p, const MdGemm &g, int dtype) {
+  const int esz = dtype == MDHIP_F16 ? 2 : 1, wide = dtype == MDHIP_F16 ? MDHIP_F32 : MDHIP_I32;
+  const NarrowLayout L = md_narrow_layout(g, esz);
+  const int64_t blocks = ((g.M + 127) / 128) * ((g.N + 127) / 128) * g.batch;
+  const double kk = (double)g.K / 1024.0;
+  const bool native = md_opt(MD_OPT_GEMM_WIDEN) != 0;
+  const bool thin = g.M <= 8 || g.N <= 8, few_long = esz == 2 && kk * (8.8 - 0.5 * (double)blocks) > 22.5;
+  if (native && L.ok && g.K > 0 && !thin && !few_long && !(esz == 1 && md_longk_shape(g))) {
+    GemmStep &s = p.add(S_NMFMA, esz == 2 ? "matmul(f16 -> f32 mfma)" : "matmul(i8 -> i32 mfma)");
+    s.dtype = dtype; s.g = g; s.a_kc = L.a_kc; s.b_kc = L.b_kc; s.edge = L.edge; s.wide = true;
+    return;
+  }
+  const bool small = g.K <= 512 && g.batch * g.M * g.N * g.K <= (1ll << 22);
+  if (g.K == 0 || (native && (small || (esz == 1 && !md_longk_shape(g))))) {
+    GemmStep &s = p.add(S_NGENERIC, "matmul(wide-output generic)");
+    s.dtype = dtype; s.g = g; s.wide = true;
+    return;
+  }
+  plan_widened(p, g, dtype, wide, true);
 }
 // ---- run ---------------------------------------------------------------------------------------------------------------------------
 typedef void (*GemmKernel)(GemmArgs);
@@ -1907,9 +1935,9 @@ static int run_step(const GemmStep &s, const void *const *tmp, int *skip) {
     case S_NMFMA: {
       const void *zero = s.edge ? md_zero_block() : nullptr;
       if (s.edge && !zero) return md_fail(MDHIP_EMEMORY, "matmul: zero block");
-      return md_gemm_narrow_mfma(g, s.dtype, s.a_kc, s.b_kc, s.edge, zero);
+      return s.wide ? md_gemm_widen_mfma(g, s.dtype, s.a_kc, s.b_kc, s.edge, zero) : md_gemm_narrow_mfma(g, s.dtype, s.a_kc, s.b_kc, s.edge, zero);
     }
-    case S_NGENERIC: return md_gemm_narrow_generic(g, s.dtype);
+    case S_NGENERIC: return s.wide ? md_gemm_widen_generic(g, s.dtype) : md_gemm_narrow_generic(g, s.dtype);
     case S_NCONV: {
       mdhip_array sd{}, dd{};
       sd.data = const_cast<void *>(g.a); sd.dtype = s.dtype; sd.ndim = 3;
@@ -1958,6 +1986,12 @@ struct HipExec {
   static int gemm_narrow(const MdGemm &g, int dtype) {
     if (g.batch > 65535) return md_fail(MDHIP_EVALUE, "matmul: batch extent %lld exceeds 65535", (long long)g.batch);
     GemmPlan p; plan_narrow(p, g, dtype);
+    return run_plan(p);
+  }
+  // float16 -> float32, int8 -> int32 (md_matmul_dispatch; `dtype`: the operands')
+  static int gemm_widen(const MdGemm &g, int dtype) {
+    if (g.batch > 65535) return md_fail(MDHIP_EVALUE, "matmul: batch extent %lld exceeds 65535", (long long)g.batch);
+    GemmPlan p; plan_widen(p, g, dtype);
     return run_plan(p);
   }
 };

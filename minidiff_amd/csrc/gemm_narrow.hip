@@ -24,6 +24,8 @@
 //       int8: 128-B k-rows, slot c ^ (((r >> 1) & 3) << 1) — conflict-free for the transposed reads of a 32-lane half.
 // The k order inside one MFMA does not matter (A and B take element j of a lane from the same k): the KC read gives element j =
 // k 8h + j (16h + j for int8) of step s, the transposed reads give the same k.
+// Wide-output forms (np.matmul's dtype=: float16 -> float32, int8 -> int32; k_gemm_widen_mfma, k_gemm_widen_generic) share the tile
+// loop and store the accumulators as they are. uint8 has none: the signed MFMA's sums are right modulo 256 only.
 // int8 outputs leave through LDS: the accumulator layout holds one column per lane, so the bytes are assembled into the tile's rows
 // in LDS first and stored as 16-B pieces of whole rows.
 #include "md_hip.h"
@@ -164,20 +166,18 @@ __device__ __forceinline__ void mma_tile(const char *SA, const char *SB, int wm,
   }
 }
 
-// ESZ 2: float16, 1: int8 / uint8. A_KC / B_KC: operand images (above). EDGE: ragged tiles (zero-filled DMA lanes).
+// The block's output tile (XCD-aware order, bijective for any tile count: the blocks that share an XCD take a contiguous band of
+// output tiles) and its whole k loop, shared by the narrow-output and the wide-output kernels. ESZ 2: float16, 1: int8 / uint8.
+// A_KC / B_KC: operand images (above). EDGE: ragged tiles (zero-filled DMA lanes). The four LDS buffers are the kernel's own objects.
 template <int ESZ, bool A_KC, bool B_KC, bool EDGE>
-__global__ void __launch_bounds__(NL_NT, 2) k_gemm_narrow_mfma(NarrowArgs g) {
-  __shared__ __attribute__((aligned(16))) char sA0[16384];
-  __shared__ __attribute__((aligned(16))) char sA1[16384];
-  __shared__ __attribute__((aligned(16))) char sB0[16384];
-  __shared__ __attribute__((aligned(16))) char sB1[16384];
-  // XCD-aware order (bijective for any tile count): the blocks that share an XCD take a contiguous band of output tiles
+__device__ __forceinline__ void narrow_tile_product(const NarrowArgs &g, char *sA0, char *sA1, char *sB0, char *sB1, int64_t *m0_out, int64_t *n0_out,
+                                                    typename Acc<ESZ>::type (&acc)[2][2]) {
   const int nwg = g.tiles_m * g.tiles_n, bid = blockIdx.x, xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
   const int wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
   const int64_t m0 = (int64_t)(wg / g.tiles_n) * NL_TILE, n0 = (int64_t)(wg % g.tiles_n) * NL_TILE;
   const int64_t bz = blockIdx.z;
   const char *A = g.A + bz * g.a_bs, *B = g.B + bz * g.b_bs;
-  const int wave = threadIdx.x >> 6, wm = wave >> 1, wn = wave & 1, l = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6, wm = wave >> 1, wn = wave & 1;
   constexpr int BK = NL_KB / ESZ;
   const int nk = (int)((g.K + BK - 1) / BK);
   // KC operands: rows along m / n with stride *_ms / *_ns, k unit; MN operands: k-rows with stride *_ks, rows unit
@@ -186,7 +186,6 @@ __global__ void __launch_bounds__(NL_NT, 2) k_gemm_narrow_mfma(NarrowArgs g) {
     stage<ESZ, A_KC, EDGE>(A, g.a_ms, g.a_ks, m0, k0, g.M, g.K, SA, g.zero);
     stage<ESZ, B_KC, EDGE>(B, g.b_ns, g.b_ks, n0, k0, g.N, g.K, SB, g.zero);
   };
-  typename Acc<ESZ>::type acc[2][2];
 #pragma unroll
   for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -203,6 +202,21 @@ __global__ void __launch_bounds__(NL_NT, 2) k_gemm_narrow_mfma(NarrowArgs g) {
     if (kt + 2 < nk) stage_ab(kt + 2, sA0, sB0);
     mma_tile<ESZ, A_KC, B_KC>(sA1, sB1, wm, wn, acc);
   }
+  *m0_out = m0; *n0_out = n0;
+}
+
+// float16 -> float16 (rounded on the store), int8 / uint8 -> the low byte
+template <int ESZ, bool A_KC, bool B_KC, bool EDGE>
+__global__ void __launch_bounds__(NL_NT, 2) k_gemm_narrow_mfma(NarrowArgs g) {
+  __shared__ __attribute__((aligned(16))) char sA0[16384];
+  __shared__ __attribute__((aligned(16))) char sA1[16384];
+  __shared__ __attribute__((aligned(16))) char sB0[16384];
+  __shared__ __attribute__((aligned(16))) char sB1[16384];
+  int64_t m0, n0;
+  typename Acc<ESZ>::type acc[2][2];
+  narrow_tile_product<ESZ, A_KC, B_KC, EDGE>(g, sA0, sA1, sB0, sB1, &m0, &n0, acc);
+  const int wave = threadIdx.x >> 6, wm = wave >> 1, wn = wave & 1, l = threadIdx.x & 63;
+  const int64_t bz = blockIdx.z;
   // epilogue. accumulator element e of lane l: row (e & 3) + 8 (e >> 2) + 4 (l >> 5), column l & 31 of the 32 x 32 tile
   char *C = g.C + bz * g.c_bs;
   if constexpr (ESZ == 2) {
@@ -239,18 +253,44 @@ __global__ void __launch_bounds__(NL_NT, 2) k_gemm_narrow_mfma(NarrowArgs g) {
   }
 }
 
+// The wide-output form: float16 operands -> float32 C, int8 -> int32 C, the accumulators stored as they are (c_* are byte strides of
+// the 4-byte C). One wave store writes 32 consecutive elements of two rows (lane & 31 = column): whole 128-B lines, no detour through LDS.
+template <int ESZ, bool A_KC, bool B_KC, bool EDGE>
+__global__ void __launch_bounds__(NL_NT, 2) k_gemm_widen_mfma(NarrowArgs g) {
+  __shared__ __attribute__((aligned(16))) char sA0[16384];
+  __shared__ __attribute__((aligned(16))) char sA1[16384];
+  __shared__ __attribute__((aligned(16))) char sB0[16384];
+  __shared__ __attribute__((aligned(16))) char sB1[16384];
+  int64_t m0, n0;
+  typename Acc<ESZ>::type acc[2][2];
+  narrow_tile_product<ESZ, A_KC, B_KC, EDGE>(g, sA0, sA1, sB0, sB1, &m0, &n0, acc);
+  const int wave = threadIdx.x >> 6, wm = wave >> 1, wn = wave & 1, l = threadIdx.x & 63;
+  char *C = g.C + (int64_t)blockIdx.z * g.c_bs;
+  typedef typename md_cond<ESZ == 2, float, int32_t>::type CT;
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const int64_t m = m0 + wm * 64 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * (l >> 5), n = n0 + wn * 64 + j * 32 + (l & 31);
+        if (!EDGE || (m < g.M && n < g.N)) *(CT *)(C + m * g.c_ms + n * g.c_ns) = acc[i][j][e];
+      }
+}
+
 // ---- generic: any strides, any size (tiny products, odd strides) ---------------------------------------------------------------
 // 16 x 16 output tiles; each operand read in its own type, the sum in k order in the carrier: float (fma chain) for float16, int32
 // (wrapping) for int8 / uint8 — what NumPy's own loops compute.
-template <class T, class Acc>
-__global__ void __launch_bounds__(256) k_gemm_narrow_generic(MdGemm g) {
+// (TC: the type stored — the operands' own, or the carrier for the wide-output products)
+template <class T, class Acc, class TC>
+__device__ __forceinline__ void narrow_generic_product(const MdGemm &g) {
   __shared__ Acc As[16][17];
   __shared__ Acc Bs[16][17];
   const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
   const int64_t bz = blockIdx.z;
   const T *A = (const T *)g.a + bz * g.a_bs;
   const T *B = (const T *)g.b + bz * g.b_bs;
-  T *C = (T *)g.c + bz * g.c_bs;
+  TC *C = (TC *)g.c + bz * g.c_bs;
   const int64_t row = (int64_t)blockIdx.y * 16 + ty, col = (int64_t)blockIdx.x * 16 + tx;
   Acc acc = 0;
   for (int64_t k0 = 0; k0 < g.K; k0 += 16) {
@@ -265,35 +305,50 @@ __global__ void __launch_bounds__(256) k_gemm_narrow_generic(MdGemm g) {
     }
     __syncthreads();
   }
-  if (row < g.M && col < g.N) C[row * g.c_ms + col * g.c_ns] = (T)acc;
+  if (row < g.M && col < g.N) C[row * g.c_ms + col * g.c_ns] = (TC)acc;
+}
+template <class T, class Acc>
+__global__ void __launch_bounds__(256) k_gemm_narrow_generic(MdGemm g) { narrow_generic_product<T, Acc, T>(g); }
+template <class T, class Acc>
+__global__ void __launch_bounds__(256) k_gemm_widen_generic(MdGemm g) { narrow_generic_product<T, Acc, Acc>(g); }
+
+template <bool WIDE, int ESZ, bool A, bool B> static void (*mfma_kernel(bool edge))(NarrowArgs) {
+  if constexpr (WIDE) return edge ? k_gemm_widen_mfma<ESZ, A, B, true> : k_gemm_widen_mfma<ESZ, A, B, false>;
+  else return edge ? k_gemm_narrow_mfma<ESZ, A, B, true> : k_gemm_narrow_mfma<ESZ, A, B, false>;
 }
 
-template <int ESZ, bool A, bool B> static void (*mfma_kernel(bool edge))(NarrowArgs) {
-  return edge ? k_gemm_narrow_mfma<ESZ, A, B, true> : k_gemm_narrow_mfma<ESZ, A, B, false>;
-}
-
-}  // namespace
-
-// launches planned by gemm.hip (plan_narrow): see md_hip.h
-int md_gemm_narrow_mfma(const MdGemm &g, int dtype, bool a_kc, bool b_kc, bool edge, const void *zero) {
-  const int esz = dtype == MDHIP_F16 ? 2 : 1;
+// WIDE: the 4-byte C of the wide-output kernels (uint8 has none: the signed MFMA's sums are right modulo 256 only)
+template <bool WIDE> int launch_mfma(const MdGemm &g, int dtype, bool a_kc, bool b_kc, bool edge, const void *zero) {
+  const int esz = dtype == MDHIP_F16 ? 2 : 1, csz = WIDE ? 4 : esz;
   NarrowArgs a{};
   a.A = (const char *)g.a; a.B = (const char *)g.b; a.C = (char *)g.c;
   a.M = g.M; a.N = g.N; a.K = g.K;
   a.a_bs = g.a_bs * esz; a.a_ms = g.a_ms * esz; a.a_ks = g.a_ks * esz;
   a.b_bs = g.b_bs * esz; a.b_ks = g.b_ks * esz; a.b_ns = g.b_ns * esz;
-  a.c_bs = g.c_bs * esz; a.c_ms = g.c_ms * esz; a.c_ns = g.c_ns * esz;
+  a.c_bs = g.c_bs * csz; a.c_ms = g.c_ms * csz; a.c_ns = g.c_ns * csz;
   a.zero = (const char *)zero;
   a.tiles_m = (int)((g.M + NL_TILE - 1) / NL_TILE);
   a.tiles_n = (int)((g.N + NL_TILE - 1) / NL_TILE);
-  a.c_vec = g.c_ns == 1 && !((uintptr_t)g.c & 15) && !(g.c_ms & 15) && !(g.c_bs & 15);
+  a.c_vec = !WIDE && g.c_ns == 1 && !((uintptr_t)g.c & 15) && !(g.c_ms & 15) && !(g.c_bs & 15);
   void (*k)(NarrowArgs);
-  if (esz == 2) k = a_kc ? (b_kc ? mfma_kernel<2, true, true>(edge) : mfma_kernel<2, true, false>(edge))
-                         : (b_kc ? mfma_kernel<2, false, true>(edge) : mfma_kernel<2, false, false>(edge));
-  else k = a_kc ? (b_kc ? mfma_kernel<1, true, true>(edge) : mfma_kernel<1, true, false>(edge))
-                : (b_kc ? mfma_kernel<1, false, true>(edge) : mfma_kernel<1, false, false>(edge));
+  if (esz == 2) k = a_kc ? (b_kc ? mfma_kernel<WIDE, 2, true, true>(edge) : mfma_kernel<WIDE, 2, true, false>(edge))
+                         : (b_kc ? mfma_kernel<WIDE, 2, false, true>(edge) : mfma_kernel<WIDE, 2, false, false>(edge));
+  else k = a_kc ? (b_kc ? mfma_kernel<WIDE, 1, true, true>(edge) : mfma_kernel<WIDE, 1, true, false>(edge))
+                : (b_kc ? mfma_kernel<WIDE, 1, false, true>(edge) : mfma_kernel<WIDE, 1, false, false>(edge));
   MD_LAUNCH(k, dim3((unsigned)(a.tiles_m * a.tiles_n), 1, (unsigned)g.batch), NL_NT, a);
+  if (WIDE) return MD_LAUNCH_CHECK(esz == 2 ? "matmul(f16 -> f32 mfma)" : "matmul(i8 -> i32 mfma)");
   return MD_LAUNCH_CHECK(esz == 2 ? "matmul(f16 mfma)" : "matmul(i8 mfma)");
+}
+
+}  // namespace
+
+// launches planned by gemm.hip (plan_narrow, plan_widen): see md_hip.h
+int md_gemm_narrow_mfma(const MdGemm &g, int dtype, bool a_kc, bool b_kc, bool edge, const void *zero) {
+  return launch_mfma<false>(g, dtype, a_kc, b_kc, edge, zero);
+}
+int md_gemm_widen_mfma(const MdGemm &g, int dtype, bool a_kc, bool b_kc, bool edge, const void *zero) {
+  if (dtype != MDHIP_F16 && dtype != MDHIP_I8) return md_fail(MDHIP_ETYPE, "matmul: no wide-output kernel for %s operands", md_dtype_name(dtype));
+  return launch_mfma<true>(g, dtype, a_kc, b_kc, edge, zero);
 }
 
 int md_gemm_narrow_generic(const MdGemm &g, int dtype) {
@@ -305,4 +360,14 @@ int md_gemm_narrow_generic(const MdGemm &g, int dtype) {
     default: k_gemm_narrow_generic<uint8_t, int32_t><<<grid, 256, 0, md_stream()>>>(g); break;
   }
   return MD_LAUNCH_CHECK("matmul(narrow generic)");
+}
+int md_gemm_widen_generic(const MdGemm &g, int dtype) {
+  const dim3 grid((unsigned)((g.N + 15) / 16), (unsigned)((g.M + 15) / 16), (unsigned)g.batch);
+  if (grid.y > 65535) return md_fail(MDHIP_EVALUE, "matmul: M too large for the generic kernel");
+  switch (dtype) {
+    case MDHIP_F16: k_gemm_widen_generic<_Float16, float><<<grid, 256, 0, md_stream()>>>(g); break;
+    case MDHIP_I8: k_gemm_widen_generic<int8_t, int32_t><<<grid, 256, 0, md_stream()>>>(g); break;
+    default: return md_fail(MDHIP_ETYPE, "matmul: no wide-output kernel for %s operands", md_dtype_name(dtype));
+  }
+  return MD_LAUNCH_CHECK("matmul(wide-output generic)");
 }

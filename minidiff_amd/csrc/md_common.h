@@ -373,10 +373,14 @@ struct MdGemm {
   int64_t b_bs, b_ks, b_ns;
   int64_t c_bs, c_ms, c_ns;
 };
+// the two products whose result is wider than the operands: float16 @ float16 -> float32, int8 @ int8 -> int32 (np.matmul's dtype=)
+static inline bool md_gemm_widening(int a, int b, int c) {
+  return a == b && ((a == MDHIP_F16 && c == MDHIP_F32) || (a == MDHIP_I8 && c == MDHIP_I32));
+}
 static inline int md_build_gemm(MdGemm *g, const mdhip_array *a, const mdhip_array *b, const mdhip_array *c) {
   if (a->ndim != 3 || b->ndim != 3 || c->ndim != 3)
     return md_fail(MDHIP_EVALUE, "matmul: operands must be passed 3-D (batch, rows, cols)");
-  if (a->dtype != b->dtype || a->dtype != c->dtype)
+  if ((a->dtype != b->dtype || a->dtype != c->dtype) && !md_gemm_widening(a->dtype, b->dtype, c->dtype))
     return md_fail(MDHIP_ETYPE, "matmul: dtypes must agree (%s, %s -> %s)", md_dtype_name(a->dtype),
                    md_dtype_name(b->dtype), md_dtype_name(c->dtype));
   g->batch = c->shape[0];

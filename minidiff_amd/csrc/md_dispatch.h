@@ -310,7 +310,39 @@ template <class X> static int md_gemm_narrow(const MdGemm &g, int dt, long) {
       }
   return MDHIP_OK;
 }
+// float16 @ float16 -> float32 and int8 @ int8 -> int32 (np.matmul's dtype=): the same sums with the carrier kept. A policy with
+// `gemm_widen(g, dtype)` runs them on its kernels (`dtype`: the operands'); any other policy gets the loops above without the final
+// conversion — the float fma chain stored as float, the wrapping sum stored as int32.
+template <class X> static auto md_gemm_widen(const MdGemm &g, int dt, int) -> decltype(X::gemm_widen(g, dt)) { return X::gemm_widen(g, dt); }
+template <class X> static int md_gemm_widen(const MdGemm &g, int dt, long) {
+  for (int64_t bi = 0; bi < g.batch; ++bi)
+    for (int64_t m = 0; m < g.M; ++m)
+      for (int64_t n = 0; n < g.N; ++n) {
+        const int64_t ao = bi * g.a_bs + m * g.a_ms, bo = bi * g.b_bs + n * g.b_ns, co = bi * g.c_bs + m * g.c_ms + n * g.c_ns;
+        if (dt == MDHIP_F16) {
+          float acc = 0.0f;
+          for (int64_t k = 0; k < g.K; ++k)
+            acc = std::fma(md_load<float>(g.a, dt, ao + k * g.a_ks), md_load<float>(g.b, dt, bo + k * g.b_ks), acc);
+          ((float *)g.c)[co] = acc;
+        } else {
+          uint32_t acc = 0;
+          for (int64_t k = 0; k < g.K; ++k)
+            acc += (uint32_t)md_load<int32_t>(g.a, dt, ao + k * g.a_ks) * (uint32_t)md_load<int32_t>(g.b, dt, bo + k * g.b_ks);
+          ((int32_t *)g.c)[co] = (int32_t)acc;
+        }
+      }
+  return MDHIP_OK;
+}
 template <class X> int md_matmul_dispatch(const mdhip_array *a, const mdhip_array *b, const mdhip_array *c) {
+  if (a && b && c && md_gemm_widening(a->dtype, b->dtype, c->dtype)) {
+    MD_TRY(md_check_any_array(a, "matmul a"));
+    MD_TRY(md_check_any_array(b, "matmul b"));
+    MD_TRY(md_check_array(c, "matmul c"));
+    MdGemm g{};
+    MD_TRY(md_build_gemm(&g, a, b, c));
+    if (g.batch == 0 || g.M == 0 || g.N == 0) return MDHIP_OK;
+    return md_gemm_widen<X>(g, a->dtype, 0);
+  }
   if (a && b && c && a->dtype == b->dtype && a->dtype == c->dtype && (c->dtype == MDHIP_F16 || c->dtype == MDHIP_I8 || c->dtype == MDHIP_U8)) {
     MD_TRY(md_check_any_array(a, "matmul a"));
     MD_TRY(md_check_any_array(b, "matmul b"));

@@ -16,6 +16,9 @@ int md_gemm_longk(const MdGemm &g, int dtype);            // skinny.hip: both si
 // unit-stride (else its row axis is), edge = ragged tiles (zero: 16-B aligned zeros for the lanes outside the operands)
 int md_gemm_narrow_mfma(const MdGemm &g, int dtype, bool a_kc, bool b_kc, bool edge, const void *zero);
 int md_gemm_narrow_generic(const MdGemm &g, int dtype);
+// the same with the accumulators stored as they are: float16 operands -> float32 c, int8 -> int32 (`dtype`: the operands')
+int md_gemm_widen_mfma(const MdGemm &g, int dtype, bool a_kc, bool b_kc, bool edge, const void *zero);
+int md_gemm_widen_generic(const MdGemm &g, int dtype);
 unsigned *md_tickets();                                   // MD_TICKET_WORDS zeroed counters (md_ticket.h)
 bool md_capturing();                                      // a stream capture is recording (mdhip_graph_begin .. _end)
 int *md_sticky();                                         // host-mapped word a CAPTURED gather / scatter sets on an out-of-bounds index

@@ -8,7 +8,8 @@ float32: csrc/md_narrow.h) and stores in the result's type, 1.0x the algorithmic
 by index arrays (csrc/index.hip: elements move by size; np.add.at wraps the integers and rounds float16 after every
 contribution, in index order, as NumPy's unbuffered loop does), and the products of the three pairs whose NumPy loop is the
 pair's own — float16 @ float16, int8 @ int8, uint8 @ uint8 (matmul / dot / tensordot: csrc/gemm_narrow.hip, the low-precision
-matrix cores). The functions listed in COMPUTE below, and the products of every other combination, still go
+matrix cores); `matmul(a, b, dtype=)` is let through untouched — matmul casts the operands itself, and float16 operands with
+dtype=float32 / int8 operands with dtype=int32 are one native call that keeps the accumulators. The functions listed in COMPUTE below, and the products of every other combination, still go
 
     promote to a wide device type  ->  the ordinary kernel  ->  demote to NumPy's result dtype
 
@@ -180,6 +181,8 @@ def install(ns: dict):
                     return fn(*args, **kw)
             if name in _PRODUCTS and native_product(args, kw):
                 return fn(*args, **kw)
+            if name == "matmul" and kw.get("dtype") is not None:
+                return fn(*args, **kw)   # matmul itself casts the operands to the loop's dtype (float16 -> float32, int8 -> int32: natively)
             # NumPy's own verdict on dtypes (and its exceptions) from one-element dummies
             dargs = [dummy(a) for a in args]
             dkw = {k: dummy(v) for k, v in kw.items()}

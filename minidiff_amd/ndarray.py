@@ -2066,23 +2066,52 @@ def _as3d(x: DeviceArray, batch_shape: tuple):
     return full._view(full._offset, (B, r, c), (st[0], full._strides[-2], full._strides[-1]))
 
 
-def matmul(a, b, out=None, **kw):
+# np.matmul(a, b, dtype=X) products that mdhip_matmul takes as they are (operands, result): the accumulators of the low-precision
+# matrix cores kept (csrc/gemm_narrow.hip, k_gemm_widen_*)
+_WIDENING_PRODUCTS = {(np.dtype(np.float16), np.dtype(np.float32)), (np.dtype(np.int8), np.dtype(np.int32))}
+
+
+def matmul(a, b, out=None, dtype=None, **kw):
     """np.matmul (numpy.py:84). `out`: like NumPy's — a C-contiguous array of the result's shape and dtype that
-    receives the product (dp.GradSync points it at a row panel of the all-reduce bucket)."""
+    receives the product (dp.GradSync points it at a row panel of the all-reduce bucket). `dtype`: NumPy's — the loop's
+    dtype: both operands are cast to it under 'same_kind' (TypeError if one cannot be) and the result has it. float16 operands
+    with dtype=float32 and int8 operands with dtype=int32 are ONE native call on the operands as they are; every other
+    combination converts the operands first and takes the plain route of that dtype. Never deferred in lazy mode."""
     _defaults_only("matmul", kw)
     a, b = asarray(a), asarray(b)
     if a.ndim == 0 or b.ndim == 0:
         raise ValueError("matmul: Input operand does not have enough dimensions (has 0, gufunc core with signature (n?,k),(k,m?)->(n?,m?) requires 1)")
-    odt = np.result_type(a.dtype, b.dtype)
-    if odt == np.bool_:
-        # NumPy's boolean loop: "any k with a[i, k] and b[k, j]" — the integer product of the 0 / 1 operands is the count of such k
-        res = greater(matmul(astype(a, np.int32), astype(b, np.int32)), 0)
-        return _finish_out(res, out, "matmul")
-    dtype_code(odt)
-    if a.dtype != odt:
-        a = astype(a, odt)
-    if b.dtype != odt:
-        b = astype(b, odt)
+    if dtype is not None:
+        odt = np.dtype(dtype)
+        dtype_code(odt)
+        for i, x in enumerate((a, b)):
+            if not np.can_cast(x.dtype, odt, casting="same_kind"):
+                raise TypeError(f"Cannot cast ufunc 'matmul' input {i} from {x.dtype!r} to {odt!r} with casting rule 'same_kind'")
+        if a.dtype != b.dtype or (a.dtype, odt) not in _WIDENING_PRODUCTS:
+            if out is not None and (not isinstance(out, DeviceArray) or out.dtype != odt or not out.is_c_contiguous):
+                raise ValueError("matmul: out must be a C-contiguous DeviceArray with the shape and dtype of the result")
+            a, b = a if a.dtype == odt else astype(a, odt), b if b.dtype == odt else astype(b, odt)
+            if out is not None and dtype_code(odt) >= _narrow.NARROW_CODE_MIN and not _native_product(a, b):
+                # (a storage-only dtype whose product is computed in a wide type and converted: it lands in `out` by a copy)
+                res = matmul(a, b)
+                if out.shape != res.shape:
+                    raise ValueError("matmul: out must be a C-contiguous DeviceArray with the shape and dtype of the result")
+                _copy_into(out, res)
+                return out
+            res = matmul(a, b, out=out)
+            res.materialize()
+            return res
+    else:
+        odt = np.result_type(a.dtype, b.dtype)
+        if odt == np.bool_:
+            # NumPy's boolean loop: "any k with a[i, k] and b[k, j]" — the integer product of the 0 / 1 operands is the count of such k
+            res = greater(matmul(astype(a, np.int32), astype(b, np.int32)), 0)
+            return _finish_out(res, out, "matmul")
+        dtype_code(odt)
+        if a.dtype != odt:
+            a = astype(a, odt)
+        if b.dtype != odt:
+            b = astype(b, odt)
     a_vec, b_vec = a.ndim == 1, b.ndim == 1
     if a_vec:
         a = expand_dims(a, 0)
@@ -2093,7 +2122,7 @@ def matmul(a, b, out=None, **kw):
             f"matmul: Input operand 1 has a mismatch in its core dimension 0, with gufunc signature (n?,k),(k,m?)->(n?,m?) (size {b.shape[-2]} is different from {a.shape[-1]})")
     batch = _broadcast_shapes(a.shape[:-2], b.shape[:-2])
     M, N = a.shape[-2], b.shape[-1]
-    if _LAZY and out is None and not batch and not a_vec and not b_vec and odt == np.float32 and a.shape[-1] > 0 and M * N > 0:
+    if _LAZY and out is None and dtype is None and not batch and not a_vec and not b_vec and odt == np.float32 and a.shape[-1] > 0 and M * N > 0:
         # deferred: the product may end up in the epilogue-fused form (_fused_reduce), otherwise it runs
         # unchanged the moment anything needs its bytes
         a.materialize()
