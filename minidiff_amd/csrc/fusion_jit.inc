@@ -269,6 +269,15 @@ static std::string gen_body(const Spec &S, int k, const TrigUse &tu) {
 static void gen_prelude(std::ostringstream &o, const Spec &S, const std::string &kname) {
   o << kOpsSrc << "\n";
   if (S.kind == RED_ALL || S.kind == SWEEP) o << kTicketSrc << "\n";
+  // The bodies below are straight-line source: `a * b` followed by `a + b` would be contracted into ONE fused multiply-add — one
+  // rounding where the eager kernels, the interpreter (switch dispatch: nothing to contract across) and NumPy round twice. From
+  // here on nothing is contracted. The functors above keep the mode the eager kernels compile them in: the compiler's expansion
+  // of logf ends in a contracted multiply-add, so -ffp-contract=off for the whole unit would change log(x) in the last bit
+  // (tests/test_elementwise_accuracy.py: paths, chains. Seen on the device with that flag: log(x) from a generated kernel differed
+  // from the eager kernel's in 12258 of 65536 float32 arguments by one ulp, e.g. log(FLT_MAX) = 0x42b17217 against 0x42b17218.)
+  // This relies on hiprtc's default contraction mode, fast-honor-pragmas: under a global -ffp-contract=fast the backend fuses
+  // whatever the pragma says. Only the GPU twins of the chain tests notice that — the CPU double has no generated kernels.
+  o << "#pragma clang fp contract(off)\n";
   o << "#define KNAME " << kname << "\n";
   o << "constexpr bool JNT = " << (S.nt ? "true" : "false") << ";  // non-temporal 16-B loads (streams larger than the Infinity Cache)\n";
   o << "constexpr bool JNT_ST = " << ((S.nt || S.nt_store) ? "true" : "false") << ";  // non-temporal 16-B stores\n";
