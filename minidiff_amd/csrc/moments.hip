@@ -6,7 +6,10 @@
 //   rows    (the reduced axis is the contiguous one): a row of up to 16 Ki elements is read ONCE into registers — sum, mean (a true
 //           division, as NumPy), centred squares, all from the registers; longer rows are read twice (the second time from cache);
 //   columns (axis 0 of a row-major matrix): the column sums by mdhip_reduce's strips kernel, then one more strips walk that adds
-//           (x - mean)^2 — two reads, the last block of a strip folds the band partials in band order and finishes the division.
+//           (x - mean)^2 — two reads, the last block of a strip folds the band partials in band order and finishes the division;
+//   a middle axis ((outer, n, inner) with inner contiguous: the statistics of a normalisation over the sequence axis): `outer`
+//           independent column problems — the batched column sums of mdhip_reduce, then ONE batched launch of the same second walk
+//           (the batch on blockIdx.y, per-batch offsets into x, the sums, the partial rows, the ticket words and out).
 // Same arithmetic as NumPy up to the order of the two sums (no Welford update, no E[x^2] - mean^2 cancellation). HBM-bound:
 // algorithmic bytes = one read of x.
 #include "md_hip.h"
@@ -120,15 +123,23 @@ __global__ void __launch_bounds__(256) k_var_rows(const T *__restrict__ x, int64
 
 // Second pass of the column form: out[c] = f( sum_r (x[r][c] - csum[c] / n)^2 / denom ). The walk of k_reduce_cols_strips (reduce.hip):
 // NS strips x NB bands, rows interleaved across bands and waves, batches of RB rows double-buffered, ticket finish.
+// blockIdx.y: one of several independent (n_red x n_out) problems (a MIDDLE axis reduced) — x_bs elements apart in x, o_bs in csum and
+// out, p_bs in the partial rows; each has its own strip tickets. The 2-D form is the one-batch launch (strides 0).
 template <class T, int RB>
 __global__ void __launch_bounds__(256) k_var_cols(const T *__restrict__ x, const T *__restrict__ csum, int64_t n_out, int64_t n_red, int NS, int NB,
-                                                  T *partial, unsigned *tickets, T *__restrict__ out, T denom, int take_sqrt) {
+                                                  T *partial, unsigned *tickets, T *__restrict__ out, T denom, int take_sqrt,
+                                                  int64_t x_bs, int64_t o_bs, int64_t p_bs) {
   constexpr int V = 16 / sizeof(T);
   typedef MdVec<T, V> Vec;
   __shared__ Vec sm[3][64];
   __shared__ unsigned last_flag;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int s = blockIdx.x % NS, b = blockIdx.x / NS;
+  x += (int64_t)blockIdx.y * x_bs;
+  csum += (int64_t)blockIdx.y * o_bs;
+  out += (int64_t)blockIdx.y * o_bs;
+  if (NB > 1) partial += (int64_t)blockIdx.y * p_bs;
+  tickets += (int64_t)blockIdx.y * NS * MD_TICKET_PAD;
   const int64_t col_raw = ((int64_t)s * 64 + lane) * V;
   const bool col_ok = col_raw < n_out;
   const int64_t col = col_ok ? col_raw : n_out - V;
@@ -252,28 +263,43 @@ template <class T> int var_rows(const T *x, int64_t n_rows, int64_t n, T *out, T
   return MD_LAUNCH_CHECK("var(rows)");
 }
 
-template <class T> int var_cols(const mdhip_array *x2d, int64_t n_red, int64_t n_out, T *out, T denom, int take_sqrt, int dtype) {
+// `outer` column problems of n_red x n_out, n_red * n_out elements apart (outer == 1: the 2-D form).
+template <class T> int var_cols(const void *xdata, int64_t outer, int64_t n_red, int64_t n_out, T *out, T denom, int take_sqrt, int dtype) {
   constexpr int V = 16 / sizeof(T);
   void *csum = nullptr;
-  MD_TRY(mdhip_alloc((size_t)n_out * sizeof(T), &csum));
-  mdhip_array sd{};
-  sd.data = csum; sd.dtype = dtype; sd.ndim = 2; sd.shape[0] = 1; sd.shape[1] = n_out; sd.strides[0] = n_out; sd.strides[1] = 1;
-  int rc = mdhip_reduce(MDHIP_R_SUM, x2d, &sd, 1u);
+  MD_TRY(mdhip_alloc((size_t)(outer * n_out) * sizeof(T), &csum));
+  mdhip_array xd{}, sd{};
+  xd.data = const_cast<void *>(xdata); xd.dtype = dtype;
+  sd.data = csum; sd.dtype = dtype;
+  uint32_t mask;
+  if (outer == 1) {
+    xd.ndim = 2; xd.shape[0] = n_red; xd.shape[1] = n_out; xd.strides[0] = n_out; xd.strides[1] = 1;
+    sd.ndim = 2; sd.shape[0] = 1; sd.shape[1] = n_out; sd.strides[0] = n_out; sd.strides[1] = 1;
+    mask = 1u;
+  } else {   // (the batched strips launch of reduce.hip; whichever kernel it picks, csum holds the column sums)
+    xd.ndim = 3; xd.shape[0] = outer; xd.shape[1] = n_red; xd.shape[2] = n_out; xd.strides[0] = n_red * n_out; xd.strides[1] = n_out; xd.strides[2] = 1;
+    sd.ndim = 3; sd.shape[0] = outer; sd.shape[1] = 1; sd.shape[2] = n_out; sd.strides[0] = n_out; sd.strides[1] = n_out; sd.strides[2] = 1;
+    mask = 1u << 1;
+  }
+  int rc = mdhip_reduce(MDHIP_R_SUM, &xd, &sd, mask);
   if (rc != MDHIP_OK) { mdhip_free(csum); return rc; }
   const int64_t NS = (n_out + 64 * V - 1) / (64 * V);
-  int64_t NB = (1024 + NS - 1) / NS;
+  // 2-D: ~1024 blocks; batched: one block per CU, as the batched column sums
+  int64_t NB = outer == 1 ? (1024 + NS - 1) / NS : (NS * outer >= MD_NUM_CUS ? 1 : MD_NUM_CUS / (NS * outer));
   if (NB > 64) NB = 64;
   if (NB > n_red / 32) NB = n_red / 32;
   if (NB < 1) NB = 1;
-  if (NS * MD_TICKET_PAD > MD_TICKET_WORDS) NB = 1;
-  while (NB > 1 && NB * n_out * (int64_t)sizeof(T) >= (1ll << 31)) NB /= 2;
+  if (NS * outer * MD_TICKET_PAD > MD_TICKET_WORDS) NB = 1;
+  while (NB > 1 && NB * n_out * (int64_t)sizeof(T) >= (1ll << 31)) NB /= 2;   // (32-bit byte offsets into a batch's partial rows)
   void *partial = nullptr;
   if (NB > 1) {
-    rc = mdhip_alloc((size_t)(NB * n_out) * sizeof(T), &partial);
+    rc = mdhip_alloc((size_t)(outer * NB * n_out) * sizeof(T), &partial);
     if (rc != MDHIP_OK) { mdhip_free(csum); return rc; }
   }
-  MD_LAUNCH((k_var_cols<T, 8>), (unsigned)(NS * NB), 256, (const T *)x2d->data, (const T *)csum, n_out, n_red, (int)NS, (int)NB, (T *)partial, md_tickets(), out, denom, take_sqrt);
-  rc = MD_LAUNCH_CHECK("var(cols)");
+  const dim3 grid((unsigned)(NS * NB), (unsigned)outer);
+  MD_LAUNCH((k_var_cols<T, 8>), grid, 256, (const T *)xdata, (const T *)csum, n_out, n_red, (int)NS, (int)NB, (T *)partial, md_tickets(), out, denom, take_sqrt,
+            outer == 1 ? (int64_t)0 : n_red * n_out, outer == 1 ? (int64_t)0 : n_out, outer == 1 ? (int64_t)0 : NB * n_out);
+  rc = MD_LAUNCH_CHECK(outer == 1 ? "var(cols)" : "var(cols,batched)");
   if (partial) mdhip_free(partial);
   mdhip_free(csum);   // stream-ordered
   return rc;
@@ -305,6 +331,9 @@ extern "C" int mdhip_var(const mdhip_array *x, const mdhip_array *out, int32_t a
     osz *= out->shape[d];
   }
   if (osz != outer * inner) return md_fail(MDHIP_EVALUE, "var: out has %lld elements, expected %lld", (long long)osz, (long long)(outer * inner));
+  // (A/B: with option var_batched 0 only the last axis and the first of a 2-D array are served, as before the batched column form)
+  if (!md_opt(MD_OPT_VAR_BATCHED) && !(axis == x->ndim - 1 || (axis == 0 && x->ndim == 2)))
+    return md_fail(MDHIP_EVALUE, "var: neither the last axis nor the first of a 2-D array, and option var_batched is 0 (the caller composes)");
   const int64_t V = x->dtype == MDHIP_F32 ? 4 : 2;
   if (((uintptr_t)x->data & 15) || ((uintptr_t)out->data & 15)) return md_fail(MDHIP_EVALUE, "var: unaligned operands");
   const double denom = (double)(n - ddof);
@@ -315,12 +344,9 @@ extern "C" int mdhip_var(const mdhip_array *x, const mdhip_array *out, int32_t a
     return x->dtype == MDHIP_F32 ? var_rows<float>((const float *)x->data, outer, n, (float *)out->data, (float)denom, take_sqrt)
                                  : var_rows<double>((const double *)x->data, outer, n, (double *)out->data, denom, take_sqrt);
   }
-  if (outer == 1) {
-    if ((inner % V) || n < 64 || inner < 256) return md_fail(MDHIP_EVALUE, "var: column form needs >= 256 aligned columns and >= 64 rows");
-    mdhip_array x2{};
-    x2.data = x->data; x2.dtype = x->dtype; x2.ndim = 2; x2.shape[0] = n; x2.shape[1] = inner; x2.strides[0] = inner; x2.strides[1] = 1;
-    return x->dtype == MDHIP_F32 ? var_cols<float>(&x2, n, inner, (float *)out->data, (float)denom, take_sqrt, MDHIP_F32)
-                                 : var_cols<double>(&x2, n, inner, (double *)out->data, denom, take_sqrt, MDHIP_F64);
-  }
-  return md_fail(MDHIP_EVALUE, "var: reduced axis in the middle (the caller composes)");
+  if ((inner % V) || n < 64 || inner < 256) return md_fail(MDHIP_EVALUE, "var: column form needs >= 256 aligned columns and >= 64 rows");
+  // outer > 1: `outer` column problems in one launch (the batch rides on blockIdx.y)
+  if (outer > 65535) return md_fail(MDHIP_EVALUE, "var: reduced axis in the middle of more than 65535 batches (the caller composes)");
+  return x->dtype == MDHIP_F32 ? var_cols<float>(x->data, outer, n, inner, (float *)out->data, (float)denom, take_sqrt, MDHIP_F32)
+                               : var_cols<double>(x->data, outer, n, inner, (double *)out->data, denom, take_sqrt, MDHIP_F64);
 }

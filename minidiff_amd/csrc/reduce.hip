@@ -713,9 +713,12 @@ __global__ void __launch_bounds__(MD_BLOCK) k_arg_cols_finish(const T *pval, con
 // published write-through, merged in band order by the block that arrives last at the strip's ticket. One launch (the chunked
 // kernel above + its finish pass ran at 1.5 TB/s on 8192 x 4096: 128 rows per block, four loads in flight per wave).
 // Rows are carried as 32-bit (16-byte T) or 64-bit (8-byte T) integers so that a lane's V rows fill one 16-B vector; n_red < 2^31.
+// blockIdx.y, as in k_reduce_cols_strips: one of several independent (n_red x n_out) problems x_bs / o_bs elements apart (a MIDDLE
+// axis reduced), each with its own NB partial rows and its own strip tickets.
 template <bool IsMax, class T, int RB>
 __global__ void __launch_bounds__(MD_BLOCK) k_arg_cols_strips(const T *__restrict__ x, int64_t n_out, int64_t n_red, int64_t rs, int NS, int NB,
-                                                             T *pval, void *pidx_, unsigned *tickets, int64_t *__restrict__ out) {
+                                                             T *pval, void *pidx_, unsigned *tickets, int64_t *__restrict__ out,
+                                                             int64_t x_bs, int64_t o_bs) {
   constexpr int V = 16 / sizeof(T);
   typedef MdVec<T, V> Vec;
   typedef typename md_cond<V == 4, int32_t, int64_t>::type I;
@@ -726,6 +729,9 @@ __global__ void __launch_bounds__(MD_BLOCK) k_arg_cols_strips(const T *__restric
   __shared__ unsigned last_flag;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int s = blockIdx.x % NS, b = blockIdx.x / NS;
+  x += (int64_t)blockIdx.y * x_bs;
+  out += (int64_t)blockIdx.y * o_bs;
+  tickets += (int64_t)blockIdx.y * NS * MD_TICKET_PAD;
   const int64_t col_raw = ((int64_t)s * 64 + lane) * V;
   const bool col_ok = col_raw < n_out;
   const int64_t col = col_ok ? col_raw : n_out - V;
@@ -807,7 +813,8 @@ __global__ void __launch_bounds__(MD_BLOCK) k_arg_cols_strips(const T *__restric
     if (w == 0 && col_ok) store_out();
     return;
   }
-  I *pidx = (I *)pidx_;
+  I *pidx = (I *)pidx_ + (int64_t)blockIdx.y * NB * n_out;
+  pval += (int64_t)blockIdx.y * NB * n_out;
   const __amdgpu_buffer_rsrc_t prv = md_rsrc(pval, (unsigned)((int64_t)NB * n_out * (int64_t)sizeof(T)));
   const __amdgpu_buffer_rsrc_t pri = md_rsrc(pidx, (unsigned)((int64_t)NB * n_out * (int64_t)sizeof(I)));
   if (w == 0 && col_ok) {
@@ -1163,7 +1170,7 @@ struct HipExec {
             if (rc != MDHIP_OK) { mdhip_free(pv); return rc; }
           }
           MD_LAUNCH((k_arg_cols_strips<IsMax, T, ARG_RB>), (unsigned)(NS * NB), MD_BLOCK, (const T *)x->data, n_out, n_red, pl.rx[0], (int)NS, (int)NB, (T *)pv, pi, md_tickets(),
-                    (int64_t *)out->data);
+                    (int64_t *)out->data, (int64_t)0, (int64_t)0);
           const int rc = MD_LAUNCH_CHECK("argreduce(cols,strips)");
           if (pv) mdhip_free(pv);
           if (pi) mdhip_free(pi);
@@ -1189,6 +1196,37 @@ struct HipExec {
         rc = MD_LAUNCH_CHECK("argreduce(cols,vec,split)");
         mdhip_free(pv);
         mdhip_free(pi);
+        return rc;
+      }
+      // a middle axis reduced: (outer, n_red, inner) with the inner axis contiguous — `outer` column problems in one launch of the strips
+      // kernel (the predicate of the batched column sums above); up to here these went to k_arg_block / k_arg_thread, a block or a
+      // thread per output walking its column with the row stride. (md_build_redplan merges neighbouring kept axes whose strides nest in x
+      // and in out, so (2,3,[64],256) and (2,[64],4,64) arrive here as nk == 2 as well: profiles/middle_axis_4d_kernel_stats.csv)
+      if (same && md_opt(MD_OPT_ARG_BATCHED) != 0 && pl.nk == 2 && pl.nr == 1 && pl.kx[1] == 1 && pl.ko[1] == 1 && pl.ko[0] == pl.kshape[1] &&
+          (pl.kshape[1] % V) == 0 && (pl.rx[0] % V) == 0 && (pl.kx[0] % V) == 0 && ((uintptr_t)x->data & 15) == 0 && pl.kshape[1] >= 256 &&
+          pl.n_red >= 64 && pl.n_red < (1ll << 31) && pl.kshape[0] <= 65535) {
+        const int64_t outer = pl.kshape[0], inner = pl.kshape[1], n_red = pl.n_red;
+        const int64_t NS = ceil_div(inner, 64 * V);
+        const int arg_blocks = md_opt(MD_OPT_ARG_BLOCKS) > 0 ? (int)md_opt(MD_OPT_ARG_BLOCKS) : MD_NUM_CUS;
+        int64_t NB = ceil_div(arg_blocks, NS * outer);   // one block per CU over all the batches
+        if (NB > 64) NB = 64;
+        if (NB > n_red / 32) NB = n_red / 32;
+        if (NB < 1) NB = 1;
+        if (NS * outer * MD_TICKET_PAD > MD_TICKET_WORDS) NB = 1;
+        while (NB > 1 && NB * inner * 8 >= (1ll << 31)) NB /= 2;   // (32-bit byte offsets into a batch's partial rows)
+        constexpr int ARG_RB = 4;
+        void *pv = nullptr, *pi = nullptr;
+        if (NB > 1) {
+          MD_TRY(mdhip_alloc((size_t)(outer * NB * inner) * sizeof(T), &pv));
+          const int rc = mdhip_alloc((size_t)(outer * NB * inner) * (V == 4 ? 4 : 8), &pi);
+          if (rc != MDHIP_OK) { mdhip_free(pv); return rc; }
+        }
+        const dim3 grid((unsigned)(NS * NB), (unsigned)outer);
+        MD_LAUNCH((k_arg_cols_strips<IsMax, T, ARG_RB>), grid, MD_BLOCK, (const T *)x->data, inner, n_red, pl.rx[0], (int)NS, (int)NB, (T *)pv, pi, md_tickets(),
+                  (int64_t *)out->data, (int64_t)pl.kx[0], (int64_t)inner);
+        const int rc = MD_LAUNCH_CHECK("argreduce(cols,strips,batched)");
+        if (pv) mdhip_free(pv);
+        if (pi) mdhip_free(pi);
         return rc;
       }
       // reduced axis contiguous

@@ -1994,7 +1994,9 @@ def mean(a, axis=None, dtype=None, out=None, keepdims=False, **kw):
 
 def _std_fused(a, axis, dtype, ddof, keepdims, n):
     """One-pass (rows) / two-pass (columns) kernel for the forms mdhip_var covers: a concrete float32 / float64 C-contiguous array
-    reduced over its last axis, or a 2-D one over its first; anything else -> None and `std` composes NumPy's five steps."""
+    reduced over any single axis. The library alone judges the form — rows, columns, or a middle axis as a batch of column problems —
+    and refuses what it does not cover (short / narrow / unaligned shapes); that, and anything else -> None and `std` composes
+    NumPy's five steps."""
     if a._code not in _FLOAT_CODES or a._expr is not None or (dtype is not None and np.dtype(dtype) != a.dtype) or a.ndim == 0:
         return None
     if isinstance(axis, (tuple, list)):
@@ -2013,13 +2015,11 @@ def _std_fused(a, axis, dtype, ddof, keepdims, n):
     ax %= a.ndim
     if n - int(ddof) <= 0 or n < 2 or not a.is_c_contiguous or a.size == 0:
         return None
-    if not (ax == a.ndim - 1 or (ax == 0 and a.ndim == 2)):
-        return None
     kshape = a.shape[:ax] + (1,) + a.shape[ax + 1:]
     res = DeviceArray._new(kshape, a.dtype)
     try:
         _lib().var(a.desc(), res.desc(), ax, int(ddof), 1)
-    except ValueError:       # a form the kernel leaves to the composition (alignment, short / narrow shapes)
+    except ValueError:       # a form the kernel leaves to the composition (alignment, short / narrow shapes, most middle axes)
         return None
     return res if keepdims else reshape(res, a.shape[:ax] + a.shape[ax + 1:])
 
