@@ -371,15 +371,20 @@ int mdhip_vm_reduce(const mdhip_vm_program *prog, int reduce_op, const mdhip_arr
  * hiprtc for gfx950 and cached by signature; the interpreter remains the fallback
  * (small arrays, no libhiprtc, MDHIP_JIT=0). These two entry points are diagnostics:
  * compile-only check of a program (kind 0 = eval, 1 = full reduce, 2 = column
- * reduce (tiled), 3 = column reduce (sweep), 4 = eval + column reduce in one pass;
- * needs no device), and counters {kernels compiled, kernels launched}. Generated
- * kernels are named k_fused_<form>_<digest of the program signature>. */
+ * reduce (tiled), 3 = column reduce (sweep), 4 = eval + column reduce in one pass,
+ * 5 = eval over three / four collapsed axes, with read modes and index width from
+ * the program's own leaf descriptors; needs no device; on success `log` starts
+ * with the name the kernel would carry), and counters {kernels compiled, kernels
+ * launched}. Generated kernels are named k_fused_<form>_<digest of the program
+ * signature>. */
 int mdhip_vm_jit_probe(const mdhip_vm_program *prog, int kind, int reduce_op, int out_is_bool,
                        char *log, size_t log_capacity);
 /* outs[k][...] = progs[k](...) for n programs of ONE shape (e.g. the gradients of one
  * backward sweep, which share their operands): with run-time specialisation available and
  * 2..4 programs whose merged operand tables fit one launch, every distinct leaf is read once
- * and all results are written in the same pass; otherwise exactly n mdhip_vm_eval calls. */
+ * and all results are written in the same pass — over the (rows, inner) geometry and over three
+ * or four collapsed axes whose leaves have inner stride 0 or 1 (the geometry of mdhip_vm_eval's
+ * vector kernels); otherwise exactly n mdhip_vm_eval calls. */
 int mdhip_vm_eval_multi(const mdhip_vm_program *progs, const mdhip_array *outs, int n);
 /* out_eval[r][c] = prog(r, c) AND out_red[c] = reduce over r (reduce_op in {SUM, PROD, MAX, MIN}) of a 2-D
  * program in ONE pass over its operands: the elementwise product of a backward step and its

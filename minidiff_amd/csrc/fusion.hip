@@ -13,6 +13,8 @@
 // arrays of >= 2^18 elements run the specialised kernels of fusion_jit.inc):
 //   k_vm_eval_fast     (rows, inner) geometry: leaves contiguous / row- or column-
 //                      broadcast / stride-0, 16-B loads+stores
+//   k_vm_eval_axes     three / four collapsed axes, inner stride 0 or 1 in every leaf (the
+//                      broadcasts of a normalisation layer), 16-B loads+stores
 //   k_vm_eval_generic  any <=8-D strides, one element per lane
 //   k_vm_reduce_all    full reduction of the program's value (grid-strided sweep,
 //                      block partials + finishing block) — fused "...sum()"
@@ -485,6 +487,17 @@ template <class T> static int eval_typed(const mdhip_vm_program *pr, const mdhip
   }
   VmAxes A;
   if (axes_geometry(it, pr, out, &D, &A)) {
+    if (jit::enabled() && it.total >= jit::min_elems()) {
+      jit::Spec S;
+      S.kind = jit::EVAL;
+      jit::spec_single(&S, pr);
+      S.out_bool = to_bool;
+      jit::spec_axes(&S, D, A, (int64_t)md_dtype_size(out->dtype));
+      if (hipFunction_t fn = jit::get(S)) {
+        void *outs[1] = {out->data};
+        return jit::launch_axes(fn, S, D, A, pr->imm, outs);
+      }
+    }
     if (to_bool) k_vm_eval_axes<T, b8><<<md_grid_for(it.total >> 2), MD_BLOCK, 0, st>>>(D, A, (b8 *)out->data);
     else k_vm_eval_axes<T, T><<<md_grid_for(it.total >> 2), MD_BLOCK, 0, st>>>(D, A, (T *)out->data);
     return MD_LAUNCH_CHECK("vm_eval(axes)");
@@ -562,7 +575,18 @@ static int eval_multi(const mdhip_vm_program *progs, const mdhip_array *outs, in
   MdVmDev D;
   to_dev(&merged, &D);
   int64_t rows, inner;
-  if (!fast_geometry(it, merged.n_leaves, &merged, true, &D, &rows, &inner)) return MDHIP_OK;
+  if (!fast_geometry(it, merged.n_leaves, &merged, true, &D, &rows, &inner)) {
+    // three / four collapsed axes: the axes form of the same kernel, still one launch
+    VmAxes G;
+    if (!axes_geometry(it, &merged, &outs[0], &D, &G)) return MDHIP_OK;
+    jit::spec_axes(&M, D, G, (int64_t)n * (int64_t)md_dtype_size(merged.compute_dtype));
+    hipFunction_t fn = jit::get(M);
+    if (!fn) return MDHIP_OK;
+    void *po[4] = {};
+    for (int k = 0; k < n; ++k) po[k] = outs[k].data;
+    *done = true;
+    return jit::launch_axes(fn, M, D, G, merged.imm, po);
+  }
   int64_t bytes = (int64_t)n * it.total * (int64_t)md_dtype_size(merged.compute_dtype);
   for (int l = 0; l < merged.n_leaves; ++l)
     if (D.leaf[l].is) bytes += it.total * (int64_t)md_dtype_size(merged.leaves[l].dtype);
@@ -798,6 +822,26 @@ static void probe_modes(jit::Spec *S, const mdhip_vm_program *pr) {
   }
 }
 
+// .. and the form of an EVAL: the axes form when the leaves, over a dense output of their shape, keep three or four collapsed
+// axes (`force`: whatever they collapse to — probe kind 5); index width from the vector count
+static void probe_axes(jit::Spec *S, const mdhip_vm_program *pr, bool force) {
+  int nd = 0;
+  int64_t total = 0;
+  if (pr->n_leaves > 0) {
+    mdhip_array o = pr->leaves[0];
+    int64_t dense = 1;
+    for (int d = o.ndim - 1; d >= 0; --d) { o.strides[d] = dense; dense *= o.shape[d]; }
+    MdVmIter it;
+    if (md_vm_build_iter(&it, pr, &o, &o) == MDHIP_OK) { nd = it.ndim; total = it.total; }
+  }
+  if (nd != 3 && nd != 4) {
+    if (!force) return;
+    nd = 3;
+  }
+  S->axes = nd;
+  S->wide = (total >> 2) >= (1ll << 31) || md_opt(MD_OPT_JIT_AXES_WIDE) == 1;
+}
+
 }  // namespace
 
 extern "C" {
@@ -835,9 +879,12 @@ int mdhip_vm_jit_probe_multi(const mdhip_vm_program *progs, int n, char *log, si
     probe_modes(&one, &progs[k]);
     for (int l = 0; l < progs[k].n_leaves; ++l) M.leaf_mode[M.leaf_map[k][l]] = one.leaf_mode[M.leaf_map[k][l]];
   }
+  probe_axes(&M, &merged, false);
   std::vector<char> code;
   std::string l;
-  const int rc = jit::compile(jit::gen_source(M, "k_fused_probe"), &code, &l);
+  const std::string name = jit::make_name(M, jit::make_key(M));
+  const int rc = jit::compile(jit::gen_source(M, name), &code, &l);
+  if (rc == 0) l = name + "\n" + l;  // the log of a successful probe starts with the kernel's name: which form was generated
   if (log && log_cap) { strncpy(log, l.c_str(), log_cap - 1); log[log_cap - 1] = 0; }
   if (rc != 0) return md_fail(MDHIP_ERUNTIME, "fused-kernel compilation failed: %.300s", l.c_str());
   return MDHIP_OK;
@@ -845,20 +892,23 @@ int mdhip_vm_jit_probe_multi(const mdhip_vm_program *progs, int n, char *log, si
 
 int mdhip_vm_jit_probe(const mdhip_vm_program *pr, int kind, int reduce_op, int out_is_bool, char *log, size_t log_cap) {
   MD_TRY(md_vm_check(pr));
-  if (kind < 0 || kind > 4)
-    return md_fail(MDHIP_EVALUE, "jit probe: kind must be 0 (eval), 1 (reduce all), 2 (reduce columns, tiled), 3 (reduce columns, sweep) or 4 (eval + reduce columns)");
+  if (kind < 0 || kind > 5)
+    return md_fail(MDHIP_EVALUE, "jit probe: kind must be 0 (eval), 1 (reduce all), 2 (reduce columns, tiled), 3 (reduce columns, sweep), 4 (eval + reduce columns) or 5 (eval over three / four axes)");
   jit::Spec S;
-  S.kind = kind >= 3 ? jit::SWEEP : kind;
+  S.kind = kind == 5 ? jit::EVAL : kind >= 3 ? jit::SWEEP : kind;
   jit::spec_single(&S, pr);
   probe_modes(&S, pr);
+  if (kind == 5) probe_axes(&S, pr, true);
   S.rop = reduce_op;
-  S.out_bool = out_is_bool != 0 && kind == 0;
+  S.out_bool = out_is_bool != 0 && (kind == 0 || kind == 5);
   S.store = kind == 4;
   S.Q = 4;
   S.RU = 2;
   std::vector<char> code;
   std::string l;
-  const int rc = jit::compile(jit::gen_source(S, "k_fused_probe"), &code, &l);
+  const std::string name = jit::make_name(S, jit::make_key(S));
+  const int rc = jit::compile(jit::gen_source(S, name), &code, &l);
+  if (rc == 0) l = name + "\n" + l;  // the log of a successful probe starts with the kernel's name: which form was generated
   if (log && log_cap) { strncpy(log, l.c_str(), log_cap - 1); log[log_cap - 1] = 0; }
   if (rc != 0) return md_fail(MDHIP_ERUNTIME, "fused-kernel compilation failed: %.300s", l.c_str());
   return MDHIP_OK;

@@ -42,6 +42,11 @@ struct JArgs {
   void *partial;     // RED_ALL / SWEEP: block partials, combined by the block that arrives last (md_ticket.h)
   void *tickets;     // .. and its counters
 };
+// the axes form of EVAL (three / four collapsed axes): extents of the two inner outer axes and, per leaf, its three outer strides
+struct JAxArgs : JArgs {
+  long long e1, e2;
+  long long st[MDHIP_VM_MAX_LEAVES][3];
+};
 
 // ---- hiprtc through dlopen (no link-time dependency) ---------------------------------
 typedef struct _hiprtcProgram *rtcProgram;
@@ -148,6 +153,8 @@ static const char *reduce_name(int op) {
 //   LM_VEC    unit inner stride: one 16-B (4-B for bool) vector load per group of 4 elements
 //   LM_ROWB   inner stride 0, row stride != 0 (a column broadcast): one scalar load per row
 //   LM_CONST  ONE device element behind a stride-0 view (the backward seed): read once in the prologue
+//   (the axes form of EVAL: LM_VEC at r0*s0 + r1*s1 + r2*s2 + c, LM_ROWB one load per group at the outer offset, LM_CONST when
+//    the three outer strides are 0 as well)
 //   LM_ROWINV (sweep kernels only) unit inner stride, row stride 0 (the bias row): the lane's column
 //             vectors are loaded once, before the row loop
 enum { LM_VEC = 0, LM_ROWB = 1, LM_CONST = 2, LM_ROWINV = 3 };
@@ -168,6 +175,8 @@ struct Spec {
   bool store = false;               // SWEEP: also write the evaluated value (eval + reduce-to-shape in one pass)
   int Q = 1, RU = 1;                // SWEEP: column vectors per lane (row = Q x 1024 elements), rows per trip
   int U = 2;                        // EVAL / RED_ALL: independent vector groups per lane and trip
+  int axes = 0;                     // EVAL: 0 the (rows, inner) form | 3, 4 that many collapsed axes (fusion.hip's axes_geometry)
+  bool wide = false;                // EVAL over axes: 64-bit vector index (2^31 vectors and more), else 32-bit
 };
 
 static void spec_single(Spec *S, const mdhip_vm_program *pr) {
@@ -288,6 +297,7 @@ static void gen_prelude(std::ostringstream &o, const Spec &S, const std::string 
 template <class S, int N> struct alignas(sizeof(S) * N > 16 ? 16 : sizeof(S) * N) JVec { S v[N]; };
 struct JLeaf { const void *p; long long os; int is; int pad; };
 struct JArgs { JLeaf leaf[8]; double imm[48]; void *out; long long rows, inner; long long n_out, n_red, chunk; void *outs[4]; long long dq, dr; void *partial; void *tickets; };
+struct JAxArgs : JArgs { long long e1, e2; long long st[8][3]; };
 template <class S> __device__ __forceinline__ T jcvt(S x) { return (T)x; }
 template <> __device__ __forceinline__ T jcvt<uint8_t>(uint8_t x) { return (T)(x != 0); }
 template <class V> __device__ __forceinline__ V jld(const V *p) {
@@ -368,6 +378,20 @@ struct LeafText {
       if (m == LM_VEC) o << ind << "T l" << l << sfx << "[4]; jloadv<" << St << ">(A.leaf[" << l << "], " << row << ", " << c << ", l" << l << sfx << ");\n";
       else if (m == LM_ROWINV) o << ind << "T l" << l << sfx << "[4]; jloadv<" << St << ">(A.leaf[" << l << "], 0, " << c << ", l" << l << sfx << ");\n";
       else if (m == LM_ROWB) o << ind << "const T l" << l << sfx << " = jload1<" << St << ">(A.leaf[" << l << "], (" << row << ") * A.leaf[" << l << "].os);\n";
+    }
+    return o.str();
+  }
+  // loads of one group of the axes form: the position is in r0<sfx> (four axes only), r1<sfx>, r2<sfx>, c<sfx>
+  std::string vec_axes(const std::string &sfx, const char *ind = "    ") const {
+    std::ostringstream o;
+    for (int l = 0; l < S.n_leaves; ++l) {
+      const int m = S.leaf_mode[l];
+      if (m != LM_VEC && m != LM_ROWB) continue;
+      const char *St = storage_name(S.leaf_dtype[l]);
+      const std::string L = "A.st[" + std::to_string(l) + "]";
+      const std::string off = (S.axes == 4 ? "r0" + sfx + " * " + L + "[0] + " : std::string()) + "r1" + sfx + " * " + L + "[1] + r2" + sfx + " * " + L + "[2]";
+      if (m == LM_VEC) o << ind << "T l" << l << sfx << "[4]; jloadv<" << St << ">(A.leaf[" << l << "], 0, " << off << " + c" << sfx << ", l" << l << sfx << ");\n";
+      else o << ind << "const T l" << l << sfx << " = jload1<" << St << ">(A.leaf[" << l << "], " << off << ");\n";
     }
     return o.str();
   }
@@ -467,7 +491,10 @@ constexpr unsigned LM_ALL = 0xFu;
 
 static std::string kind_tag(const Spec &S) {
   switch (S.kind) {
-    case EVAL: return S.n > 1 ? "eval" + std::to_string(S.n) : (S.out_bool ? "evalb" : "eval");
+    case EVAL: {
+      const std::string form = S.axes ? "evalaxes" : "eval";
+      return S.n > 1 ? form + std::to_string(S.n) : (S.out_bool && !S.axes ? "evalb" : form);
+    }
     case RED_ALL: return "redall";
     case RED_COLS: return "redcols";
   }
@@ -489,7 +516,38 @@ static std::string gen_source(const Spec &S, const std::string &kname) {
     }
     return e.str();
   };
-  if (S.kind == EVAL) {
+  if (S.kind == EVAL && S.axes) {
+    // Three / four collapsed axes (k_vm_eval_axes with the expression inlined): a lane takes U vectors of four per trip, the outer
+    // position of each from two or three divisions of its vector index — 32-bit, or 64-bit from 2^31 vectors on: the host's choice.
+    // The output is dense, so its offset is the vector index itself.
+    o << "typedef " << (S.wide ? "long long" : "unsigned") << " I;\n"
+         "extern \"C\" __global__ void __launch_bounds__(256) KNAME(JAxArgs A) {\n"
+         "  const I nv = (I)(A.inner >> 2), total = (I)A.rows * nv, e1 = (I)A.e1, e2 = (I)A.e2;\n"
+         "  const I gid = (I)blockIdx.x * (I)blockDim.x + (I)threadIdx.x, gs = (I)gridDim.x * (I)blockDim.x;\n"
+      << LT.pro() << "  I v = gid;\n";
+    auto position = [&](const std::string &sfx, const std::string &vx) {
+      std::ostringstream e;
+      e << "    const I v" << sfx << " = " << vx << ", w" << sfx << " = v" << sfx << " / nv, q" << sfx << " = w" << sfx << " / e2;\n"
+        << "    const long long off" << sfx << " = (long long)v" << sfx << " << 2, c" << sfx << " = (long long)(v" << sfx << " - w" << sfx << " * nv) << 2, r2" << sfx
+        << " = (long long)(w" << sfx << " - q" << sfx << " * e2);\n";
+      if (S.axes == 4)
+        e << "    const I t" << sfx << " = q" << sfx << " / e1;\n    const long long r0" << sfx << " = (long long)t" << sfx << ", r1" << sfx << " = (long long)(q" << sfx << " - t"
+          << sfx << " * e1);\n";
+      else
+        e << "    const long long r1" << sfx << " = (long long)q" << sfx << ";\n";
+      return e.str();
+    };
+    o << "  for (; v + " << (S.U - 1) << " * gs < total; v += " << S.U << " * gs) {\n";
+    for (int u = 0; u < S.U; ++u) {
+      const std::string sfx = "_" + std::to_string(u);
+      o << position(sfx, "v + " + std::to_string(u) + " * gs") << LT.vec_axes(sfx);
+    }
+    for (int u = 0; u < S.U; ++u) {
+      const std::string sfx = "_" + std::to_string(u);
+      o << LT.trig(sfx, LM_ALL) << emit_outputs(sfx, "off" + sfx, "    ");
+    }
+    o << "  }\n  for (; v < total; v += gs) {\n" << position("_t", "v") << LT.vec_axes("_t") << LT.trig("_t", LM_ALL) << emit_outputs("_t", "off_t", "    ") << "  }\n}\n";
+  } else if (S.kind == EVAL) {
     o << "extern \"C\" __global__ void __launch_bounds__(256) KNAME(JArgs A) {\n"
          "  const long long nv = A.inner >> 2, total = A.rows * nv;\n"
          "  const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x, gs = (long long)gridDim.x * blockDim.x;\n"
@@ -710,7 +768,7 @@ static std::string gen_source(const Spec &S, const std::string &kname) {
 
 static std::string make_key(const Spec &S) {
   std::ostringstream k;
-  k << S.kind << ':' << (int)S.f32 << (int)S.out_bool << (int)S.nt << (int)S.nt_store << (int)S.store << ':' << S.rop << ':' << S.Q << ':' << S.RU << ':' << S.U << ':' << S.n;
+  k << S.kind << ':' << (int)S.f32 << (int)S.out_bool << (int)S.nt << (int)S.nt_store << (int)S.store << ':' << S.rop << ':' << S.Q << ':' << S.RU << ':' << S.U << ':' << S.n << ':' << S.axes << (int)S.wide;
   for (int p = 0; p < S.n; ++p) {
     k << '/';
     for (int i = 0; i < S.pr[p]->n_instr; ++i) k << std::hex << S.pr[p]->ctrl[i] << ',';
@@ -789,8 +847,8 @@ static hipFunction_t get(const Spec &S) {
   return e.fn;
 }
 
-static int launch(hipFunction_t fn, JArgs &A, dim3 grid) {
-  size_t sz = sizeof(JArgs);
+template <class Args> static int launch(hipFunction_t fn, Args &A, dim3 grid) {
+  size_t sz = sizeof(Args);
   void *cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &A, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
   ++g_launched;
   hipEvent_t e0, e1;
@@ -834,6 +892,46 @@ static int stream_grid(JArgs *A, int64_t rows, int64_t inner, int blocks_per_cu 
   A->dq = nv > 0 ? gs / nv : 0;
   A->dr = nv > 0 ? gs % nv : 0;
   return grid;
+}
+
+static int axes_grid(const Spec &S, const VmAxes &G) {
+  const int cap = md_max_blocks();
+  return md_grid_for(G.rows * G.nv, MD_BLOCK, cap != MD_NUM_CUS * 8 ? cap : MD_NUM_CUS * eval_blocks(S));
+}
+// The axes form of EVAL (fusion.hip's axes_geometry passed): read modes from the stride table, index width from the vector count
+// (option jit_axes_wide = 1 forces the 64-bit form: tests), non-temporal by the streamed bytes. `out_elem_bytes`: all outputs together.
+static void spec_axes(Spec *S, const MdVmDev &D, const VmAxes &G, int64_t out_elem_bytes) {
+  const int64_t total = G.rows * G.nv * 4;
+  int64_t bytes = total * out_elem_bytes;
+  S->axes = G.e0 != 1 ? 4 : 3;
+  for (int l = 0; l < S->n_leaves; ++l) {
+    if (D.leaf[l].is) {
+      S->leaf_mode[l] = LM_VEC;
+      bytes += total * (int64_t)md_dtype_size(S->leaf_dtype[l]);
+    } else {
+      S->leaf_mode[l] = (G.st[l][0] | G.st[l][1] | G.st[l][2]) == 0 ? LM_CONST : LM_ROWB;
+    }
+  }
+  S->nt = bytes > ((int64_t)320 << 20);
+  eval_shape(S);
+  // 32-bit index arithmetic while the largest value the trip loop forms, vector count + U grid strides, stays below 2^31
+  S->wide = G.rows * G.nv + (int64_t)S->U * axes_grid(*S, G) * MD_BLOCK >= (1ll << 31) || md_opt(MD_OPT_JIT_AXES_WIDE) == 1;
+}
+static int launch_axes(hipFunction_t fn, const Spec &S, const MdVmDev &D, const VmAxes &G, const double *imm, void *const *outs) {
+  JAxArgs A;
+  memset(&A, 0, sizeof A);
+  for (int l = 0; l < S.n_leaves; ++l) {
+    A.leaf[l].p = D.leaf[l].p;
+    A.leaf[l].is = D.leaf[l].is;
+    for (int j = 0; j < 3; ++j) A.st[l][j] = G.st[l][j];
+  }
+  for (int i = 0; i < S.n_imm; ++i) A.imm[i] = imm[i];
+  for (int k = 0; k < S.n; ++k) A.outs[k] = outs[k];
+  A.rows = G.rows;
+  A.inner = G.nv << 2;
+  A.e1 = G.e1;
+  A.e2 = G.e2;
+  return launch(fn, A, dim3((unsigned)axes_grid(S, G)));
 }
 
 }  // namespace jit

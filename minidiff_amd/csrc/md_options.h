@@ -41,6 +41,7 @@
   X(GEMM_WIDEN, "gemm_widen", 1, 'x')                  /* 0: float16 -> float32 / int8 -> int32 products convert their operands first (A/B) */ \
   X(JIT_U, "jit_u", 0, 'x')                            /* vector groups per lane and trip of the generated streaming kernels (0: by form) */ \
   X(JIT_BLOCKS, "jit_blocks", 0, 'x')                  /* blocks per CU of the generated EVAL kernels (0: by form) */                     \
+  X(JIT_AXES_WIDE, "jit_axes_wide", 0, 'x')            /* 1: generated three / four-axis EVAL kernels take the 64-bit index form at any size (tests) */ \
   X(SWEEP_NB, "sweep_nb", 0, 'x')                      /* fused eval + column sum: row bands (0: by shape) */                   \
   X(SWEEP_RU, "sweep_ru", 0, 'x')                                                                                               \
   X(SWEEP_NT_STORE, "sweep_nt_store", 1, 'x')                                                                                   \
