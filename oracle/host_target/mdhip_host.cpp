@@ -116,16 +116,28 @@ struct HostExec {
     }
     return MDHIP_OK;
   }
+  // reduced elements [r0, r1) of one output, PAIRWISE over leaves of eight: a float sum of n elements is then within
+  // (7 + ceil(log2(n / 8))) unit roundoffs of sum|x| in the worst case (< 34 for any n that fits memory) — one running
+  // accumulator is (n - 1) away in the worst case and ~sqrt(n / 3) on positive data, more than the product's kernels (lanes,
+  // waves, bands: trees of short runs) and more than the bound the reduction tests hold BOTH libraries to
+  template <class R, class Tacc>
+  static Tacc fold(const MdRedPlan &pl, const mdhip_array *x, int64_t xo, int64_t r0, int64_t r1) {
+    if (r1 - r0 <= 8) {
+      Tacc acc = R::template identity<Tacc>();
+      for (int64_t r = r0; r < r1; ++r) acc = R::combine(acc, md_load<Tacc>(x->data, x->dtype, xo + md_red_offset(pl, r)));
+      return acc;
+    }
+    const int64_t mid = r0 + (r1 - r0) / 2;
+    const Tacc a = fold<R, Tacc>(pl, x, xo, r0, mid);
+    return R::combine(a, fold<R, Tacc>(pl, x, xo, mid, r1));
+  }
   template <class R, class Tacc, class To>
   static int reduce(const MdRedPlan &pl, const mdhip_array *x, const mdhip_array *out) {
     To *o = (To *)out->data;
     for (int64_t i = 0; i < pl.n_out; ++i) {
       int64_t xo, oo;
       md_red_kept_offsets(pl, i, &xo, &oo);
-      Tacc acc = R::template identity<Tacc>();
-      for (int64_t r = 0; r < pl.n_red; ++r)
-        acc = R::combine(acc, md_load<Tacc>(x->data, x->dtype, xo + md_red_offset(pl, r)));
-      o[oo] = md_cast<To>(acc);
+      o[oo] = md_cast<To>(fold<R, Tacc>(pl, x, xo, 0, pl.n_red));
     }
     return MDHIP_OK;
   }
