@@ -360,8 +360,18 @@ typedef struct mdhip_vm_program {
 /* out[...] = program(...)  (out dtype: compute_dtype, or BOOL for a 0/1 result) */
 int mdhip_vm_eval(const mdhip_vm_program *prog, const mdhip_array *out);
 /* out = reduce(program) with reduce_op in {SUM, PROD, MAX, MIN}. `shape` is the
- * program's shape (leaves are broadcast to it); supported forms: all axes reduced,
- * or a 2-D program reduced over axis 0 (reduce-to-shape of a row broadcast).
+ * program's shape (leaves are broadcast to it); supported forms: all axes reduced;
+ * a 2-D program reduced over axis 0 (reduce-to-shape of a row broadcast); or the
+ * TRAILING axes reduced (per-row statistics): every axis behind the first reduced one
+ * is reduced or has extent 1 and some kept axis is longer than 1. With n_red the product
+ * of the reduced extents and n_out that of the kept ones, `out` holds n_out dense
+ * elements of the compute dtype; the program must iterate as (n_out, n_red) — or as one
+ * axis, all leaves dense or fully broadcast — with n_red % 4 == 0 and per leaf an inner
+ * stride of 0 or 1 (a dense leaf, a per-row scalar such as the m of exp(x - m), a
+ * row-invariant vector, a constant; unit-stride leaves 16-byte aligned with row strides
+ * that are multiples of 4). One launch, no intermediate array, the order of combination
+ * fixed by (n_out, n_red) alone. Rows longer than 2048 elements need n_out >= 256 (rows
+ * are not split over blocks).
  * Anything else returns MDHIP_EVALUE and the caller materialises first. */
 int mdhip_vm_reduce(const mdhip_vm_program *prog, int reduce_op, const mdhip_array *shape_like,
                     const mdhip_array *out, uint32_t axis_mask);
@@ -373,7 +383,8 @@ int mdhip_vm_reduce(const mdhip_vm_program *prog, int reduce_op, const mdhip_arr
  * compile-only check of a program (kind 0 = eval, 1 = full reduce, 2 = column
  * reduce (tiled), 3 = column reduce (sweep), 4 = eval + column reduce in one pass,
  * 5 = eval over three / four collapsed axes, with read modes and index width from
- * the program's own leaf descriptors; needs no device; on success `log` starts
+ * the program's own leaf descriptors, 6 = row reduce with a wave per row, 7 = row
+ * reduce with a block per row; needs no device; on success `log` starts
  * with the name the kernel would carry), and counters {kernels compiled, kernels
  * launched}. Generated kernels are named k_fused_<form>_<digest of the program
  * signature>. */

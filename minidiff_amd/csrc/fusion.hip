@@ -20,6 +20,9 @@
 //                      block partials + finishing block) — fused "...sum()"
 //   k_vm_reduce_cols   2-D program reduced over rows: lane owns 4 columns, rows
 //                      split over gridDim.y — fused reduce-to-shape (bias gradient)
+//   k_vm_reduce_rows   program reduced over its trailing axes: a wave per row, lanes
+//                      stride the row's vector groups — fused per-row statistics
+//                      (softmax denominators, row-wise dots, the gradient of a (R,1) scale)
 // Reductions are deterministic (no atomics).
 #include <vector>
 
@@ -374,6 +377,48 @@ __global__ void __launch_bounds__(MD_BLOCK) k_vm_reduce_cols(MdVmDev P, int64_t 
   }
 }
 
+// (n_out rows, n_red columns) program reduced over the columns — the trailing axes of the recorded shape. One form for every
+// row length: a wave per row, four rows per block; lane l takes the row's vector groups l, l + 64, .. and alternates between two
+// sets of four accumulators (even / odd trips: half the serial chain of additions — a row of 8196 passes 17 trips per set, not
+// 33), then the sets and their four components merge and a 64-lane shuffle tree finishes; lane 0 stores. The order depends on
+// (n_out, n_red) alone. Lanes past the last vector group re-evaluate group 0 of their row and waves past the last row the last
+// row, both masked out of the combine / the store: every wave runs the interpreter in step (uniform control flow).
+template <class R, class T>
+__global__ void __launch_bounds__(MD_BLOCK) k_vm_reduce_rows(MdVmDev P, int64_t n_out, int64_t n_red, T *dst) {
+  MD_VM_PROLOGUE;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int64_t row_raw = (int64_t)blockIdx.x * (MD_BLOCK / 64) + w;
+  const bool row_ok = row_raw < n_out;
+  const int64_t row = row_ok ? row_raw : n_out - 1;
+  const int64_t nv = n_red >> 2;
+  T a[VW], b[VW];
+#pragma unroll
+  for (int j = 0; j < VW; ++j) { a[j] = R::template identity<T>(); b[j] = a[j]; }
+  bool odd = false;
+  for (int64_t g0 = 0; g0 < nv; g0 += 64) {
+    const int64_t g = g0 + lane;
+    const bool ok = g < nv;
+    FastLoader<T> ld{P, {}, {}};
+    ld.row[0] = row;
+    ld.c[0] = (ok ? g : 0) << 2;
+    T r[VW];
+    md_vm_run<T, VW>(P.n_instr, fetch, ld, r);
+#pragma unroll
+    for (int j = 0; j < VW; ++j) {
+      const T c = R::combine(odd ? b[j] : a[j], r[j]);
+      a[j] = (ok && !odd) ? c : a[j];
+      b[j] = (ok && odd) ? c : b[j];
+    }
+    odd = !odd;
+  }
+#pragma unroll
+  for (int j = 0; j < VW; ++j) a[j] = R::combine(a[j], b[j]);
+  T acc = R::combine(R::combine(a[0], a[1]), R::combine(a[2], a[3]));
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) acc = R::combine(acc, md_shfl_down(acc, d));
+  if (lane == 0 && row_ok) dst[row_raw] = acc;
+}
+
 }  // namespace
 #include "fusion_jit.inc"
 namespace {
@@ -607,6 +652,11 @@ static int eval_multi(const mdhip_vm_program *progs, const mdhip_array *outs, in
 
 static int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// Trailing-axis reductions (mdhip_vm_reduce's third form): rows up to 64 lanes x 8 groups x 4 elements go a wave per row in the
+// generated kernels, longer ones a block per row; long rows need at least a row per CU (no cross-block split yet)
+constexpr int64_t VM_ROWS_WAVE_MAX = 64 * 4 * 8;
+constexpr int64_t VM_ROWS_MIN_OUT = MD_NUM_CUS;
+
 // A program whose operands are all dense or fully broadcast collapses to ONE axis; the column reductions want it as
 // (R rows, C columns) again: dense leaves advance C elements per row, broadcast ones none.
 static bool uncollapse_2d(const MdVmIter &it, int n_leaves, MdVmDev *D, int64_t R, int64_t C, int64_t *rows, int64_t *inner) {
@@ -786,7 +836,52 @@ static int reduce_typed(const mdhip_vm_program *pr, int rop, const mdhip_array *
     mdhip_free(partial);
     return rc;
   }
-  return md_fail(MDHIP_EVALUE, "vm_reduce: only full reductions and axis-0 reductions of 2-D programs are fused");
+  // reduce over the TRAILING axes: every axis behind the first reduced one is reduced or has extent 1, some kept axis is longer
+  // than 1. The iteration is (n_out, n_red) as it stands, or one axis (all leaves dense or fully broadcast) taken apart again.
+  int first = 0;
+  while (first < nd && !((mask >> first) & 1u)) ++first;
+  bool trailing = mask != 0 && (mask >> nd) == 0;
+  int64_t n_red = 1;
+  for (int d = first; d < nd; ++d) {
+    if ((mask >> d) & 1u) n_red *= shape_like->shape[d];
+    else trailing = trailing && shape_like->shape[d] == 1;
+  }
+  if (trailing && it.total / n_red > 1) {
+    const int64_t n_out = it.total / n_red;
+    if (!uncollapse_2d(it, pr->n_leaves, &D, n_out, n_red, &rows, &inner))
+      return md_fail(MDHIP_EVALUE, "vm_reduce: a trailing-axis reduction needs (rows, reduced) geometry with rows of whole 16-byte groups");
+    int64_t out_elems = 1;
+    for (int d = 0; d < out->ndim; ++d) out_elems *= out->shape[d];
+    if (out_elems != n_out) return md_fail(MDHIP_EVALUE, "vm_reduce: out holds %lld elements for %lld rows", (long long)out_elems, (long long)n_out);
+    if (n_out >= (1ll << 31)) return md_fail(MDHIP_EVALUE, "vm_reduce: %lld rows exceed the grid of the row kernels", (long long)n_out);
+    // long rows are walked by ONE block (generated) or wave (interpreter) each: fewer rows than CUs would leave the chip idle
+    // where the eager route splits rows over blocks
+    if (n_red > VM_ROWS_WAVE_MAX && n_out < VM_ROWS_MIN_OUT)
+      return md_fail(MDHIP_EVALUE, "vm_reduce: %lld rows of %lld elements are too few to fill the device without splitting rows", (long long)n_out, (long long)n_red);
+    if (jit::enabled() && it.total >= jit::min_elems()) {
+      int64_t rbytes = 0;
+      for (int l = 0; l < pr->n_leaves; ++l)
+        if (D.leaf[l].is && D.leaf[l].os) rbytes += it.total * (int64_t)md_dtype_size(pr->leaves[l].dtype);
+      jit::Spec S;
+      S.kind = jit::RED_ROWS;
+      jit::spec_single(&S, pr);
+      jit::spec_modes(&S, D, rows);
+      S.rop = rop;
+      S.nt = rbytes > ((int64_t)320 << 20);
+      const int64_t nvec = n_red >> 2;   // wave per row: 1 / 2 / 4 / 8 vector groups per lane; block per row (NV 0) above
+      S.NV = n_red > VM_ROWS_WAVE_MAX ? 0 : nvec <= 64 ? 1 : nvec <= 128 ? 2 : nvec <= 256 ? 4 : 8;
+      if (hipFunction_t fn = jit::get(S)) {
+        jit::JArgs A;
+        jit::fill_args(&A, pr, D);
+        A.rows = rows; A.inner = inner; A.n_out = n_out; A.n_red = n_red;
+        A.out = out->data;
+        return jit::launch(fn, A, dim3((unsigned)(S.NV ? ceil_div(n_out, 4) : n_out)));
+      }
+    }
+    k_vm_reduce_rows<R, T><<<(unsigned)ceil_div(n_out, MD_BLOCK / 64), MD_BLOCK, 0, st>>>(D, n_out, n_red, (T *)out->data);
+    return MD_LAUNCH_CHECK("vm_reduce(rows)");
+  }
+  return md_fail(MDHIP_EVALUE, "vm_reduce: only full reductions, axis-0 reductions of 2-D programs and reductions over trailing axes are fused");
 }
 
 // out_eval[r][c] = program(r, c) and out_red[c] = reduce over r, ONE pass (generated sweep kernel only)
@@ -892,10 +987,11 @@ int mdhip_vm_jit_probe_multi(const mdhip_vm_program *progs, int n, char *log, si
 
 int mdhip_vm_jit_probe(const mdhip_vm_program *pr, int kind, int reduce_op, int out_is_bool, char *log, size_t log_cap) {
   MD_TRY(md_vm_check(pr));
-  if (kind < 0 || kind > 5)
-    return md_fail(MDHIP_EVALUE, "jit probe: kind must be 0 (eval), 1 (reduce all), 2 (reduce columns, tiled), 3 (reduce columns, sweep), 4 (eval + reduce columns) or 5 (eval over three / four axes)");
+  if (kind < 0 || kind > 7)
+    return md_fail(MDHIP_EVALUE, "jit probe: kind must be 0 (eval), 1 (reduce all), 2 (reduce columns, tiled), 3 (reduce columns, sweep), 4 (eval + reduce columns), 5 (eval over three / four axes), 6 (reduce rows, a wave per row) or 7 (reduce rows, a block per row)");
   jit::Spec S;
-  S.kind = kind == 5 ? jit::EVAL : kind >= 3 ? jit::SWEEP : kind;
+  S.kind = kind >= 6 ? jit::RED_ROWS : kind == 5 ? jit::EVAL : kind >= 3 ? jit::SWEEP : kind;
+  S.NV = kind == 6 ? 2 : 0;
   jit::spec_single(&S, pr);
   probe_modes(&S, pr);
   if (kind == 5) probe_axes(&S, pr, true);

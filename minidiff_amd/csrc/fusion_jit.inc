@@ -6,8 +6,8 @@
 // Constants and geometry stay kernel ARGUMENTS, so changing a scalar or a shape never
 // recompiles. Any failure (no libhiprtc, compile error) falls back to the interpreter.
 //
-// Generated kernels mirror the interpreter's three shapes (eval / full reduce / column
-// reduce) but with the expression inlined: all leaf loads of an element group are
+// Generated kernels mirror the interpreter's shapes (eval / full reduce / column
+// reduce / row reduce) but with the expression inlined: all leaf loads of an element group are
 // issued up front as 16-B vector loads, the body is register-only, occupancy is that
 // of a plain streaming kernel — i.e. HBM-bound at the fused byte count.
 #include <dlfcn.h>
@@ -150,7 +150,8 @@ static const char *reduce_name(int op) {
 // ---- what one generated kernel is ----------------------------------------------------------------
 // How a leaf is read is a compile-time property of the generated kernel (part of the cache key), so
 // that the loads of one trip are unconditional and issue back to back:
-//   LM_VEC    unit inner stride: one 16-B (4-B for bool) vector load per group of 4 elements
+//   LM_VEC    unit inner stride: one 16-B (4-B for bool) vector load per group of 4 elements (RED_ROWS: also the row-invariant
+//             vector, at row stride 0 — every row re-reads it from the caches)
 //   LM_ROWB   inner stride 0, row stride != 0 (a column broadcast): one scalar load per row
 //   LM_CONST  ONE device element behind a stride-0 view (the backward seed): read once in the prologue
 //   (the axes form of EVAL: LM_VEC at r0*s0 + r1*s1 + r2*s2 + c, LM_ROWB one load per group at the outer offset, LM_CONST when
@@ -158,7 +159,7 @@ static const char *reduce_name(int op) {
 //   LM_ROWINV (sweep kernels only) unit inner stride, row stride 0 (the bias row): the lane's column
 //             vectors are loaded once, before the row loop
 enum { LM_VEC = 0, LM_ROWB = 1, LM_CONST = 2, LM_ROWINV = 3 };
-enum Kind { EVAL = 0, RED_ALL = 1, RED_COLS = 2, SWEEP = 3 };
+enum Kind { EVAL = 0, RED_ALL = 1, RED_COLS = 2, SWEEP = 3, RED_ROWS = 4 };
 
 struct Spec {
   int kind = EVAL;
@@ -177,6 +178,7 @@ struct Spec {
   int U = 2;                        // EVAL / RED_ALL: independent vector groups per lane and trip
   int axes = 0;                     // EVAL: 0 the (rows, inner) form | 3, 4 that many collapsed axes (fusion.hip's axes_geometry)
   bool wide = false;                // EVAL over axes: 64-bit vector index (2^31 vectors and more), else 32-bit
+  int NV = 0;                       // RED_ROWS: 1, 2, 4, 8 vector groups per lane, a wave per row | 0 a block per row
 };
 
 static void spec_single(Spec *S, const mdhip_vm_program *pr) {
@@ -446,20 +448,23 @@ struct LeafText {
     }
     return o.str();
   }
-  std::string args(const std::string &sfx, const std::string &j) const {
+  // (`rowb`: the suffix of the LM_ROWB leaves where they are loaded apart from the vector groups — once per row in RED_ROWS)
+  std::string args(const std::string &sfx, const std::string &j, const char *rowb = nullptr) const {
     std::ostringstream o;
+    const std::string rsfx = rowb ? std::string(rowb) : sfx;
     for (int l = 0; l < S.n_leaves; ++l) {
       const int m = S.leaf_mode[l];
       if (m == LM_CONST) o << ", k" << l;
-      else if (m == LM_ROWB) o << ", l" << l << sfx;
+      else if (m == LM_ROWB) o << ", l" << l << rsfx;
       else o << ", l" << l << sfx << "[" << j << "]";
     }
     for (int l = 0; l < S.n_leaves; ++l) {
       const int m = S.leaf_mode[l];
       const bool arr = m == LM_VEC || m == LM_ROWINV;
       const std::string pre = m == LM_CONST ? "k" : "";
-      if (tu.s[l]) o << ", " << pre << "sn" << l << (m == LM_CONST ? "" : sfx) << (arr ? "[" + j + "]" : "");
-      if (tu.c[l]) o << ", " << pre << "cs" << l << (m == LM_CONST ? "" : sfx) << (arr ? "[" + j + "]" : "");
+      const std::string sf = m == LM_CONST ? std::string() : m == LM_ROWB ? rsfx : sfx;
+      if (tu.s[l]) o << ", " << pre << "sn" << l << sf << (arr ? "[" + j + "]" : "");
+      if (tu.c[l]) o << ", " << pre << "cs" << l << sf << (arr ? "[" + j + "]" : "");
     }
     return o.str();
   }
@@ -497,6 +502,7 @@ static std::string kind_tag(const Spec &S) {
     }
     case RED_ALL: return "redall";
     case RED_COLS: return "redcols";
+    case RED_ROWS: return S.NV ? "redrowsw" + std::to_string(S.NV) : "redrowsb";
   }
   return S.store ? "evalcols" : "sweepcols";
 }
@@ -603,6 +609,62 @@ static std::string gen_source(const Spec &S, const std::string &kname) {
   if (threadIdx.x == 0) ((T *)A.out)[0] = R::combine(R::combine(smem[0], smem[1]), R::combine(smem[2], smem[3]));
 }
 )";
+  } else if (S.kind == RED_ROWS) {
+    // (n_out rows, n_red columns) reduced over the columns; row-broadcast leaves (the m of exp(x - m)) cost one scalar load per row
+    const unsigned vecm = 1u << LM_VEC, rowb = 1u << LM_ROWB;
+    auto combine = [&](const std::string &acc, const std::string &sfx, const char *ind) {
+      return std::string(ind) + "#pragma unroll\n" + ind + "for (int j = 0; j < 4; ++j) " + acc + "[j] = R::combine(" + acc + "[j], body0(A" + LT.args(sfx, "j", "_r") + "));\n";
+    };
+    if (S.NV) {
+      // short rows (reduce.hip's k_reduce_rows_wave with the expression inlined): a wave per row, four rows per block, lane l
+      // takes vector groups l + 64 g, g < NV, all loads issued before the first use; a group past the end of the row re-reads
+      // group 0 and stays out of the combine. Four accumulators (one per vector component), merged pairwise, then the wave tree.
+      o << "extern \"C\" __global__ void __launch_bounds__(256) KNAME(JArgs A) {\n"
+           "  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;\n"
+           "  const long long row = (long long)blockIdx.x * 4 + w;\n"
+           "  if (row >= A.n_out) return;  // (whole waves: no barrier below)\n"
+           "  const long long nv = A.n_red >> 2;\n"
+        << LT.pro() << LT.vec("row", "0", "_r", rowb, "  ") << LT.trig("_r", rowb, "  ");
+      for (int g = 0; g < S.NV; ++g) {
+        const std::string sfx = "_" + std::to_string(g);
+        o << "  const bool ok" << sfx << " = lane + " << 64 * g << " < nv;\n"
+          << "  const long long c" << sfx << " = (ok" << sfx << " ? (long long)(lane + " << 64 * g << ") : 0ll) << 2;\n"
+          << LT.vec("row", "c" + sfx, sfx, vecm, "  ");
+      }
+      o << "  T a[4];\n#pragma unroll\n  for (int j = 0; j < 4; ++j) a[j] = R::template identity<T>();\n";
+      for (int g = 0; g < S.NV; ++g) {
+        const std::string sfx = "_" + std::to_string(g);
+        o << "  if (ok" << sfx << ") {\n" << LT.trig(sfx, vecm, "    ") << combine("a", sfx, "    ") << "  }\n";
+      }
+      o << R"(  T acc = R::combine(R::combine(a[0], a[1]), R::combine(a[2], a[3]));
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) acc = R::combine(acc, jshfl(acc, d));
+  if (lane == 0) ((T *)A.out)[row] = acc;
+}
+)";
+    } else {
+      // long rows: a block per row, 256 lanes stride the row's vector groups with two in flight (as RED_ALL), wave tree, four
+      // partials through LDS, one store
+      o << "extern \"C\" __global__ void __launch_bounds__(256) KNAME(JArgs A) {\n"
+           "  __shared__ T smem[4];\n"
+           "  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;\n"
+           "  const long long row = blockIdx.x, nv = A.n_red >> 2;\n"
+        << LT.pro() << LT.vec("row", "0", "_r", rowb, "  ") << LT.trig("_r", rowb, "  ")
+        << "  T a[2][4];\n#pragma unroll\n  for (int u = 0; u < 2; ++u)\n#pragma unroll\n    for (int j = 0; j < 4; ++j) a[u][j] = R::template identity<T>();\n"
+           "  long long v = threadIdx.x;\n"
+           "  for (; v + 256 < nv; v += 512) {\n"
+        << LT.vec("row", "(v << 2)", "_0", vecm) << LT.vec("row", "((v + 256) << 2)", "_1", vecm)
+        << LT.trig("_0", vecm) << combine("a[0]", "_0", "    ") << LT.trig("_1", vecm) << combine("a[1]", "_1", "    ")
+        << "  }\n  if (v < nv) {\n" << LT.vec("row", "(v << 2)", "_t", vecm) << LT.trig("_t", vecm) << combine("a[0]", "_t", "    ") << "  }\n";
+      o << R"(  T acc = R::combine(R::combine(R::combine(a[0][0], a[1][0]), R::combine(a[0][1], a[1][1])), R::combine(R::combine(a[0][2], a[1][2]), R::combine(a[0][3], a[1][3])));
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) acc = R::combine(acc, jshfl(acc, d));
+  if (lane == 0) smem[w] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) ((T *)A.out)[row] = R::combine(R::combine(smem[0], smem[1]), R::combine(smem[2], smem[3]));
+}
+)";
+    }
   } else if (S.kind == RED_COLS) {
     // tiled: block = 64 column groups x 4 row lanes, rows split over gridDim.y; two rows in flight per lane
     o << "extern \"C\" __global__ void __launch_bounds__(256) KNAME(JArgs A) {\n"
@@ -768,7 +830,7 @@ static std::string gen_source(const Spec &S, const std::string &kname) {
 
 static std::string make_key(const Spec &S) {
   std::ostringstream k;
-  k << S.kind << ':' << (int)S.f32 << (int)S.out_bool << (int)S.nt << (int)S.nt_store << (int)S.store << ':' << S.rop << ':' << S.Q << ':' << S.RU << ':' << S.U << ':' << S.n << ':' << S.axes << (int)S.wide;
+  k << S.kind << ':' << (int)S.f32 << (int)S.out_bool << (int)S.nt << (int)S.nt_store << (int)S.store << ':' << S.rop << ':' << S.Q << ':' << S.RU << ':' << S.U << ':' << S.n << ':' << S.axes << (int)S.wide << ':' << S.NV;
   for (int p = 0; p < S.n; ++p) {
     k << '/';
     for (int i = 0; i < S.pr[p]->n_instr; ++i) k << std::hex << S.pr[p]->ctrl[i] << ',';

@@ -4,8 +4,9 @@ With ``MDHIP_LAZY=1`` (or ``ndarray.set_lazy(True)``) an elementwise backend
 call does not launch: it returns a DeviceArray that carries an expression tree.
 The tree grows while further elementwise calls consume it and is evaluated in
 ONE pass by libmdhip's expression interpreter (``mdhip_vm_eval``) — or folded
-into a reduction (``mdhip_vm_reduce``: full reduce, or the reduce-to-shape
-column sum of the broadcast-gradient path) — when something needs the bytes:
+into a reduction (``mdhip_vm_reduce``: full reduce, the reduce-to-shape
+column sum of the broadcast-gradient path, or a reduction over the trailing
+axes: per-row statistics) — when something needs the bytes:
 a view, a matmul, a gather, an in-place write, a D2H copy. The tape above is
 untouched; it simply sees arrays.
 
