@@ -126,6 +126,11 @@ template <class T> __device__ __forceinline__ T val_at(const ValDesc &v, T s, co
   return ((const T *)v.p)[vo];
 }
 
+// one contribution of np.add.at in the storage type T (every ordered path below adds through this)
+template <class T> __device__ __forceinline__ T elem_add(T acc, T x) {
+  if constexpr (md_same<T, uint8_t>::value) return (uint8_t)(acc || x);   // (bool: np.add on booleans is logical or)
+  else return md_storage_add(acc, x);
+}
 // integer ADD: atomics are exact and order-independent
 template <class T>
 __global__ void __launch_bounds__(MD_BLOCK) k_scatter_add_int(mdhip_index_plan pl, int64_t total, T *dst, ValDesc v, T s) {
@@ -150,12 +155,8 @@ __global__ void k_scatter_serial(mdhip_index_plan pl, int64_t total, T *dst, Val
     bool oob = false;
     const int64_t off = md_plan_offset(pl, i, pos, &oob);
     const T val = val_at<T>(v, s, pl, pos);
-    if constexpr (MODE == MDHIP_SCATTER_ADD) {
-      if constexpr (md_same<T, uint8_t>::value) dst[off] = (uint8_t)(dst[off] || val);
-      else dst[off] = md_storage_add(dst[off], val);
-    } else {
-      dst[off] = val;
-    }
+    if constexpr (MODE == MDHIP_SCATTER_ADD) dst[off] = elem_add<T>(dst[off], val);
+    else dst[off] = val;
   }
 }
 // float ADD at scale, order-preserving without atomics on the payload:
@@ -191,7 +192,7 @@ __global__ void __launch_bounds__(MD_BLOCK) k_apply(mdhip_index_plan pl, const i
       int64_t lin = i;
       for (int d = pl.ndim - 1; d >= 0; --d) { int64_t e = pl.shape[d]; int64_t q = lin / e; pos[d] = lin - q * e; lin = q; }
       const T val = val_at<T>(v, s, pl, pos);
-      if constexpr (MODE == MDHIP_SCATTER_ADD) dst[offs[i]] = md_storage_add(dst[offs[i]], val);
+      if constexpr (MODE == MDHIP_SCATTER_ADD) dst[offs[i]] = elem_add<T>(dst[offs[i]], val);
       else dst[offs[i]] = val;
       done[i] = 1;
     } else {
@@ -569,10 +570,6 @@ template <class T> __device__ __forceinline__ T elem_value(const mdhip_index_pla
     lin = qq;
   }
   return ((const T *)v.p)[vo];
-}
-template <class T> __device__ __forceinline__ T elem_add(T acc, T x) {
-  if constexpr (md_same<T, uint8_t>::value) return (uint8_t)(acc || x);   // (bool: np.add on booleans is logical or)
-  else return md_storage_add(acc, x);
 }
 constexpr int ELEM_SHORT = 64;   // destinations with more contributions than this go to the wave-per-destination kernel
 // One thread per sorted position. SET: the LAST position of a destination writes (no scan). ADD: the FIRST position of a destination
