@@ -639,26 +639,24 @@ __global__ void __launch_bounds__(MD_BLOCK) k_arg_rows_finish(MdRedPlan pl, cons
 
 // Contiguous KEPT axis (argmax over axis 0 of a row-major matrix): a lane owns V adjacent
 // columns and walks the rows (coalesced 16-B loads, four rows in flight); the four waves of a
-// block take rows r, r+1, r+2, r+3 (mod 4) and are merged through LDS; row chunks (gridDim.y)
-// leave (value, index) partials merged by k_arg_cols_finish.
-template <bool IsMax, class T, bool FINAL>
+// block take rows r, r+1, r+2, r+3 (mod 4) and are merged through LDS. For the shapes
+// k_arg_cols_strips does not take; a block walks the whole of its columns (see the launcher).
+template <bool IsMax, class T>
 __global__ void __launch_bounds__(MD_BLOCK) k_arg_cols_vec(const T *__restrict__ x, int64_t n_out, int64_t n_red, int64_t rs,
-                                                          int64_t chunk, T *__restrict__ pval, int64_t *__restrict__ pidx) {
+                                                          int64_t *__restrict__ pidx) {
   constexpr int V = 16 / sizeof(T);
   __shared__ T sv[3][64][V];
   __shared__ int64_t si[3][64][V];
   const int cx = threadIdx.x & 63, ry = threadIdx.x >> 6;
   const int64_t col = ((int64_t)blockIdx.x * 64 + cx) * V;
-  const int64_t s = blockIdx.y, r0 = s * chunk;
-  int64_t r1 = r0 + chunk;
-  if (r1 > n_red) r1 = n_red;
+  const int64_t r1 = n_red;
   T bv[V];
   int64_t bi[V];
 #pragma unroll
   for (int j = 0; j < V; ++j) { bv[j] = T(); bi[j] = INT64_MAX; }
   if (col < n_out) {
     const T *p = x + col;
-    int64_t r = r0 + ry;
+    int64_t r = ry;
     for (; r + 12 < r1; r += 16) {
       MdVec<T, V> t[4];
 #pragma unroll
@@ -693,25 +691,16 @@ __global__ void __launch_bounds__(MD_BLOCK) k_arg_cols_vec(const T *__restrict__
       md_argpair<T> a{bv[j], bi[j]};
 #pragma unroll
       for (int k = 0; k < 3; ++k) a = RArg<IsMax>::combine(a, md_argpair<T>{sv[k][cx][j], si[k][cx][j]});
-      if constexpr (FINAL) pidx[col + j] = a.i;
-      else { pval[s * n_out + col + j] = a.v; pidx[s * n_out + col + j] = a.i; }
+      pidx[col + j] = a.i;
     }
   }
-}
-template <bool IsMax, class T>
-__global__ void __launch_bounds__(MD_BLOCK) k_arg_cols_finish(const T *pval, const int64_t *pidx, int64_t n_out, int64_t splits, int64_t *out) {
-  const int64_t o = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (o >= n_out) return;
-  md_argpair<T> a = RArg<IsMax>::template identity<T>();
-  for (int64_t s = 0; s < splits; ++s) a = RArg<IsMax>::combine(a, md_argpair<T>{pval[s * n_out + o], pidx[s * n_out + o]});
-  out[o] = a.i;
 }
 
 // The same walk as k_reduce_cols_strips for (value, row) pairs: NS strips of 64 lanes x 16 B of columns, NB bands of rows, rows
 // interleaved across bands and the block's four waves (a lane meets its rows in increasing order, so "strictly better" keeps the
 // first of equal values and the first NaN, as np.argmax does), batches of RB rows double-buffered; band partials (value + row)
-// published write-through, merged in band order by the block that arrives last at the strip's ticket. One launch (the chunked
-// kernel above + its finish pass ran at 1.5 TB/s on 8192 x 4096: 128 rows per block, four loads in flight per wave).
+// published write-through, merged in band order by the block that arrives last at the strip's ticket. One launch (its
+// predecessor, a row-chunked form of k_arg_cols_vec with a finish pass, since removed, ran at 1.5 TB/s on 8192 x 4096).
 // Rows are carried as 32-bit (16-byte T) or 64-bit (8-byte T) integers so that a lane's V rows fill one 16-B vector; n_red < 2^31.
 // blockIdx.y, as in k_reduce_cols_strips: one of several independent (n_red x n_out) problems x_bs / o_bs elements apart (a MIDDLE
 // axis reduced), each with its own NB partial rows and its own strip tickets.
@@ -1153,7 +1142,7 @@ struct HipExec {
           (pl.rx[0] % V) == 0 && ((uintptr_t)x->data & 15) == 0 && pl.n_red >= 16) {
         const int64_t n_out = pl.n_out, n_red = pl.n_red;
         const int64_t bxv = ceil_div(n_out, 64 * V);
-        constexpr bool strips_on = true;   // (the chunked kernel + finish pass below: more strips than ticket words, short columns)
+        constexpr bool strips_on = true;   // (k_arg_cols_vec below: more strips than ticket words, short columns)
         if (strips_on && n_red < (1ll << 31) && n_red >= 64 && bxv * MD_TICKET_PAD <= MD_TICKET_WORDS) {
           const int64_t NS = bxv;
           const int arg_blocks = md_opt(MD_OPT_ARG_BLOCKS) > 0 ? (int)md_opt(MD_OPT_ARG_BLOCKS) : MD_NUM_CUS;   // one block per CU, as the column sums (rocprofv3: 26.6 us against 38.0 with four per CU); the knob is for experiments
@@ -1176,27 +1165,13 @@ struct HipExec {
           if (pi) mdhip_free(pi);
           return rc;
         }
-        int64_t splits = 1024 / bxv;
-        if (splits > n_red / 64) splits = n_red / 64;
-        if (splits > 65535) splits = 65535;
-        if (splits < 1) splits = 1;
-        const int64_t chunk = ceil_div(ceil_div(n_red, splits), 16) * 16;
-        splits = ceil_div(n_red, chunk);
-        const T *xp = (const T *)x->data;
-        if (splits == 1) {
-          k_arg_cols_vec<IsMax, T, true><<<dim3((unsigned)bxv, 1), MD_BLOCK, 0, st>>>(xp, n_out, n_red, pl.rx[0], chunk, nullptr, (int64_t *)out->data);
-          return MD_LAUNCH_CHECK("argreduce(cols,vec)");
-        }
-        void *pv = nullptr, *pi = nullptr;
-        MD_TRY(mdhip_alloc((size_t)(splits * n_out) * sizeof(T), &pv));
-        int rc = mdhip_alloc((size_t)(splits * n_out) * sizeof(int64_t), &pi);
-        if (rc != MDHIP_OK) { mdhip_free(pv); return rc; }
-        k_arg_cols_vec<IsMax, T, false><<<dim3((unsigned)bxv, (unsigned)splits), MD_BLOCK, 0, st>>>(xp, n_out, n_red, pl.rx[0], chunk, (T *)pv, (int64_t *)pi);
-        k_arg_cols_finish<IsMax, T><<<(unsigned)ceil_div(n_out, MD_BLOCK), MD_BLOCK, 0, st>>>((const T *)pv, (const int64_t *)pi, n_out, splits, (int64_t *)out->data);
-        rc = MD_LAUNCH_CHECK("argreduce(cols,vec,split)");
-        mdhip_free(pv);
-        mdhip_free(pi);
-        return rc;
+        // What the strips kernel leaves: columns of 16 .. 63 rows, or more than 1024 strips (more than the ticket block serves); a
+        // block per strip walks the whole of its columns. Cutting the rows into chunks (partials + a finish pass, as the row form
+        // below does) was unreachable here: its split count min(1024 / strips, n_red / 64) is 0 -> 1 both ways — n_red < 64 gives
+        // n_red / 64 == 0, more than 1024 strips give 1024 / strips == 0 — and the third way past the strips kernel, n_red >= 2^31
+        // rows of >= 256 columns, does not fit in memory.
+        k_arg_cols_vec<IsMax, T><<<(unsigned)bxv, MD_BLOCK, 0, st>>>((const T *)x->data, n_out, n_red, pl.rx[0], (int64_t *)out->data);
+        return MD_LAUNCH_CHECK("argreduce(cols,vec)");
       }
       // a middle axis reduced: (outer, n_red, inner) with the inner axis contiguous — `outer` column problems in one launch of the strips
       // kernel (the predicate of the batched column sums above); up to here these went to k_arg_block / k_arg_thread, a block or a
