@@ -372,6 +372,19 @@ int mdhip_vm_eval(const mdhip_vm_program *prog, const mdhip_array *out);
  * that are multiples of 4). One launch, no intermediate array, the order of combination
  * fixed by (n_out, n_red) alone. Rows longer than 2048 elements need n_out >= 256 (rows
  * are not split over blocks).
+ * Fourth form, a MIDDLE axis or the leading axes reduced (the gradients of a (B,1,C)
+ * scale and of a (C,) weight on a 3-D activation): the reduced axes are one run of
+ * adjacent axes (extent-1 axes separate nothing), every axis behind the run is kept with
+ * extents that multiply to inner > 1, the axes in front are kept and multiply to
+ * outer >= 1. The program is seen as (outer, n_red, inner); `out` holds outer * inner
+ * dense elements of the compute dtype. Each leaf's strides, from its own descriptor, must
+ * collapse to one stride per group (s_o, s_r, s_i) with s_i 0 or 1; unit-s_i leaves are
+ * 16-byte aligned with s_o and s_r multiples of 4; inner % 4 == 0; outer <= 65535; n_red
+ * is any positive number. That admits dense (B,R,C), (B,1,C), (1,1,C) / (C,), (B,R,1),
+ * (1,R,1), (B,1,1) and one element behind a stride-0 view. outer == 1 is the 2-D column
+ * problem (n_red, inner) and runs its kernels (same bits as the 2-D call); outer > 1 is one
+ * launch with the batch on the grid's second (generated kernels) or third (interpreter)
+ * dimension, the order of combination fixed by (outer, n_red, inner) and the options.
  * Anything else returns MDHIP_EVALUE and the caller materialises first. */
 int mdhip_vm_reduce(const mdhip_vm_program *prog, int reduce_op, const mdhip_array *shape_like,
                     const mdhip_array *out, uint32_t axis_mask);
@@ -384,7 +397,9 @@ int mdhip_vm_reduce(const mdhip_vm_program *prog, int reduce_op, const mdhip_arr
  * reduce (tiled), 3 = column reduce (sweep), 4 = eval + column reduce in one pass,
  * 5 = eval over three / four collapsed axes, with read modes and index width from
  * the program's own leaf descriptors, 6 = row reduce with a wave per row, 7 = row
- * reduce with a block per row; needs no device; on success `log` starts
+ * reduce with a block per row, 8 / 9 = the batched column reduces of a middle axis
+ * (8 strips, 9 tiled) on a 3-D program whose axis 1 is the reduced one, read modes from
+ * its leaf descriptors; needs no device; on success `log` starts
  * with the name the kernel would carry), and counters {kernels compiled, kernels
  * launched}. Generated kernels are named k_fused_<form>_<digest of the program
  * signature>. */

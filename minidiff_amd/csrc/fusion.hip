@@ -19,7 +19,9 @@
 //   k_vm_reduce_all    full reduction of the program's value (grid-strided sweep,
 //                      block partials + finishing block) — fused "...sum()"
 //   k_vm_reduce_cols   2-D program reduced over rows: lane owns 4 columns, rows
-//                      split over gridDim.y — fused reduce-to-shape (bias gradient)
+//                      split over gridDim.y — fused reduce-to-shape (bias gradient);
+//                      batched on gridDim.z: a middle axis of an (outer, n_red, inner)
+//                      program reduced (the gradient of a (B,1,C) scale)
 //   k_vm_reduce_rows   program reduced over its trailing axes: a wave per row, lanes
 //                      stride the row's vector groups — fused per-row statistics
 //                      (softmax denominators, row-wise dots, the gradient of a (R,1) scale)
@@ -38,13 +40,18 @@ constexpr int VG = 1;        // 16-B vector groups per lane per interpreter pass
 constexpr int VW = 4 * VG;   // lanes of the operand stack per thread
 
 // leaf load for VG element groups of the (rows, inner) geometry: VG independent 16-B loads
+struct VmBatch {  // batched column reductions: per leaf, the elements from one batch to the next
+  int64_t bs[MDHIP_VM_MAX_LEAVES];
+};
 template <class T> struct FastLoader {
   const MdVmDev &P;
   int64_t row[VG], c[VG];
-  template <class S> __device__ __forceinline__ void vec(const MdVmLeaf &L, T (&d)[VW]) const {
+  const int64_t *bs = nullptr;  // batched launches only: VmBatch::bs and the block's batch
+  int64_t batch = 0;
+  template <class S> __device__ __forceinline__ void vec(const MdVmLeaf &L, int64_t bo, T (&d)[VW]) const {
     MdVec<S, 4> v[VG];
 #pragma unroll
-    for (int g = 0; g < VG; ++g) v[g] = *reinterpret_cast<const MdVec<S, 4> *>((const S *)L.p + row[g] * L.os + c[g]);
+    for (int g = 0; g < VG; ++g) v[g] = *reinterpret_cast<const MdVec<S, 4> *>((const S *)L.p + bo + row[g] * L.os + c[g]);
 #pragma unroll
     for (int g = 0; g < VG; ++g)
 #pragma unroll
@@ -55,18 +62,19 @@ template <class T> struct FastLoader {
   }
   __device__ __forceinline__ void operator()(int l, T (&d)[VW]) const {
     const MdVmLeaf &L = P.leaf[l];
+    const int64_t bo = bs ? batch * bs[l] : 0;
     if (L.is) {
       switch (L.dtype) {
-        case MDHIP_F32: vec<float>(L, d); break;
-        case MDHIP_F64: vec<double>(L, d); break;
-        case MDHIP_BOOL: vec<uint8_t>(L, d); break;
-        case MDHIP_I32: vec<int32_t>(L, d); break;
-        default: vec<int64_t>(L, d); break;
+        case MDHIP_F32: vec<float>(L, bo, d); break;
+        case MDHIP_F64: vec<double>(L, bo, d); break;
+        case MDHIP_BOOL: vec<uint8_t>(L, bo, d); break;
+        case MDHIP_I32: vec<int32_t>(L, bo, d); break;
+        default: vec<int64_t>(L, bo, d); break;
       }
     } else {
 #pragma unroll
       for (int g = 0; g < VG; ++g) {
-        const T s = md_load<T>(L.p, L.dtype, row[g] * L.os);
+        const T s = md_load<T>(L.p, L.dtype, bo + row[g] * L.os);
 #pragma unroll
         for (int j = 0; j < 4; ++j) d[4 * g + j] = s;
       }
@@ -322,9 +330,12 @@ __global__ void __launch_bounds__(MD_BLOCK) k_vm_reduce_all(MdVmDev P, int64_t r
 
 // 2-D program [n_red rows][n_out cols] reduced over rows; a lane owns 4 columns and
 // takes rows r, r+4, r+8, r+12 per interpreter pass (four 16-B loads per leaf in flight).
-template <class R, class T, bool FINAL>
-__global__ void __launch_bounds__(MD_BLOCK) k_vm_reduce_cols(MdVmDev P, int64_t n_out, int64_t n_red, int64_t chunk, T *dst) {
+// BATCH: gridDim.z independent problems of that shape (a middle axis reduced), unsplit; batch z reads leaf l from B.bs[l] * z on
+// and writes row z of dst.
+template <class R, class T, bool FINAL, bool BATCH = false>
+__global__ void __launch_bounds__(MD_BLOCK) k_vm_reduce_cols(MdVmDev P, int64_t n_out, int64_t n_red, int64_t chunk, T *dst, VmBatch B) {
   MD_VM_PROLOGUE;
+  if constexpr (BATCH) dst += (int64_t)blockIdx.z * n_out;
   __shared__ T smem[3][64][4];
   const int cx = threadIdx.x & 63, ry = threadIdx.x >> 6;
   const int64_t col = ((int64_t)blockIdx.x * 64 + cx) * 4;
@@ -339,6 +350,7 @@ __global__ void __launch_bounds__(MD_BLOCK) k_vm_reduce_cols(MdVmDev P, int64_t 
   const int64_t lcol = col < n_out ? col : (int64_t)blockIdx.x * 256;
   for (int64_t r = r0 + ry; r < r1; r += 4 * VG) {
     FastLoader<T> ld{P, {}, {}};
+    if constexpr (BATCH) { ld.bs = B.bs; ld.batch = blockIdx.z; }
     bool ok[VG];
 #pragma unroll
     for (int g = 0; g < VG; ++g) {
@@ -670,14 +682,18 @@ static bool uncollapse_2d(const MdVmIter &it, int n_leaves, MdVmDev *D, int64_t 
 
 // Strip geometry for a (n_red x n_out) program (the generated SWEEP kernel, fusion_jit.inc): NS strips of 256 columns x NB
 // interleaved row bands, one block per CU, <= 64 bands (the last block of a strip holds its partial rows in registers).
-static bool sweep_geometry(int64_t n_out, int64_t n_red, int ru, int64_t *NS, int64_t *NB) {
+// `outer` > 1: that many such problems in one launch (the batch on blockIdx.y, as reduce.hip's batched strips): the bands come
+// from NS * outer blocks; where the batches' tickets (one per strip and batch) or a batch's partial rows (32-bit buffer offsets
+// in the kernel) do not fit, every batch runs in one band.
+static bool sweep_geometry(int64_t n_out, int64_t n_red, int ru, int64_t *NS, int64_t *NB, int64_t outer = 1) {
   if ((n_out & 3) || n_out < 4 || n_red < 512) return false;
   const int nb_force = (int)md_opt(MD_OPT_SWEEP_NB);
-  const int64_t ns = (n_out + 255) / 256;
-  int64_t nb = nb_force > 0 ? nb_force : (ns >= MD_NUM_CUS ? 1 : MD_NUM_CUS / ns);
+  const int64_t ns = (n_out + 255) / 256, nse = ns * outer;
+  int64_t nb = nb_force > 0 ? nb_force : (nse >= MD_NUM_CUS ? 1 : MD_NUM_CUS / nse);
   if (nb > 64) nb = 64;
   if (nb > n_red / (4 * ru)) nb = n_red / (4 * ru);
   if (nb < 1) nb = 1;
+  if (outer > 1 && nb > 1 && (nse * MD_TICKET_PAD > MD_TICKET_WORDS || nb * n_out * (int64_t)sizeof(double) >= (1ll << 32))) nb = 1;
   if (ns * nb >= (1ll << 31) || (nb > 1 && ns * MD_TICKET_PAD > MD_TICKET_WORDS)) return false;
   *NS = ns;
   *NB = nb;
@@ -686,12 +702,14 @@ static bool sweep_geometry(int64_t n_out, int64_t n_red, int ru, int64_t *NS, in
 
 // reduce over axis 0 of a 2-D program with the generated sweep kernel; `eval_out` != nullptr: the evaluated value
 // is written as well (one pass for an elementwise product and its reduce-to-shape). false: not applicable.
+// `B` != nullptr: `outer` problems of that shape in one launch, leaf l of batch z read from B->bs[l] * z on, row z of `out` written.
 template <class R, class T>
 static bool sweep_cols(const mdhip_vm_program *pr, int rop, const MdVmDev &D, int64_t rows, int64_t inner, void *eval_out,
-                       const mdhip_array *out, int *status) {
-  if (!jit::enabled() || rows * inner < jit::min_elems()) return false;
+                       const mdhip_array *out, int *status, int64_t outer = 1, const VmBatch *B = nullptr) {
+  if (!jit::enabled() || outer * rows * inner < jit::min_elems()) return false;
   jit::Spec S;
   S.kind = jit::SWEEP;
+  S.batch = B != nullptr;
   jit::spec_single(&S, pr);
   jit::spec_modes(&S, D, rows);
   S.rop = rop;
@@ -699,6 +717,7 @@ static bool sweep_cols(const mdhip_vm_program *pr, int rop, const MdVmDev &D, in
   int64_t bytes = eval_out ? rows * inner * (int64_t)sizeof(T) : 0;
   for (int l = 0; l < pr->n_leaves; ++l)
     if (S.leaf_mode[l] == jit::LM_VEC) bytes += rows * inner * (int64_t)md_dtype_size(pr->leaves[l].dtype);
+  bytes *= outer;
   // rows per trip: ~128 B of loads in flight per lane (a bool leaf brings 4 B per row, a float leaf 16)
   int64_t row_bytes = 0;
   for (int l = 0; l < pr->n_leaves; ++l)
@@ -708,7 +727,7 @@ static bool sweep_cols(const mdhip_vm_program *pr, int rop, const MdVmDev &D, in
   if (S.RU > 8) S.RU = 8;
   if (S.RU < 1) S.RU = 1;
   int64_t NS, NB;
-  if (!sweep_geometry(inner, rows, S.RU, &NS, &NB)) return false;
+  if (!sweep_geometry(inner, rows, S.RU, &NS, &NB, outer)) return false;
   S.nt = bytes > ((int64_t)320 << 20);
   // the evaluated value of a one-pass eval + column reduce is a large write next to (often much smaller) reads, and its
   // reader is whatever needed it in memory (cfg4: the weight-gradient GEMM, which is not bandwidth-bound): written around
@@ -719,7 +738,7 @@ static bool sweep_cols(const mdhip_vm_program *pr, int rop, const MdVmDev &D, in
   if (!fn) return false;
   void *partial = nullptr;
   if (NB > 1) {
-    *status = mdhip_alloc((size_t)(NB * inner) * sizeof(T), &partial);
+    *status = mdhip_alloc((size_t)(outer * NB * inner) * sizeof(T), &partial);
     if (*status != MDHIP_OK) return true;
   }
   jit::JArgs A;
@@ -729,15 +748,180 @@ static bool sweep_cols(const mdhip_vm_program *pr, int rop, const MdVmDev &D, in
   A.outs[0] = eval_out;
   A.partial = partial;
   A.tickets = md_tickets();
-  *status = jit::launch(fn, A, dim3((unsigned)(NS * NB)));
+  if (B)
+    for (int l = 0; l < pr->n_leaves; ++l) A.bo[l] = B->bs[l];
+  *status = jit::launch(fn, A, dim3((unsigned)(NS * NB), (unsigned)outer));
   if (partial) mdhip_free(partial);  // stream-ordered
   return true;
+}
+
+// (rows, inner) program reduced over its rows: the generated strips kernel, else the tiled kernels (generated or interpreted)
+// with the rows split over gridDim.y and a second pass over the partial rows
+template <class R, class T>
+static int reduce_cols_2d(const mdhip_vm_program *pr, int rop, MdVmDev &D, int64_t rows, int64_t inner, const mdhip_array *out) {
+  hipStream_t st = md_stream();
+  int status = MDHIP_OK;
+  if (sweep_cols<R, T>(pr, rop, D, rows, inner, nullptr, out, &status)) return status;
+  const int64_t n_out = inner, n_red = rows;
+  const int64_t bx = ceil_div(n_out, 256);
+  int64_t splits = 1024 / bx;
+  if (splits > n_red / 32) splits = n_red / 32;
+  if (splits > 65535) splits = 65535;
+  if (splits < 1) splits = 1;
+  const int64_t chunk = ceil_div(ceil_div(n_red, splits), 16) * 16;
+  splits = ceil_div(n_red, chunk);
+  hipFunction_t fn = nullptr;
+  if (jit::enabled() && rows * inner >= jit::min_elems()) {
+    jit::Spec S;
+    S.kind = jit::RED_COLS;
+    jit::spec_single(&S, pr);
+    jit::spec_modes(&S, D, rows);
+    S.rop = rop;
+    fn = jit::get(S);
+  }
+  jit::JArgs A;
+  if (fn) {
+    jit::fill_args(&A, pr, D);
+    A.rows = rows; A.inner = inner; A.n_out = n_out; A.n_red = n_red; A.chunk = chunk;
+  }
+  if (splits == 1) {
+    if (fn) { A.out = out->data; return jit::launch(fn, A, dim3((unsigned)bx, 1)); }
+    k_vm_reduce_cols<R, T, true><<<dim3((unsigned)bx, 1), MD_BLOCK, 0, st>>>(D, n_out, n_red, chunk, (T *)out->data, VmBatch{});
+    return MD_LAUNCH_CHECK("vm_reduce(cols)");
+  }
+  void *partial = nullptr;
+  MD_TRY(mdhip_alloc((size_t)(splits * n_out) * sizeof(T), &partial));
+  if (fn) {
+    A.out = partial;
+    int rc = jit::launch(fn, A, dim3((unsigned)bx, (unsigned)splits));
+    if (rc != MDHIP_OK) { mdhip_free(partial); return rc; }
+  } else {
+    k_vm_reduce_cols<R, T, false><<<dim3((unsigned)bx, (unsigned)splits), MD_BLOCK, 0, st>>>(D, n_out, n_red, chunk, (T *)partial, VmBatch{});
+  }
+  // second pass: a one-instruction program over the partial buffer
+  MdVmDev F;
+  memset(&F, 0, sizeof F);
+  F.n_instr = 1; F.n_leaves = 1;
+  F.code[0].ctrl = MDHIP_VM_CTRL(MDHIP_VM_PUSH, 0, 0, 0, MDHIP_VM_SRC_LEAF, 0);
+  F.leaf[0].p = partial; F.leaf[0].os = n_out; F.leaf[0].is = 1; F.leaf[0].dtype = md_dtype_of<T>::value;
+  const int64_t chunk2 = ceil_div(splits, 16) * 16;
+  k_vm_reduce_cols<R, T, true><<<dim3((unsigned)bx, 1), MD_BLOCK, 0, st>>>(F, n_out, splits, chunk2, (T *)out->data, VmBatch{});
+  int rc = MD_LAUNCH_CHECK("vm_reduce(cols,split)");
+  mdhip_free(partial);
+  return rc;
+}
+
+// The fourth form of mdhip_vm_reduce — ONE run of adjacent reduced axes with kept axes behind it: the program seen as
+// (outer, n_red, inner), inner > 1. Extent-1 axes separate nothing. false: the mask is another form's (or none).
+struct VmAxisForm {
+  int first, last;  // the run: axes first .. last
+  int64_t outer, n_red, inner;
+};
+static bool axis_form(const mdhip_array *sl, uint32_t mask, VmAxisForm *F) {
+  const int nd = sl->ndim;
+  if (mask == 0 || nd < 2 || (mask >> nd) != 0) return false;
+  int first = 0, last = nd - 1;
+  while (!((mask >> first) & 1u)) ++first;
+  while (!((mask >> last) & 1u)) --last;
+  F->outer = F->n_red = F->inner = 1;
+  for (int d = 0; d < nd; ++d) {
+    const int64_t e = sl->shape[d];
+    if (d < first) F->outer *= e;
+    else if (d > last) F->inner *= e;
+    else if (((mask >> d) & 1u) || e == 1) F->n_red *= e;
+    else return false;  // a kept axis inside the run: two separated runs
+  }
+  F->first = first;
+  F->last = last;
+  return F->inner > 1;
+}
+// one stride for the axes [d0, d1) of a leaf (extent-1 axes skipped; 0 when there is none): false if they do not collapse
+static bool group_stride(const mdhip_array &a, int d0, int d1, int64_t *stride) {
+  int64_t expect = 0;
+  bool have = false;
+  *stride = 0;
+  for (int d = d1 - 1; d >= d0; --d) {
+    const int64_t e = a.shape[d];
+    if (e == 1) continue;
+    if (!have) { *stride = a.strides[d]; expect = a.strides[d] * e; have = true; }
+    else if (a.strides[d] != expect) return false;
+    else expect *= e;
+  }
+  return true;
+}
+
+// The batched column kernels, by size: generated strips (n_red >= 512), generated tiled, interpreter — always ONE launch, unsplit
+// over n_red except for the strips' row bands. D holds the 2-D geometry of one batch (os = the stride over n_red), B the batch strides.
+template <class R, class T>
+static int reduce_axis_batched(const mdhip_vm_program *pr, int rop, MdVmDev &D, const VmBatch &B, int64_t outer, int64_t n_red, int64_t inner,
+                               const mdhip_array *out) {
+  int status = MDHIP_OK;
+  if (sweep_cols<R, T>(pr, rop, D, n_red, inner, nullptr, out, &status, outer, &B)) return status;
+  const int64_t bx = ceil_div(inner, 256);
+  if (jit::enabled() && outer * n_red * inner >= jit::min_elems()) {
+    jit::Spec S;
+    S.kind = jit::RED_COLS;
+    S.batch = true;
+    jit::spec_single(&S, pr);
+    jit::spec_modes(&S, D, n_red);
+    S.rop = rop;
+    if (hipFunction_t fn = jit::get(S)) {
+      jit::JArgs A;
+      jit::fill_args(&A, pr, D);
+      A.rows = n_red; A.inner = inner; A.n_out = inner; A.n_red = n_red; A.chunk = n_red;
+      A.out = out->data;
+      for (int l = 0; l < pr->n_leaves; ++l) A.bo[l] = B.bs[l];
+      return jit::launch(fn, A, dim3((unsigned)bx, (unsigned)outer));
+    }
+  }
+  k_vm_reduce_cols<R, T, true, true><<<dim3((unsigned)bx, 1, (unsigned)outer), MD_BLOCK, 0, md_stream()>>>(D, inner, n_red, n_red, (T *)out->data, B);
+  return MD_LAUNCH_CHECK("vm_reduce(cols,batched)");
+}
+
+template <class R, class T>
+static int reduce_axis(const mdhip_vm_program *pr, int rop, const mdhip_array *shape_like, const mdhip_array *out, const VmAxisForm &F) {
+  if (F.outer * F.n_red * F.inner == 0) return md_fail(MDHIP_EVALUE, "vm_reduce: empty operand");
+  if (F.inner & 3) return md_fail(MDHIP_EVALUE, "vm_reduce: %lld kept elements behind the reduced axes are not whole 16-byte groups", (long long)F.inner);
+  if (F.outer > 65535) return md_fail(MDHIP_EVALUE, "vm_reduce: %lld batches in front of the reduced axes exceed the grid (65535)", (long long)F.outer);
+  if (F.inner >= (1ll << 31) || F.n_red >= (1ll << 31)) return md_fail(MDHIP_EVALUE, "vm_reduce: extents of 2^31 and more are not fused over a middle axis");
+  if (((uintptr_t)out->data & 15) != 0) return md_fail(MDHIP_EVALUE, "vm_reduce: unaligned output");
+  int64_t out_elems = 1;
+  for (int d = 0; d < out->ndim; ++d) out_elems *= out->shape[d];
+  if (out_elems != F.outer * F.inner)
+    return md_fail(MDHIP_EVALUE, "vm_reduce: out holds %lld elements for %lld x %lld kept ones", (long long)out_elems, (long long)F.outer, (long long)F.inner);
+  MdVmDev D;
+  to_dev(pr, &D);
+  VmBatch B;
+  memset(&B, 0, sizeof B);
+  // per leaf (s_o, s_r, s_i) from its OWN descriptor (broadcast to the program's shape already): the jointly collapsed iteration
+  // merges axes across the reduced / kept boundaries when every leaf is dense
+  const int nd = shape_like->ndim;
+  for (int l = 0; l < pr->n_leaves; ++l) {
+    const mdhip_array &a = pr->leaves[l];
+    if (a.is_scalar || a.ndim != nd) return md_fail(MDHIP_EVALUE, "vm_reduce: leaf %d is not broadcast to the program's shape", l);
+    for (int d = 0; d < nd; ++d)
+      if (a.shape[d] != shape_like->shape[d]) return md_fail(MDHIP_EVALUE, "vm_reduce: leaf %d shape mismatch on axis %d", l, d);
+    int64_t so, sr, si;
+    if (!group_stride(a, 0, F.first, &so) || !group_stride(a, F.first, F.last + 1, &sr) || !group_stride(a, F.last + 1, nd, &si))
+      return md_fail(MDHIP_EVALUE, "vm_reduce: leaf %d does not collapse to (outer, reduced, inner) strides", l);
+    if (si != 0 && si != 1) return md_fail(MDHIP_EVALUE, "vm_reduce: leaf %d has inner stride %lld (0 or 1 are fused)", l, (long long)si);
+    if (si == 1 && (!al_for(a.data, a.dtype) || (so & 3) || (sr & 3)))
+      return md_fail(MDHIP_EVALUE, "vm_reduce: leaf %d is not aligned to whole 16-byte groups", l);
+    D.leaf[l].os = sr;
+    D.leaf[l].is = (int32_t)si;
+    B.bs[l] = so;
+  }
+  // leading axes reduced: the 2-D column problem (n_red, inner) itself
+  if (F.outer == 1) return reduce_cols_2d<R, T>(pr, rop, D, F.n_red, F.inner, out);
+  return reduce_axis_batched<R, T>(pr, rop, D, B, F.outer, F.n_red, F.inner, out);
 }
 
 template <class R, class T>
 static int reduce_typed(const mdhip_vm_program *pr, int rop, const mdhip_array *shape_like, const mdhip_array *out, uint32_t mask) {
   const int nd = shape_like->ndim;
   const uint32_t all = nd ? ((1u << nd) - 1u) : 0u;
+  VmAxisForm F;
+  if (!(nd == 2 && mask == 1u) && axis_form(shape_like, mask, &F)) return reduce_axis<R, T>(pr, rop, shape_like, out, F);
   MdVmIter it;
   MD_TRY(md_vm_build_iter(&it, pr, shape_like, nullptr));
   if (it.total == 0) return md_fail(MDHIP_EVALUE, "vm_reduce: empty operand");
@@ -785,57 +969,8 @@ static int reduce_typed(const mdhip_vm_program *pr, int rop, const mdhip_array *
     return rc;
   }
   // reduce over axis 0 of a 2-D program that did NOT collapse to 1-D
-  if (nd == 2 && mask == 1u && uncollapse_2d(it, pr->n_leaves, &D, shape_like->shape[0], shape_like->shape[1], &rows, &inner)) {
-    int status = MDHIP_OK;
-    if (sweep_cols<R, T>(pr, rop, D, rows, inner, nullptr, out, &status)) return status;
-    const int64_t n_out = inner, n_red = rows;
-    const int64_t bx = ceil_div(n_out, 256);
-    int64_t splits = 1024 / bx;
-    if (splits > n_red / 32) splits = n_red / 32;
-    if (splits > 65535) splits = 65535;
-    if (splits < 1) splits = 1;
-    const int64_t chunk = ceil_div(ceil_div(n_red, splits), 16) * 16;
-    splits = ceil_div(n_red, chunk);
-    hipFunction_t fn = nullptr;
-    if (jit::enabled() && it.total >= jit::min_elems()) {
-      jit::Spec S;
-      S.kind = jit::RED_COLS;
-      jit::spec_single(&S, pr);
-      jit::spec_modes(&S, D, rows);
-      S.rop = rop;
-      fn = jit::get(S);
-    }
-    jit::JArgs A;
-    if (fn) {
-      jit::fill_args(&A, pr, D);
-      A.rows = rows; A.inner = inner; A.n_out = n_out; A.n_red = n_red; A.chunk = chunk;
-    }
-    if (splits == 1) {
-      if (fn) { A.out = out->data; return jit::launch(fn, A, dim3((unsigned)bx, 1)); }
-      k_vm_reduce_cols<R, T, true><<<dim3((unsigned)bx, 1), MD_BLOCK, 0, st>>>(D, n_out, n_red, chunk, (T *)out->data);
-      return MD_LAUNCH_CHECK("vm_reduce(cols)");
-    }
-    void *partial = nullptr;
-    MD_TRY(mdhip_alloc((size_t)(splits * n_out) * sizeof(T), &partial));
-    if (fn) {
-      A.out = partial;
-      int rc = jit::launch(fn, A, dim3((unsigned)bx, (unsigned)splits));
-      if (rc != MDHIP_OK) { mdhip_free(partial); return rc; }
-    } else {
-      k_vm_reduce_cols<R, T, false><<<dim3((unsigned)bx, (unsigned)splits), MD_BLOCK, 0, st>>>(D, n_out, n_red, chunk, (T *)partial);
-    }
-    // second pass: a one-instruction program over the partial buffer
-    MdVmDev F;
-    memset(&F, 0, sizeof F);
-    F.n_instr = 1; F.n_leaves = 1;
-    F.code[0].ctrl = MDHIP_VM_CTRL(MDHIP_VM_PUSH, 0, 0, 0, MDHIP_VM_SRC_LEAF, 0);
-    F.leaf[0].p = partial; F.leaf[0].os = n_out; F.leaf[0].is = 1; F.leaf[0].dtype = md_dtype_of<T>::value;
-    const int64_t chunk2 = ceil_div(splits, 16) * 16;
-    k_vm_reduce_cols<R, T, true><<<dim3((unsigned)bx, 1), MD_BLOCK, 0, st>>>(F, n_out, splits, chunk2, (T *)out->data);
-    int rc = MD_LAUNCH_CHECK("vm_reduce(cols,split)");
-    mdhip_free(partial);
-    return rc;
-  }
+  if (nd == 2 && mask == 1u && uncollapse_2d(it, pr->n_leaves, &D, shape_like->shape[0], shape_like->shape[1], &rows, &inner))
+    return reduce_cols_2d<R, T>(pr, rop, D, rows, inner, out);
   // reduce over the TRAILING axes: every axis behind the first reduced one is reduced or has extent 1, some kept axis is longer
   // than 1. The iteration is (n_out, n_red) as it stands, or one axis (all leaves dense or fully broadcast) taken apart again.
   int first = 0;
@@ -881,7 +1016,7 @@ static int reduce_typed(const mdhip_vm_program *pr, int rop, const mdhip_array *
     k_vm_reduce_rows<R, T><<<(unsigned)ceil_div(n_out, MD_BLOCK / 64), MD_BLOCK, 0, st>>>(D, n_out, n_red, (T *)out->data);
     return MD_LAUNCH_CHECK("vm_reduce(rows)");
   }
-  return md_fail(MDHIP_EVALUE, "vm_reduce: only full reductions, axis-0 reductions of 2-D programs and reductions over trailing axes are fused");
+  return md_fail(MDHIP_EVALUE, "vm_reduce: only full reductions and reductions over one run of adjacent axes are fused");
 }
 
 // out_eval[r][c] = program(r, c) and out_red[c] = reduce over r, ONE pass (generated sweep kernel only)
@@ -915,6 +1050,20 @@ static void probe_modes(jit::Spec *S, const mdhip_vm_program *pr) {
     else if (S->kind == jit::SWEEP && a.ndim == 2 && a.strides[0] == 0) S->leaf_mode[slot] = jit::LM_ROWINV;
     else S->leaf_mode[slot] = jit::LM_VEC;
   }
+}
+
+// .. of the batched column reductions (probe kinds 8, 9): a 3-D program whose axis 1 is the reduced one — the modes spec_modes
+// gives the 2-D problem of one batch, from the strides over axes 1 and 2
+static bool probe_modes_axis(jit::Spec *S, const mdhip_vm_program *pr) {
+  for (int l = 0; l < pr->n_leaves; ++l) {
+    const mdhip_array &a = pr->leaves[l];
+    if (a.ndim != 3) return false;
+    const int64_t sr = a.shape[1] == 1 ? 0 : a.strides[1], si = a.shape[2] == 1 ? 0 : a.strides[2];
+    const int slot = S->leaf_map[0][l];
+    if (si) S->leaf_mode[slot] = (S->kind == jit::SWEEP && sr == 0) ? jit::LM_ROWINV : jit::LM_VEC;
+    else S->leaf_mode[slot] = sr == 0 ? jit::LM_CONST : jit::LM_ROWB;
+  }
+  return true;
 }
 
 // .. and the form of an EVAL: the axes form when the leaves, over a dense output of their shape, keep three or four collapsed
@@ -987,13 +1136,15 @@ int mdhip_vm_jit_probe_multi(const mdhip_vm_program *progs, int n, char *log, si
 
 int mdhip_vm_jit_probe(const mdhip_vm_program *pr, int kind, int reduce_op, int out_is_bool, char *log, size_t log_cap) {
   MD_TRY(md_vm_check(pr));
-  if (kind < 0 || kind > 7)
-    return md_fail(MDHIP_EVALUE, "jit probe: kind must be 0 (eval), 1 (reduce all), 2 (reduce columns, tiled), 3 (reduce columns, sweep), 4 (eval + reduce columns), 5 (eval over three / four axes), 6 (reduce rows, a wave per row) or 7 (reduce rows, a block per row)");
+  if (kind < 0 || kind > 9)
+    return md_fail(MDHIP_EVALUE, "jit probe: kind must be 0 (eval), 1 (reduce all), 2 (reduce columns, tiled), 3 (reduce columns, sweep), 4 (eval + reduce columns), 5 (eval over three / four axes), 6 (reduce rows, a wave per row), 7 (reduce rows, a block per row), 8 (reduce a middle axis, batched sweep) or 9 (reduce a middle axis, batched tiled)");
   jit::Spec S;
-  S.kind = kind >= 6 ? jit::RED_ROWS : kind == 5 ? jit::EVAL : kind >= 3 ? jit::SWEEP : kind;
+  S.kind = kind == 9 ? jit::RED_COLS : kind == 8 ? jit::SWEEP : kind >= 6 ? jit::RED_ROWS : kind == 5 ? jit::EVAL : kind >= 3 ? jit::SWEEP : kind;
   S.NV = kind == 6 ? 2 : 0;
+  S.batch = kind >= 8;
   jit::spec_single(&S, pr);
-  probe_modes(&S, pr);
+  if (kind < 8) probe_modes(&S, pr);
+  else if (!probe_modes_axis(&S, pr)) return md_fail(MDHIP_EVALUE, "jit probe: kinds 8 and 9 take a 3-D program (its axis 1 is the reduced one)");
   if (kind == 5) probe_axes(&S, pr, true);
   S.rop = reduce_op;
   S.out_bool = out_is_bool != 0 && (kind == 0 || kind == 5);

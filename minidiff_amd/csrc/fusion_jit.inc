@@ -41,6 +41,7 @@ struct JArgs {
   long long dq, dr;  // divmod(grid stride in vectors, vectors per row): position advance of the streaming forms
   void *partial;     // RED_ALL / SWEEP: block partials, combined by the block that arrives last (md_ticket.h)
   void *tickets;     // .. and its counters
+  long long bo[MDHIP_VM_MAX_LEAVES];  // batched column reductions: per leaf, the elements from one batch (blockIdx.y) to the next
 };
 // the axes form of EVAL (three / four collapsed axes): extents of the two inner outer axes and, per leaf, its three outer strides
 struct JAxArgs : JArgs {
@@ -179,6 +180,7 @@ struct Spec {
   int axes = 0;                     // EVAL: 0 the (rows, inner) form | 3, 4 that many collapsed axes (fusion.hip's axes_geometry)
   bool wide = false;                // EVAL over axes: 64-bit vector index (2^31 vectors and more), else 32-bit
   int NV = 0;                       // RED_ROWS: 1, 2, 4, 8 vector groups per lane, a wave per row | 0 a block per row
+  bool batch = false;               // RED_COLS / SWEEP: `outer` independent (n_red, n_out) problems, the batch on blockIdx.y (a middle axis reduced)
 };
 
 static void spec_single(Spec *S, const mdhip_vm_program *pr) {
@@ -298,7 +300,7 @@ static void gen_prelude(std::ostringstream &o, const Spec &S, const std::string 
   o << R"(
 template <class S, int N> struct alignas(sizeof(S) * N > 16 ? 16 : sizeof(S) * N) JVec { S v[N]; };
 struct JLeaf { const void *p; long long os; int is; int pad; };
-struct JArgs { JLeaf leaf[8]; double imm[48]; void *out; long long rows, inner; long long n_out, n_red, chunk; void *outs[4]; long long dq, dr; void *partial; void *tickets; };
+struct JArgs { JLeaf leaf[8]; double imm[48]; void *out; long long rows, inner; long long n_out, n_red, chunk; void *outs[4]; long long dq, dr; void *partial; void *tickets; long long bo[8]; };
 struct JAxArgs : JArgs { long long e1, e2; long long st[8][3]; };
 template <class S> __device__ __forceinline__ T jcvt(S x) { return (T)x; }
 template <> __device__ __forceinline__ T jcvt<uint8_t>(uint8_t x) { return (T)(x != 0); }
@@ -501,10 +503,10 @@ static std::string kind_tag(const Spec &S) {
       return S.n > 1 ? form + std::to_string(S.n) : (S.out_bool && !S.axes ? "evalb" : form);
     }
     case RED_ALL: return "redall";
-    case RED_COLS: return "redcols";
+    case RED_COLS: return S.batch ? "redcolsb" : "redcols";
     case RED_ROWS: return S.NV ? "redrowsw" + std::to_string(S.NV) : "redrowsb";
   }
-  return S.store ? "evalcols" : "sweepcols";
+  return S.store ? "evalcols" : S.batch ? "sweepb" : "sweepcols";
 }
 
 static std::string gen_source(const Spec &S, const std::string &kname) {
@@ -520,6 +522,16 @@ static std::string gen_source(const Spec &S, const std::string &kname) {
       e << ind << "{ JVec<To, 4> o;\n" << ind << "#pragma unroll\n" << ind << "  for (int j = 0; j < 4; ++j) o.v[j] = md_cast<To>(body" << k << "(A" << LT.args(sfx, "j") << "));\n"
         << ind << "  jst(reinterpret_cast<JVec<To, 4> *>((To *)A.outs[" << k << "] + " << off << "), o); }\n";
     }
+    return e.str();
+  };
+  // batched column reductions (a middle axis reduced: the program seen as (outer, n_red, n_out)): block row blockIdx.y works on
+  // its own (n_red, n_out) problem — every leaf's base and `out` move on by the batch's offset, the rest of the kernel is the 2-D one
+  auto batch_pro = [&]() {
+    std::ostringstream e;
+    e << "  const long long bt = blockIdx.y;\n";
+    for (int l = 0; l < S.n_leaves; ++l)
+      e << "  A.leaf[" << l << "].p = (const " << storage_name(S.leaf_dtype[l]) << " *)A.leaf[" << l << "].p + bt * A.bo[" << l << "];\n";
+    e << "  A.out = (T *)A.out + bt * A.n_out;\n";
     return e.str();
   };
   if (S.kind == EVAL && S.axes) {
@@ -667,12 +679,14 @@ static std::string gen_source(const Spec &S, const std::string &kname) {
     }
   } else if (S.kind == RED_COLS) {
     // tiled: block = 64 column groups x 4 row lanes, rows split over gridDim.y; two rows in flight per lane
+    // (batched: gridDim.y is the batch, rows unsplit — the form below the strips kernel's floor of 512 reduced rows)
     o << "extern \"C\" __global__ void __launch_bounds__(256) KNAME(JArgs A) {\n"
          "  __shared__ T smem[3][64][4];\n"
          "  const int cx = threadIdx.x & 63, ry = threadIdx.x >> 6;\n"
          "  const long long col = ((long long)blockIdx.x * 64 + cx) * 4;\n"
-         "  const long long s = blockIdx.y, r0 = s * A.chunk;\n"
-         "  long long r1 = r0 + A.chunk;\n  if (r1 > A.n_red) r1 = A.n_red;\n"
+      << (S.batch ? "  const long long s = 0, r0 = 0, r1 = A.n_red;  // unsplit: the grid's second dimension is the batch\n" + batch_pro()
+                  : std::string("  const long long s = blockIdx.y, r0 = s * A.chunk;\n"
+                                "  long long r1 = r0 + A.chunk;\n  if (r1 > A.n_red) r1 = A.n_red;\n"))
       << LT.pro() <<
          "  T a[2][4];\n#pragma unroll\n  for (int u = 0; u < 2; ++u)\n#pragma unroll\n    for (int j = 0; j < 4; ++j) a[u][j] = R::template identity<T>();\n"
          "  if (col < A.n_out) {\n    const long long c = col;\n    long long row = r0 + ry;\n    for (; row + 4 < r1; row += 8) {\n"
@@ -716,8 +730,10 @@ static std::string gen_source(const Spec &S, const std::string &kname) {
          "  const bool col_ok = col_raw < A.n_out;\n"
          "  const long long c = col_ok ? col_raw : A.n_out - 4;  // lanes past a ragged edge compute a valid group and store nothing\n"
          "  const long long first = b + (long long)NB * w, step = (long long)NB * 4;\n"
-         "  const long long nrw = first < A.n_red ? (A.n_red - first + step - 1) / step : 0;  // rows of this wave: first + step * i\n"
-      << LT.pro() <<
+         "  const long long nrw = first < A.n_red ? (A.n_red - first + step - 1) / step : 0;  // rows of this wave: first + step * i\n";
+    if (S.batch)  // .. and each batch has its own partial rows and its own ticket per strip
+      o << batch_pro() << "  A.partial = (T *)A.partial + bt * NB * A.n_out;\n  A.tickets = (unsigned *)A.tickets + bt * NS * MD_TICKET_PAD;\n";
+    o << LT.pro() <<
          "  T acc[4];\n#pragma unroll\n  for (int j = 0; j < 4; ++j) acc[j] = R::template identity<T>();\n";
     o << LT.vec("0", "c", "_i", inv, "  ") << LT.trig("_i", inv, "  ");
     const unsigned vecm = 1u << LM_VEC, rowb = 1u << LM_ROWB;
@@ -831,6 +847,7 @@ static std::string gen_source(const Spec &S, const std::string &kname) {
 static std::string make_key(const Spec &S) {
   std::ostringstream k;
   k << S.kind << ':' << (int)S.f32 << (int)S.out_bool << (int)S.nt << (int)S.nt_store << (int)S.store << ':' << S.rop << ':' << S.Q << ':' << S.RU << ':' << S.U << ':' << S.n << ':' << S.axes << (int)S.wide << ':' << S.NV;
+  if (S.batch) k << 'b';
   for (int p = 0; p < S.n; ++p) {
     k << '/';
     for (int i = 0; i < S.pr[p]->n_instr; ++i) k << std::hex << S.pr[p]->ctrl[i] << ',';

@@ -80,7 +80,7 @@ def lazy_enabled() -> bool:
 
 
 # launches issued for pending expressions (tests assert that fusion really happened)
-FUSION_STATS = {"vm_eval": 0, "vm_reduce": 0, "vm_reduce_rows": 0, "vm_eval_multi": 0, "vm_eval_reduce_cols": 0, "deferred_cols": 0, "gemm_deferred": 0, "gemm_epilogue": 0}
+FUSION_STATS = {"vm_eval": 0, "vm_reduce": 0, "vm_reduce_rows": 0, "vm_reduce_axis": 0, "vm_eval_multi": 0, "vm_eval_reduce_cols": 0, "deferred_cols": 0, "gemm_deferred": 0, "gemm_epilogue": 0}
 
 _DTYPE_CODES = {
     np.dtype(np.bool_): _capi.BOOL,
@@ -1744,8 +1744,10 @@ def _staged_reduce(code, a, axes, mask, keepdims, kshape, out_dtype):
 
 def _fused_reduce(code, a, mask, kshape, out_dtype):
     """reduce(pending expression) in one pass: full reductions, the axis-0 reduce-to-shape
-    of a 2-D expression and reductions over trailing axes (per-row statistics: softmax
-    denominators, row-wise dots); None -> caller materialises and reduces."""
+    of a 2-D expression, reductions over trailing axes (per-row statistics: softmax
+    denominators, row-wise dots) and over one run of axes with kept axes behind it (the
+    gradients of a (B,1,C) scale and of a (C,) weight on a 3-D activation); None -> caller
+    materialises and reduces."""
     e = a._expr
     if e.kind == _lz.GEMM:
         return None
@@ -1765,6 +1767,14 @@ def _fused_reduce(code, a, mask, kshape, out_dtype):
         # fused against 0.4 ms; 1,000,000 x 268: 1.7 against 1.0) — one fused evaluation, then the eager column reduction
         return None
     if not (full or cols):
+        if a.shape[-1] != 1 and not (mask >> (nd - 1)) & 1:
+            # the last axis is kept: the axis form or none (one predicate per call: a second one cost the shapes under the floors 1 us)
+            if not _axis_run(a.shape, mask):
+                return None
+            res = DeviceArray.empty(kshape, out_dtype)
+            if not _reduce_pending(e, a.shape, code, mask, res, "vm_reduce_axis"):
+                return None
+            return res
         if not _trailing_rows(a.shape, mask):
             return None
         # the library alone judges the geometry of the leaves (as for mdhip_var in _std_fused): a refusal is today's route
@@ -1817,6 +1827,40 @@ def _trailing_rows(shape, mask) -> py_bool:
 
 
 _ROWS_WAVE_MAX, _ROWS_MIN_OUT = 2048, 256   # fusion.hip: VM_ROWS_WAVE_MAX, VM_ROWS_MIN_OUT
+
+
+def _axis_run(shape, mask) -> py_bool:
+    """The fourth fused form of mdhip_vm_reduce: the reduced axes are ONE run of adjacent axes (extent-1 axes separate nothing)
+    and the kept axes behind it multiply to inner > 1 — the program seen as (outer, n_red, inner). Judged from the shape alone,
+    with the library's limits (whole 16-byte vectors, outer <= 65535) and the floors below which the call is not worth offering
+    (DESIGN.md §4.7); the leaves' geometry is the library's to judge, and a refusal there is today's route."""
+    nd = len(shape)
+    if mask == 0 or nd < 2 or (nd == 2 and mask == 1):
+        return False
+    first, last = 0, nd - 1
+    while not (mask >> first) & 1:
+        first += 1
+    while not (mask >> last) & 1:
+        last -= 1
+    outer = n_red = inner = 1
+    for i, n in enumerate(shape):
+        if i < first:
+            outer *= n
+        elif i > last:
+            inner *= n
+        elif (mask >> i) & 1 or n == 1:
+            n_red *= n
+        else:
+            return False                    # two separated runs: _staged_reduce, whose innermost stage fuses
+    if inner % 4 or inner < _AXIS_MIN_INNER or n_red < _AXIS_MIN_RED or outer > _AXIS_MAX_OUTER:
+        return False
+    if outer == 1 and inner < 512 and n_red >= 65536:
+        return False                        # the 2-D column route's guard against tall problems of few columns (_fused_reduce)
+    return True
+
+
+# the eager batched strips' floors (DESIGN.md §4.3) and the grid's limit on the batch (fusion.hip: reduce_axis)
+_AXIS_MIN_INNER, _AXIS_MIN_RED, _AXIS_MAX_OUTER = 256, 64, 65535
 
 
 def _gemm_epilogue_sum(e, a, kshape, out_dtype):
