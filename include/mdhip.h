@@ -264,7 +264,15 @@ int mdhip_var(const mdhip_array *x, const mdhip_array *out, int32_t axis, int64_
 /* C[b] = A[b] @ B[b]: A (batch.., M, K), B (batch.., K, N), C (batch.., M, N),
  * any strides (NN / NT / TN arrive as strided views: definitions.py:487-492).
  * Arrays are passed 3-D (batch, rows, cols); batch stride 0 broadcasts.
- * f32 and f64 run on MFMA; int32 / int64 take the generic kernel. Storage-only triples: float16 @ float16 -> float16
+ * f32 and f64 run on MFMA; int32 / int64 take the generic kernel.
+ * float32 above the size floors (batch 1, row-major c, 16-B aligned operands with strides a multiple of 4, M a multiple of 256 and
+ * >= 512, N of 128, K of 32, N and K >= 4096) is NOT the fp32 fma chain: every operand element is split exactly into three bfloat16
+ * planes, the six plane products a1b1, a1b2, a2b1, a1b3, a2b2, a3b1 run on the bf16 matrix cores and are accumulated in float32
+ * (gemm_bf16x3.hip): a fresh accumulator per 32 k, the k-tiles' sums added round-to-nearest (the matrix instruction's own accumulation
+ * truncates). The three dropped products are below 2^-23 |a||b| per term; the measured error against float64 is under the fma chain's,
+ * on mixed-sign and on same-sign operands (profiles/gemm_bf16x3_after.txt).
+ * Operands holding an inf or a NaN get the fma chain's result. Option gemm_bf16x3 = 0 (mdhip_debug_set_option, or
+ * MDHIP_GEMM_BF16X3 under MDHIP_EXPERIMENTS=1) restores the fma chain everywhere. Storage-only triples: float16 @ float16 -> float16
  * (float32 accumulation, one rounding) and int8 @ int8 -> int8, uint8 @ uint8 -> uint8 (the low byte of the exact sum) run
  * on the low-precision MFMA (gemm_narrow.hip). Two triples keep the accumulator instead (np.matmul's dtype=): float16 @ float16 ->
  * float32 and int8 @ int8 -> int32 (c has the wide dtype; the same kernels, stored without the final conversion). No other
@@ -276,7 +284,8 @@ int mdhip_matmul(const mdhip_array *a, const mdhip_array *b, const mdhip_array *
  *     mask_out = (a @ b + bias > 0)                                  (M x N numpy.bool_, C-contiguous)
  * in ONE pass: the pre-activation is never written; the mask is what the backward pass needs of it
  * (reference call pattern: minidiff/ops/definitions.py:487-492 matmul, :424-427 add, :468-471 greater,
- * :555-559 where, :403-407 sum). Shapes that are not whole aligned tiles return MDHIP_EVALUE and the caller
+ * :555-559 where, :403-407 sum). Shapes that are not whole aligned tiles, and shapes whose plain product runs as six bf16
+ * products (above: the mask must be the plain product's, bit for bit), return MDHIP_EVALUE and the caller
  * runs the plain product followed by the fused tail. Deterministic (per-block partials summed in order). */
 int mdhip_matmul_bias_relu_sum(const mdhip_array *a, const mdhip_array *b, const mdhip_array *bias,
                                const mdhip_array *mask_out, const mdhip_array *sum_out);

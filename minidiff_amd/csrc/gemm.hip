@@ -84,6 +84,9 @@ struct GemmArgs {
   // C is addressed with unit stride along ROWS (a swapped "TT" product, HipExec::gemm) and everything is 16-B aligned: the direct-to-LDS
   // NN kernel stores the four consecutive rows a lane holds of one column as one vector
   int c_vec_rows;
+  // non-null: the launch is the fp32 stand-in behind a bf16x3 product (plan_bf16x3) and runs only when the split passes set the word
+  // (an operand holds an inf or a NaN); every block returns at once otherwise — one uniform load and branch at kernel entry
+  const unsigned *run_if_set;
 };
 
 // Tile loaders for a ROWS x BK operand tile, NT threads, 16 B per thread per pass.
@@ -256,6 +259,7 @@ __global__ void __launch_bounds__(64 * WM * WN, (EPI != 0 && BM * BN <= 256 * 12
   constexpr int WTM = BM / (32 * WM), WTN = BN / (32 * WN);  // MFMA tiles per wave along m / n
   __shared__ float As[2][BK][BM + LDP];
   __shared__ float Bs[2][BK][BN + LDP];
+  if (g.run_if_set && *g.run_if_set == 0) return;
 
   // XCD-aware tile order: ids b, b+8, b+16.. share an XCD -> give them neighbours
   const int nblk = g.tiles_m * g.tiles_n;
@@ -518,6 +522,7 @@ __global__ void __launch_bounds__(64 * WM * WN) k_gemm_f32_tn_glds(GemmArgs g) {
   __shared__ __attribute__((aligned(16))) float B1[BK][BN];
   __shared__ __attribute__((aligned(16))) float A2[NBUF == 3 ? BK : 1][BM];
   __shared__ __attribute__((aligned(16))) float B2[NBUF == 3 ? BK : 1][BN];
+  if (g.run_if_set && *g.run_if_set == 0) return;
 
   const int nblk = g.tiles_m * g.tiles_n;
   int bid = blockIdx.x;
@@ -743,6 +748,7 @@ __global__ void __launch_bounds__(64 * WM * WN) k_gemm_f32_kc_glds(GemmArgs g) {
   __shared__ __attribute__((aligned(16))) float B1[BN * BK];
   __shared__ __attribute__((aligned(16))) float A2[NBUF == 3 ? BM * BK : 4];
   __shared__ __attribute__((aligned(16))) float B2[NBUF == 3 ? BN * BK : 4];
+  if (g.run_if_set && *g.run_if_set == 0) return;
 
   const int nblk = g.tiles_m * g.tiles_n;
   int bid = blockIdx.x;
@@ -1454,7 +1460,8 @@ static bool dma_priced(const GemmArgs &ga, bool a_kc, bool b_kc, bool aligned) {
 }
 // ---- the plan --------------------------------------------------------------------------------------------------------------------------
 enum { ST_REG, ST_DMA, ST_DMA_SELECT, ST_DMA_PRED };   // staging; the ragged DMA forms are the kernels' RAGGED = 1 (select) / 2 (predicated)
-enum { S_LONGK, S_SKINNY, S_REPACK, S_F32, S_SUM, S_F64, S_GENERIC, S_NMFMA, S_NGENERIC, S_NCONV };   // S_N*: float16 / int8 / uint8 operands
+enum { S_LONGK, S_SKINNY, S_REPACK, S_F32, S_SUM, S_F64, S_GENERIC, S_NMFMA, S_NGENERIC, S_NCONV,   // S_N*: float16 / int8 / uint8 operands
+       S_BX_CLEAR, S_BX_SPLIT_ROWS, S_BX_SPLIT_COLS, S_BX_GEMM };   // float32 on the bf16 matrix cores (gemm_bf16x3.hip): flag word, split passes, product
 struct GemmStep {   // only the steps in use are initialised (GemmPlan::add)
   int kind, dtype, cfg, staging, nbuf, splits, epi, skip;   // cfg: kTiles row (S_F64: 0 64x64, 1 128x128, 2 TN direct to LDS); skip: hand-off
   int dtype_to;                                             // S_NCONV: the destination's dtype
@@ -1466,6 +1473,9 @@ struct GemmStep {   // only the steps in use are initialised (GemmPlan::add)
   GemmArgs64 ga64;
   MdGemm g;    // hand-offs, S_GENERIC, S_N*: the product; S_REPACK: a -> c, rows x cols = M x N, a_ms / c_ms row strides; S_SUM: K partials at a;
                // S_NCONV: a (dtype) -> c (dtype_to), batch x M x N with strides a_bs / a_ms / a_ks and c_bs / c_ms / c_ns
+               // S_BX_*: b = the flag word; CLEAR: nothing else; SPLIT_*: a (M rows x K, a_ms the row / k-row stride) -> planes at c;
+               // GEMM: planes at a, planes at b_planes, C at c with c_ms
+  const void *b_planes;
   const char *what;
 };
 struct GemmPlan {
@@ -1625,8 +1635,68 @@ template <class GA> static void md_gemm_args(GA &ga, const MdGemm &g) {   // the
   ga.a_bs = g.a_bs; ga.a_ms = g.a_ms; ga.a_ks = g.a_ks; ga.b_bs = g.b_bs; ga.b_ks = g.b_ks; ga.b_ns = g.b_ns; ga.c_bs = g.c_bs; ga.c_ms = g.c_ms; ga.c_ns = g.c_ns;
 }
 static void plan_generic(GemmPlan &p, const MdGemm &g, int dtype) { GemmStep &s = p.add(S_GENERIC, "matmul(generic)"); s.g = g; s.dtype = dtype; }
-// f32 past the hand-offs and the k ranges: TT swap, repack, peel, MFMA; the generic kernel for what the MFMA kernels do not take
-static void plan_f32(GemmPlan &p, const MdGemm &g_in) {
+// ---- float32 on the bf16 matrix cores (gemm_bf16x3.hip) ---------------------------------------------------------------------------
+// Which products run as six bf16 products of pre-split planes (option gemm_bf16x3: 0 never | 1 above the floors | 2 every shape the
+// kernels take whose fp32 plan is plain launches, see plan_bf16x3). Structure: batch 1, row-major C with unit column stride, both operands 16-B aligned with a unit stride along k or
+// along their rows and the other stride a multiple of four, whole 256 x 128 x 32 tiles. The decision depends on M only through
+// M >= 512 and divisibility (as plan_kranges' both-sides-at-most-2048 rule): a 512- or 1024-row panel of a product takes the route of
+// the whole product, so panelled and un-panelled gradients stay bit-identical (every output element's bits are the same in both).
+// Floors: the split passes stream 10 bytes per operand element and the 256 x 128 tiles must fill the chip; read off the option 0 / 2 sweep
+// in profiles/gemm_bf16x3_after.txt so that no product with M >= 2048 loses (the 512- and 1024-row panels of such a product do).
+constexpr int64_t kBx3FloorN = 4096, kBx3FloorK = 4096;
+static bool bf16x3_takes(const MdGemm &g) {
+  const int64_t mode = md_opt(MD_OPT_GEMM_BF16X3);
+  if (mode == 0 || g.batch != 1 || g.c_ns != 1 || g.c_ms < g.N) return false;
+  if (g.M < 256 || g.N < 128 || g.K < 32 || (g.M % 256) || (g.N % 128) || (g.K % 32)) return false;
+  if (g.M > (1ll << 20) || g.N > (1ll << 20) || g.K > (1ll << 20)) return false;   // (grid extents, 32-bit lane offsets)
+  auto side = [](const void *q, int64_t rows, int64_t K, int64_t rs, int64_t ks) {
+    if ((uintptr_t)q & 15) return false;
+    if (ks == 1) return rs >= K && rs % 4 == 0;
+    return rs == 1 && ks >= rows && ks % 4 == 0;
+  };
+  if (!side(g.a, g.M, g.K, g.a_ms, g.a_ks) || !side(g.b, g.N, g.K, g.b_ns, g.b_ks)) return false;
+  return mode == 2 || (g.M >= 512 && g.N >= kBx3FloorN && g.K >= kBx3FloorK);
+}
+static void plan_f32(GemmPlan &p, const MdGemm &g_in, bool top = true);
+// flag word = 0, split A, split B, the product, and behind it the fp32 plan of the same product with run_if_set: when a split pass
+// met an inf or a NaN the product kernel returns at once and the fp32 kernels run (the fma chain's inf / NaN pattern, no host
+// synchronisation); with finite operands the fp32 launches return at once. false: the fp32 plan is more than plain launches — a
+// split-K launch with its sum, a k-range batch, a repack: steps with temporaries of their own that cannot be switched by the flag —
+// and the product stays fp32. Such plans arise only from few 64 x 64 tiles under a long k (pick_cfg: < 256 tiles, K >= 1024) or
+// misaligned operands, i.e. never above option 1's floors (M >= 512 and N >= 4096 are >= 512 such tiles, bf16x3_takes wants aligned
+// operands, whole 256 x 128 tiles leave nothing to peel but 128-column strips the skinny hand-off declines); under option 2 a
+// small shape may stay fp32 for this reason (tests/test_gemm_bf16x3.py pins both).
+static bool plan_bf16x3(GemmPlan &p, const MdGemm &g) {
+  GemmPlan q;
+  plan_f32(q, g, false);
+  if (q.ntmp || p.n + q.n + 4 > GemmPlan::kMaxSteps) return false;
+  for (int i = 0; i < q.n; ++i) {
+    const GemmStep &s = q.step[i];
+    // (a hand-off in front of a peeled strip declines every strip of >= 128 rows and columns: md_gemm_skinny)
+    if (!(s.kind == S_F32 && s.splits == 1 && !s.epi) && s.kind != S_SKINNY) return false;
+  }
+  const size_t a_bytes = (size_t)(3 * g.M * g.K) * 2, b_bytes = (size_t)(3 * g.N * g.K) * 2;
+  char *buf = (char *)p.temp(256 + a_bytes + b_bytes);
+  char *ap = buf + 256, *bp = ap + a_bytes;
+  p.add(S_BX_CLEAR, "matmul(bf16x3 flag)").g.b = buf;
+  auto split = [&](const void *src, int64_t rows, int64_t rs, int64_t ks, void *dst) {
+    MdGemm &x = p.add(ks == 1 ? S_BX_SPLIT_ROWS : S_BX_SPLIT_COLS, "matmul(bf16x3 split)").g;
+    x.a = src; x.b = buf; x.c = dst; x.M = rows; x.K = g.K; x.a_ms = ks == 1 ? rs : ks;
+  };
+  split(g.a, g.M, g.a_ms, g.a_ks, ap);
+  split(g.b, g.N, g.b_ns, g.b_ks, bp);
+  GemmStep &m = p.add(S_BX_GEMM, "matmul(f32 as bf16x3)");
+  m.g = g; m.g.a = ap; m.g.b = buf; m.b_planes = bp;
+  for (int i = 0; i < q.n; ++i) {
+    GemmStep &s = p.step[p.n++] = q.step[i];
+    if (s.kind == S_F32) s.ga.run_if_set = (const unsigned *)buf;
+  }
+  return true;
+}
+// f32 past the hand-offs and the k ranges: bf16x3 (top: not for the sub-products of the k ranges), TT swap, repack, peel, MFMA; the
+// generic kernel for what the MFMA kernels do not take
+static void plan_f32(GemmPlan &p, const MdGemm &g_in, bool top) {
+  if (top && bf16x3_takes(g_in) && plan_bf16x3(p, g_in)) return;
   MdGemm g = g_in;
   bool c_rows_unit = false;
   // "TT" (A^T B^T of two row-major arrays: A unit-stride along m, B along k) has no kernel of its own: C^T = B'A' is the NN
@@ -1670,7 +1740,7 @@ static void plan_f32(GemmPlan &p, const MdGemm &g_in) {
 // step along k, c_bs from partial to partial), a second product takes the remainder, the partials are added in range order. The
 // sub-products go to plan_f32: no hand-off can take them (t64 >= 256 with both sides <= 2048 puts both over 448: not long-k's <= 128,
 // not skinny's <= 8), nor the k ranges again (a batch of >= 2 ranges, a remainder k < 128).
-static bool plan_kranges(GemmPlan &p, const MdGemm &g) {
+static bool kranges_shape(const MdGemm &g, int64_t *splits_out, int64_t *k_chunk_out) {
   const int64_t t128 = ((g.M + 127) / 128) * ((g.N + 127) / 128), t64 = ((g.M + 63) / 64) * ((g.N + 63) / 64);
   // (both sides at most 2048: the row panels dp.GradSync cuts a wide weight gradient into — 512 x 4096 — keep the plain product's
   // summation order, so panelled and un-panelled gradients stay bit-identical)
@@ -1678,19 +1748,26 @@ static bool plan_kranges(GemmPlan &p, const MdGemm &g) {
       g.K < 2 * (g.M > g.N ? g.M : g.N))
     return false;
   const int64_t splits = std::min<int64_t>(MD_NUM_CUS / t128, 4);
-  const int64_t k_chunk = g.K / splits / 32 * 32, k_rem = g.K - splits * k_chunk;
+  const int64_t k_chunk = g.K / splits / 32 * 32;
   if (splits < 2 || k_chunk < 1024) return false;
+  *splits_out = splits; *k_chunk_out = k_chunk;
+  return true;
+}
+static bool plan_kranges(GemmPlan &p, const MdGemm &g) {
+  int64_t splits, k_chunk;
+  if (!kranges_shape(g, &splits, &k_chunk)) return false;
+  const int64_t k_rem = g.K - splits * k_chunk;
   const int64_t parts = splits + (k_rem > 0 ? 1 : 0);
   float *partial = (float *)p.temp((size_t)(parts * g.M * g.N) * sizeof(float));
   MdGemm g2 = g;
   g2.batch = splits; g2.K = k_chunk; g2.a_bs = k_chunk * g.a_ks; g2.b_bs = k_chunk * g.b_ks;
   g2.c = partial; g2.c_bs = g.M * g.N; g2.c_ms = g.N; g2.c_ns = 1;
-  plan_f32(p, g2);
+  plan_f32(p, g2, false);
   if (k_rem > 0) {
     MdGemm g3 = g2;
     g3.batch = 1; g3.K = k_rem;
     g3.a = (const float *)g.a + splits * k_chunk * g.a_ks; g3.b = (const float *)g.b + splits * k_chunk * g.b_ks; g3.c = partial + splits * g.M * g.N;
-    plan_f32(p, g3);
+    plan_f32(p, g3, false);
   }
   plan_sum(p, partial, parts, 1, g.M, g.N, g.c, g.c_bs, g.c_ms, g.c_ns, "matmul(f32, k ranges as a batch)");
   return true;
@@ -1909,7 +1986,7 @@ static int run_step(const GemmStep &s, const void *const *tmp, int *skip) {
     }
     case S_F32: {
       GemmArgs ga = s.ga;
-      ga.A = at(ga.A); ga.B = at(ga.B); ga.C = at(ga.C); ga.partial = at(ga.partial);
+      ga.A = at(ga.A); ga.B = at(ga.B); ga.C = at(ga.C); ga.partial = at(ga.partial); ga.run_if_set = at(ga.run_if_set);
       if (s.epi) ga.tickets = md_tickets();
       const GemmKernel k = f32_kernel(s);
       if (!k) return md_fail(MDHIP_ERUNTIME, "matmul: no kernel for the planned launch (cfg %d)", s.cfg);
@@ -1937,6 +2014,11 @@ static int run_step(const GemmStep &s, const void *const *tmp, int *skip) {
       if (s.edge && !zero) return md_fail(MDHIP_EMEMORY, "matmul: zero block");
       return s.wide ? md_gemm_widen_mfma(g, s.dtype, s.a_kc, s.b_kc, s.edge, zero) : md_gemm_narrow_mfma(g, s.dtype, s.a_kc, s.b_kc, s.edge, zero);
     }
+    case S_BX_CLEAR: return md_hip_check(hipMemsetAsync(const_cast<void *>(g.b), 0, 4, md_stream()), s.what);
+    case S_BX_SPLIT_ROWS:
+    case S_BX_SPLIT_COLS:   // launched plainly, as the repack: attached events wait for the product
+      return md_gemm_bf16x3_split((const float *)g.a, s.kind == S_BX_SPLIT_ROWS, g.M, g.K, g.a_ms, g.c, (unsigned *)const_cast<void *>(g.b));
+    case S_BX_GEMM: return md_gemm_bf16x3(g.a, at(s.b_planes), (float *)g.c, g.M, g.N, g.K, g.c_ms, (const unsigned *)g.b);
     case S_NGENERIC: return s.wide ? md_gemm_widen_generic(g, s.dtype) : md_gemm_narrow_generic(g, s.dtype);
     case S_NCONV: {
       mdhip_array sd{}, dd{};
@@ -1998,6 +2080,15 @@ struct HipExec {
 // mdhip_matmul_bias_relu_sum: the plain product's tile choice (and summation order: a mask recomputed from `a @ b + bias` agrees bit
 // for bit), restricted to tiles that divide the problem; the fused DMA kernel takes whole k-tiles only. false: not covered.
 static bool plan_epi(GemmPlan &p, GemmArgs ga) {
+  {  // a shape whose plain product runs as bf16x3 (past the hand-offs, which take no such shape, and the k ranges) is not covered: the
+     // caller's plain product and fused tail keep product and mask bit-identical; an epilogue form of that kernel is not built
+    MdGemm g{1, ga.M, ga.N, ga.K, ga.A, ga.B, ga.C, 0, ga.a_ms, ga.a_ks, 0, ga.b_ks, ga.b_ns, 0, ga.c_ms, ga.c_ns};
+    int64_t splits, k_chunk;
+    if (!kranges_shape(g, &splits, &k_chunk) && bf16x3_takes(g)) {
+      GemmPlan q;
+      if (plan_bf16x3(q, g)) return false;
+    }
+  }
   const bool priced = dma_priced(ga, true, false, true) && ga.K % 32 == 0;
   const int cfg = pick_cfg(ga.M, ga.N, ga.K, 1, false, priced);
   auto divides = [&](Tile t) { return t.bm && ga.M % t.bm == 0 && ga.N % t.bn == 0; };

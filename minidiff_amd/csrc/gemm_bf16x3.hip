@@ -1,0 +1,261 @@
+// gemm_bf16x3.hip — a float32 product as six bfloat16 products of pre-split planes, accumulated in float32.
+//
+// Every float32 operand element splits EXACTLY into three bfloat16 planes x = p1 + p2 + p3 (md_bf16x3.h). Of the nine plane products
+// the six with i + j <= 4 are formed on v_mfma_f32_32x32x16_bf16 — a1b1, a1b2, a2b1, a1b3, a2b2, a3b1, in that order, into ONE float32
+// accumulator per output element and k-tile (bx_mma: the k-tiles' sums are added with VALU adds); the three dropped ones are below 2^-23 |a||b|. The plane products themselves are exact (8 x 8
+// significand bits), so integer operands whose sums stay below 2^24 and products with an identity come out exact.
+// Planned by gemm.hip (plan_bf16x3): split A, split B, the product, and behind it the fp32 kernel that runs instead when a split saw
+// an inf or a NaN (the flag word).
+//
+// Split pass (one per operand, streaming): reads the float32 operand once, writes three row-major [rows][K] bfloat16 planes, the k
+// axis contiguous whatever the operand's layout — k_bf16x3_split_rows for an operand whose k axis is contiguous, k_bf16x3_split_cols
+// (64 rows x 32 k patches transposed through LDS) for one that is contiguous along its rows (A of TN, B of NN, both of TT). 16-B
+// loads and stores. A block that saw a non-finite element ORs 1 into the flag word (an ordinary vector atomic).
+//
+// Product kernel k_gemm_bf16x3: block tile 256 x 128, eight waves 4 x 2 (wave tile 64 x 64 = 2 x 2 MFMA tiles), k-tile 32 = 64-B
+// rows: six plane tiles (3 x 256 + 3 x 128 rows) = 72 KiB per k-tile, two buffers = 144 KiB of the 160 KiB LDS, one block per CU and
+// two waves per SIMD. Each plane tile is staged ONCE per k-tile (global_load_lds_dwordx4: scalar base + 32-bit lane offset, a 1-KiB
+// piece = 16 rows per wave instruction, nine pieces per wave and k-tile) and serves all its products: per k16 step a wave reads 12
+// fragments (3 planes x 2 row blocks of A and of B, one ds_read_b128 each) for 24 MFMAs. No VALU work in the k16 steps; 64 adds per wave fold a k-tile's sum into the running sum.
+// LDS image (as gemm_narrow.hip's KC image, for 64-B rows): [row][64 B], 16-B chunk c of row r in slot c ^ ((r >> 2) & 3), swizzled
+// through the per-lane SOURCE address; the 16 lanes of a read group hit 16 distinct bank slots.
+// The buffers are separate __shared__ objects and the k loop is unrolled by two, as in gemm_narrow.hip. Whole tiles only. The k order
+// and the product order are fixed: an output element's bits do not depend on M, N or where its tile lies. No float atomics.
+#include "md_hip.h"
+#include "md_bf16x3.h"
+
+namespace {
+
+typedef __attribute__((address_space(3))) void bx_lds_void;
+typedef __attribute__((address_space(1))) const void bx_gbl_void;
+typedef __bf16 bx_bf16x8 __attribute__((ext_vector_type(8)));
+typedef int bx_i32x4 __attribute__((ext_vector_type(4)));
+typedef float bx_f32x4 __attribute__((ext_vector_type(4)));
+typedef float bx_f32x16 __attribute__((ext_vector_type(16)));
+
+constexpr int BX_BM = 256, BX_BN = 128, BX_BK = 32;   // block tile; BX_BK bfloat16 = 64 B per row and k-tile
+constexpr int BX_NT = 512;                            // threads (eight waves)
+constexpr int BX_ROWB = BX_BK * 2;                    // bytes of a row in the LDS image
+
+// ---- split pass ------------------------------------------------------------------------------------------------------------------
+// eight consecutive k of one row -> 16 B of each plane
+__device__ __forceinline__ bool bx_split8(const float (&x)[8], bx_i32x4 *q1, bx_i32x4 *q2, bx_i32x4 *q3) {
+  bool bad = false;
+  uint32_t h[3][8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    uint32_t p1, p2, p3;
+    bad |= md_bf16x3_split(x[j], &p1, &p2, &p3);
+    h[0][j] = p1 >> 16; h[1][j] = p2 >> 16; h[2][j] = p3 >> 16;
+  }
+  bx_i32x4 *q[3] = {q1, q2, q3};
+#pragma unroll
+  for (int p = 0; p < 3; ++p)
+#pragma unroll
+    for (int w = 0; w < 4; ++w) (*q[p])[w] = (int)(h[p][2 * w] | (h[p][2 * w + 1] << 16));
+  return bad;
+}
+
+// src: rows x K float32, k unit-stride, `rs` floats between rows. dst: three planes of rows x K bfloat16, `plane` BYTES apart.
+__global__ void __launch_bounds__(256) k_bf16x3_split_rows(const float *__restrict__ src, int64_t rows, int64_t K, int64_t rs, char *__restrict__ dst,
+                                                           int64_t plane, unsigned *flag) {
+  bool bad = false;
+  const int64_t k = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 8;
+  if (k < K) {
+    for (int64_t r = blockIdx.y; r < rows; r += gridDim.y) {
+      const bx_f32x4 lo = *(const bx_f32x4 *)(src + r * rs + k), hi = *(const bx_f32x4 *)(src + r * rs + k + 4);
+      const float x[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+      bx_i32x4 q1, q2, q3;
+      bad |= bx_split8(x, &q1, &q2, &q3);
+      char *d = dst + (r * K + k) * 2;
+      *(bx_i32x4 *)d = q1; *(bx_i32x4 *)(d + plane) = q2; *(bx_i32x4 *)(d + 2 * plane) = q3;
+    }
+  }
+  if (__syncthreads_or(bad) && threadIdx.x == 0) atomicOr(flag, 1u);
+}
+
+// src: K x rows float32, the rows unit-stride, `ks` floats between k-rows. One block: 64 rows x 32 k.
+__global__ void __launch_bounds__(256) k_bf16x3_split_cols(const float *__restrict__ src, int64_t rows, int64_t K, int64_t ks, char *__restrict__ dst,
+                                                           int64_t plane, unsigned *flag) {
+  __shared__ float T[32][66];   // [k][row]; 66: the transposed reads below hit 64 distinct banks
+  const int t = threadIdx.x;
+  for (int64_t kb = blockIdx.y; kb < K / 32; kb += gridDim.y) {
+    const int64_t r0 = (int64_t)blockIdx.x * 64, k0 = kb * 32;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int idx = t + 256 * i, kk = idx >> 4, r4 = (idx & 15) * 4;
+      const bx_f32x4 v = *(const bx_f32x4 *)(src + (k0 + kk) * ks + r0 + r4);
+      T[kk][r4] = v[0]; T[kk][r4 + 1] = v[1]; T[kk][r4 + 2] = v[2]; T[kk][r4 + 3] = v[3];
+    }
+    __syncthreads();
+    const int kg = t & 3, r = t >> 2;
+    float x[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) x[j] = T[kg * 8 + j][r];
+    bx_i32x4 q1, q2, q3;
+    const bool bad = bx_split8(x, &q1, &q2, &q3);
+    char *d = dst + ((r0 + r) * K + k0 + kg * 8) * 2;
+    *(bx_i32x4 *)d = q1; *(bx_i32x4 *)(d + plane) = q2; *(bx_i32x4 *)(d + 2 * plane) = q3;
+    if (__syncthreads_or(bad) && t == 0) atomicOr(flag, 1u);   // (also: every lane is done with T)
+  }
+}
+
+// ---- product ---------------------------------------------------------------------------------------------------------------------
+struct Bx3Args {
+  const char *A, *B;        // plane 1 of each operand; planes 2 and 3 follow a_plane / b_plane BYTES apart; rows of K bfloat16
+  float *C;
+  int64_t K, c_ms;          // c_ms in floats
+  int64_t a_plane, b_plane;
+  int tiles_m, tiles_n;
+  const unsigned *flag;     // the split passes' verdict: a non-zero word = nothing to do here (the fp32 kernel behind runs instead)
+};
+
+__device__ __forceinline__ const char *bx_uniform(const char *p) {
+  uint32_t lo = (uint32_t)(uintptr_t)p, hi = (uint32_t)((uintptr_t)p >> 32);
+  asm("" : "+s"(lo), "+s"(hi));
+  return reinterpret_cast<const char *>(((uintptr_t)hi << 32) | lo);
+}
+
+// One 1-KiB piece (16 rows x 64 B) of a plane tile: lane l lands in LDS at piece + 16 l = row l >> 2, slot l & 3, so it fetches chunk
+// (l & 3) ^ ((row >> 2) & 3) of its row (the tile row is 16 piece + (l >> 2): (row >> 2) & 3 = (l >> 4) & 3).
+__device__ __forceinline__ void bx_piece(const char *P, int64_t rs, int64_t row, int64_t k0, uint32_t lane_off, char *S) {
+  uint32_t off = lane_off;
+  asm("" : "+v"(off) : "s"((int)k0));
+  const char *src = bx_uniform(P + row * rs + k0 * 2) + off;
+  __builtin_amdgcn_global_load_lds((bx_gbl_void *)src, (bx_lds_void *)S, 16, 0, 0);
+}
+
+struct Bx3Bufs { char *a[3], *b[3]; };
+
+__device__ __forceinline__ void bx_stage(const Bx3Args &g, int64_t m0, int64_t n0, int kt, const Bx3Bufs &S, uint32_t lane_off) {
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int64_t rs = g.K * 2, k0 = (int64_t)kt * BX_BK;
+#pragma unroll
+  for (int p = 0; p < 3; ++p) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) bx_piece(g.A + p * g.a_plane, rs, m0 + 16 * (wave + 8 * i), k0, lane_off, S.a[p] + (wave + 8 * i) * 1024);
+    bx_piece(g.B + p * g.b_plane, rs, n0 + 16 * wave, k0, lane_off, S.b[p] + wave * 1024);
+  }
+}
+
+// the MFMA operand of lane l for k16 step s (0, 1) and the 32 rows from rb: row rb + (l & 31), k 16 s + 8 (l >> 5) ..
+__device__ __forceinline__ bx_bf16x8 bx_frag(const char *S, int rb, int s) {
+  const int l = threadIdx.x & 63, r = rb + (l & 31), c = 2 * s + (l >> 5);
+  return __builtin_bit_cast(bx_bf16x8, *(const bx_i32x4 *)(S + r * BX_ROWB + ((c ^ ((r >> 2) & 3)) << 4)));
+}
+
+// One k-tile. The matrix instruction's float32 accumulation TRUNCATES (measured: all-positive operands came out low by 2e-9 K of their
+// value with one accumulator over all of K), so the k-tile's 12 accumulations per element start from zero in a fresh accumulator and
+// the k-tile's sum is folded into the running sum with VALU adds (round to nearest), outside the k16 steps: the bias is that of 12
+// truncations whatever K is. The chunk is the k-tile, so the bits of an element still depend on k alone.
+__device__ __forceinline__ void bx_mma(const Bx3Bufs &S, int wm, int wn, bx_f32x16 (&acc)[2][2]) {
+  bx_f32x16 part[2][2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) part[i][j][e] = 0;
+#pragma unroll
+  for (int s = 0; s < 2; ++s) {
+    bx_bf16x8 a[3][2], b[3][2];
+#pragma unroll
+    for (int p = 0; p < 3; ++p)
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        a[p][i] = bx_frag(S.a[p], wm * 64 + i * 32, s);
+        b[p][i] = bx_frag(S.b[p], wn * 64 + i * 32, s);
+      }
+    // a1b1, a1b2, a2b1, a1b3, a2b2, a3b1 — each over the four sub-tiles, so that consecutive MFMAs write different accumulators
+    constexpr int PA[6] = {0, 0, 1, 0, 1, 2}, PB[6] = {0, 1, 0, 2, 1, 0};
+#pragma unroll
+    for (int q = 0; q < 6; ++q)
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) part[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[PA[q]][i], b[PB[q]][j], part[i][j], 0, 0, 0);
+  }
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) acc[i][j] += part[i][j];
+}
+
+__global__ void __launch_bounds__(BX_NT) k_gemm_bf16x3(Bx3Args g) {
+  __shared__ __attribute__((aligned(16))) char sA00[BX_BM * BX_ROWB];
+  __shared__ __attribute__((aligned(16))) char sA01[BX_BM * BX_ROWB];
+  __shared__ __attribute__((aligned(16))) char sA02[BX_BM * BX_ROWB];
+  __shared__ __attribute__((aligned(16))) char sB00[BX_BN * BX_ROWB];
+  __shared__ __attribute__((aligned(16))) char sB01[BX_BN * BX_ROWB];
+  __shared__ __attribute__((aligned(16))) char sB02[BX_BN * BX_ROWB];
+  __shared__ __attribute__((aligned(16))) char sA10[BX_BM * BX_ROWB];
+  __shared__ __attribute__((aligned(16))) char sA11[BX_BM * BX_ROWB];
+  __shared__ __attribute__((aligned(16))) char sA12[BX_BM * BX_ROWB];
+  __shared__ __attribute__((aligned(16))) char sB10[BX_BN * BX_ROWB];
+  __shared__ __attribute__((aligned(16))) char sB11[BX_BN * BX_ROWB];
+  __shared__ __attribute__((aligned(16))) char sB12[BX_BN * BX_ROWB];
+  if (g.flag && *g.flag != 0) return;   // (uniform: one scalar load and branch)
+  const Bx3Bufs S0{{sA00, sA01, sA02}, {sB00, sB01, sB02}}, S1{{sA10, sA11, sA12}, {sB10, sB11, sB12}};
+  // XCD-aware order, as gemm_narrow.hip: the blocks that share an XCD take a contiguous band of output tiles
+  const int nwg = g.tiles_m * g.tiles_n, bid = blockIdx.x, xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
+  const int wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
+  const int64_t m0 = (int64_t)(wg / g.tiles_n) * BX_BM, n0 = (int64_t)(wg % g.tiles_n) * BX_BN;
+  const int wave = threadIdx.x >> 6, wm = wave >> 1, wn = wave & 1, l = threadIdx.x & 63;
+  const int nk = (int)(g.K / BX_BK);
+  const uint32_t lane_off = (uint32_t)((l >> 2) * (g.K * 2) + (((l & 3) ^ ((l >> 4) & 3)) << 4));
+  bx_f32x16 acc[2][2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0;
+  bx_stage(g, m0, n0, 0, S0, lane_off);
+  for (int kt = 0; kt < nk; kt += 2) {
+    __syncthreads();   // tile kt is in buffer 0 (the barrier's vmcnt(0) retires the DMAs); every wave is done with buffer 1
+    if (kt + 1 < nk) bx_stage(g, m0, n0, kt + 1, S1, lane_off);
+    bx_mma(S0, wm, wn, acc);
+    if (kt + 1 >= nk) break;
+    __syncthreads();
+    if (kt + 2 < nk) bx_stage(g, m0, n0, kt + 2, S0, lane_off);
+    bx_mma(S1, wm, wn, acc);
+  }
+  // accumulator element e of lane l: row (e & 3) + 8 (e >> 2) + 4 (l >> 5), column l & 31 of the 32 x 32 tile; one wave store writes
+  // 32 consecutive floats of two rows (whole 128-B lines), as k_gemm_widen_mfma
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const int64_t m = m0 + wm * 64 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * (l >> 5), n = n0 + wn * 64 + j * 32 + (l & 31);
+        g.C[m * g.c_ms + n] = acc[i][j][e];
+      }
+}
+
+}  // namespace
+
+// gemm.hip's plan steps: see md_hip.h
+int md_gemm_bf16x3_split(const float *src, bool k_contig, int64_t rows, int64_t K, int64_t stride, void *planes, unsigned *flag) {
+  const int64_t plane = rows * K * 2;
+  if (k_contig) {
+    const dim3 grid((unsigned)((K / 8 + 255) / 256), (unsigned)(rows < 65535 ? rows : 65535));
+    k_bf16x3_split_rows<<<grid, 256, 0, md_stream()>>>(src, rows, K, stride, (char *)planes, plane, flag);
+  } else {
+    const dim3 grid((unsigned)(rows / 64), (unsigned)(K / 32 < 65535 ? K / 32 : 65535));
+    k_bf16x3_split_cols<<<grid, 256, 0, md_stream()>>>(src, rows, K, stride, (char *)planes, plane, flag);
+  }
+  return MD_LAUNCH_CHECK("matmul(bf16x3 split)");
+}
+
+int md_gemm_bf16x3(const void *a_planes, const void *b_planes, float *c, int64_t M, int64_t N, int64_t K, int64_t c_ms, const unsigned *flag) {
+  Bx3Args a{};
+  a.A = (const char *)a_planes; a.B = (const char *)b_planes; a.C = c;
+  a.K = K; a.c_ms = c_ms;
+  a.a_plane = M * K * 2; a.b_plane = N * K * 2;
+  a.tiles_m = (int)(M / BX_BM); a.tiles_n = (int)(N / BX_BN);
+  a.flag = flag;
+  md_opt_table()[MD_OPT_GEMM_BF16X3_RUNS] += 1;
+  MD_LAUNCH(k_gemm_bf16x3, dim3((unsigned)(a.tiles_m * a.tiles_n)), BX_NT, a);
+  return MD_LAUNCH_CHECK("matmul(f32 as bf16x3)");
+}

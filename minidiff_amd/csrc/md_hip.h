@@ -19,6 +19,11 @@ int md_gemm_narrow_generic(const MdGemm &g, int dtype);
 // the same with the accumulators stored as they are: float16 operands -> float32 c, int8 -> int32 (`dtype`: the operands')
 int md_gemm_widen_mfma(const MdGemm &g, int dtype, bool a_kc, bool b_kc, bool edge, const void *zero);
 int md_gemm_widen_generic(const MdGemm &g, int dtype);
+// gemm_bf16x3.hip: float32 products on the bf16 matrix cores, planned by gemm.hip (plan_bf16x3). split: a rows x K operand (k_contig:
+// `stride` floats between rows, else between k-rows) -> three rows x K bfloat16 planes at `planes`, ORs 1 into *flag on an inf / NaN;
+// the product: C (M x N, c_ms floats between rows) from the planes, nothing when *flag != 0
+int md_gemm_bf16x3_split(const float *src, bool k_contig, int64_t rows, int64_t K, int64_t stride, void *planes, unsigned *flag);
+int md_gemm_bf16x3(const void *a_planes, const void *b_planes, float *c, int64_t M, int64_t N, int64_t K, int64_t c_ms, const unsigned *flag);
 unsigned *md_tickets();                                   // MD_TICKET_WORDS zeroed counters (md_ticket.h)
 bool md_capturing();                                      // a stream capture is recording (mdhip_graph_begin .. _end)
 int *md_sticky();                                         // host-mapped word a CAPTURED gather / scatter sets on an out-of-bounds index

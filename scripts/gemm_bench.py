@@ -20,6 +20,8 @@ if os.environ.get("GEMM_PEEL_AB"):   # every config twice: single ragged launch 
     CFGS = {(99 if k == -1 else k) + 10000 * g: v + (" peel" if g else " one launch") for k, v in CFGS.items() for g in (0, 1)}
 if os.environ.get("GEMM_GLDS_AB"):   # every config twice: register staging / direct-to-LDS staging (option gemm_glds)
     CFGS = {(99 if k == -1 else k) + 100 * g: v + (" +glds" if g else "") for k, v in CFGS.items() for g in (0, 1)}   # (99 = auto)
+if os.environ.get("GEMM_BF16X3_AB"):   # every config twice: fp32 fma chain / six bf16 products of pre-split planes on every eligible shape (option gemm_bf16x3)
+    CFGS = {(99 if k == -1 else k) + 100000 * g: v + (" bf16x3" if g else " fp32") for k, v in CFGS.items() for g in (0, 1)}
 
 
 REPS = int(os.environ.get("GEMM_REPS", "5"))   # launches per timing (small shapes: more, the gaps between 5 short launches weigh)
@@ -40,7 +42,7 @@ def main():
         B = nd.asarray(rng.standard_normal((K, N), dtype=np.float32))
         At = nd.asarray(np.ascontiguousarray(A.get().T))
         Bt = nd.asarray(np.ascontiguousarray(B.get().T))
-        ref = None
+        ref = {}   # per bf16x3 arm: the arms differ by their own rounding (each a few 1e-6 from float64 at K = 8192)
         res = {}
         rounds = int(os.environ.get("GEMM_ROUNDS", "5"))
         for _ in range(6):          # pre-roll: the first milliseconds after an idle gap run at ramping clocks (the med 126 / max 150
@@ -51,6 +53,8 @@ def main():
                     opt("gemm_nbuf", 2 + (cfg // 1000) % 10)
                 if os.environ.get("GEMM_PEEL_AB"):
                     opt("gemm_peel", (cfg // 10000) % 10)
+                if os.environ.get("GEMM_BF16X3_AB"):
+                    opt("gemm_bf16x3", 2 * ((cfg // 100000) % 10))
                 if cfg % 100 == 99 or cfg == -1:
                     opt("gemm_cfg", -1)      # the library's own choice
                 else:
@@ -70,13 +74,13 @@ def main():
                     res.setdefault((cfg, tag), []).append(tf)
                     if rnd == 0:
                         h = out.get()
-                        if ref is None:
-                            ref = h
-                        assert np.abs(h - ref).max() / np.abs(ref).max() < 5e-6, (cfg, tag)
+                        arm = (cfg // 100000) % 10 if os.environ.get("GEMM_BF16X3_AB") else 0
+                        r = ref.setdefault(arm, h)
+                        assert np.abs(h - r).max() / np.abs(r).max() < 5e-6, (cfg, tag)
         print(f"M={M} K={K} N={N}")
         for cfg, name in CFGS.items():
             print("   %-22s " % name + "  ".join("%s med %6.1f min %6.1f max %6.1f TF" % (t, sorted(res[(cfg, t)])[len(res[(cfg, t)]) // 2], min(res[(cfg, t)]), max(res[(cfg, t)])) for t in (("NN", "NT", "TN", "TT") if os.environ.get("GEMM_TT") else ("NN", "NT", "TN"))))
-    opt("gemm_cfg", -1); opt("gemm_glds", 1); opt("gemm_nbuf", 0); opt("gemm_peel", 1)
+    opt("gemm_cfg", -1); opt("gemm_glds", 1); opt("gemm_nbuf", 0); opt("gemm_peel", 1); opt("gemm_bf16x3", 1)
 
 
 if __name__ == "__main__":
