@@ -309,8 +309,12 @@ MD_UFLOAT(UCosh, md_cosh)
 MD_UFLOAT(UTanh, md_tanh)
 MD_UFLOAT(UExp, md_exp)
 MD_UFLOAT(ULog, md_log)
-MD_UFLOAT(USqrt, md_sqrt)
 #undef MD_UFLOAT
+// a NaN operand is handed on as it is: the refinement steps behind the device's correctly rounded sqrt give a NaN either sign, and
+// which one differed from one kernel instance to the next (float16 stream kernel: 0xfe00, every other path and NumPy: 0x7e00)
+struct USqrt {
+  template <class T> static MD_HD T apply(T x) { return x != x ? x : md_sqrt(x); }
+};
 // power with a host-scalar exponent is dispatched to these (same values as BPow's shortcuts)
 struct USquare {
   template <class T> static MD_HD T apply(T x) { return x * x; }
