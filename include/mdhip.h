@@ -364,9 +364,15 @@ typedef struct mdhip_vm_program {
   int32_t n_instr, n_leaves, compute_dtype, _pad;
   uint32_t ctrl[MDHIP_VM_MAX_INSTR];
   double imm[MDHIP_VM_MAX_INSTR];
-  mdhip_array leaves[MDHIP_VM_MAX_LEAVES]; /* each broadcast to out's shape (stride 0 on broadcast axes) */
+  mdhip_array leaves[MDHIP_VM_MAX_LEAVES]; /* each broadcast to out's shape (stride 0 on broadcast axes); ANY of the twelve
+                                            * dtypes: a leaf is read in its own storage type and converted to compute_dtype
+                                            * on load (NumPy's cast of an operand to the loop dtype). The vector kernels
+                                            * read four elements per lane: unit-stride leaves aligned to min(16, 4 * element
+                                            * size) bytes, else the one-element kernel runs. */
 } mdhip_vm_program;
-/* out[...] = program(...)  (out dtype: compute_dtype, or BOOL for a 0/1 result) */
+/* out[...] = program(...)  (out dtype: compute_dtype; BOOL for a 0/1 result; or FLOAT16 — the value rounded ONCE to nearest
+ * even from float32 and from float64 alike, stored in the same pass. The other evaluating entry points — mdhip_vm_eval_multi,
+ * mdhip_vm_eval_reduce_cols — store the compute dtype only and return MDHIP_EVALUE for a FLOAT16 out.) */
 int mdhip_vm_eval(const mdhip_vm_program *prog, const mdhip_array *out);
 /* out = reduce(program) with reduce_op in {SUM, PROD, MAX, MIN}. `shape` is the
  * program's shape (leaves are broadcast to it); supported forms: all axes reduced;
@@ -408,7 +414,7 @@ int mdhip_vm_reduce(const mdhip_vm_program *prog, int reduce_op, const mdhip_arr
  * the program's own leaf descriptors, 6 = row reduce with a wave per row, 7 = row
  * reduce with a block per row, 8 / 9 = the batched column reduces of a middle axis
  * (8 strips, 9 tiled) on a 3-D program whose axis 1 is the reduced one, read modes from
- * its leaf descriptors; needs no device; on success `log` starts
+ * its leaf descriptors; out_is_bool: 1 a BOOL out, 2 a FLOAT16 out (kinds 0 and 5); needs no device; on success `log` starts
  * with the name the kernel would carry), and counters {kernels compiled, kernels
  * launched}. Generated kernels are named k_fused_<form>_<digest of the program
  * signature>. */

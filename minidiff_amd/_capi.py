@@ -22,7 +22,8 @@ UID_BYTES = 128
 
 # dtype codes (mdhip.h)
 BOOL, I32, I64, F32, F64 = range(5)
-I8, I16, U8, U16, U32, U64, F16 = range(5, 12)   # storage-only dtypes (include/mdhip.h): elementwise, reductions, F16 / I8 / U8 matmul, (F16, F16, F32) / (I8, I8, I32) matmul
+I8, I16, U8, U16, U32, U64, F16 = range(5, 12)   # storage-only dtypes (include/mdhip.h): elementwise, reductions, F16 / I8 / U8 matmul, (F16, F16, F32) / (I8, I8, I32) matmul;
+#                                                  leaves of fused float32 / float64 programs (mdhip_vm_*: read in their own type, converted on load) and, F16, the `out` of mdhip_vm_eval
 
 # op codes — keep in the order of the enums in mdhip.h
 U_COPY, U_ABS, U_NEG, U_SIGN, U_CEIL, U_FLOOR, U_SIN, U_COS, U_TAN, U_SINH, U_COSH, U_TANH, \

@@ -39,7 +39,36 @@ namespace {
 constexpr int VG = 1;        // 16-B vector groups per lane per interpreter pass (large arrays take the compiled path)
 constexpr int VW = 4 * VG;   // lanes of the operand stack per thread
 
-// leaf load for VG element groups of the (rows, inner) geometry: VG independent 16-B loads
+// A leaf is read in its OWN storage type and converted to the program's float type on load (NumPy's cast of an operand to the
+// loop dtype; md_load's conversions): four elements per lane and group whatever the type — an 8-byte load for the 2-byte types,
+// 4-byte for the 1-byte ones, 16-byte for the 4-byte ones, two 16-byte loads for the 8-byte ones.
+struct u8v { uint8_t v; };   // a uint8 VALUE (plain uint8_t is bool storage here: it loads as x != 0)
+template <class T, class S> __device__ __forceinline__ T vm_cvt(S x) {
+  if constexpr (md_same<S, uint8_t>::value) return (T)(x != 0);
+  else if constexpr (md_same<S, u8v>::value) return (T)x.v;
+  else if constexpr (md_same<S, f16>::value) return md_cast<T>(x);   // exact: every binary16 value is a float
+  else return (T)x;
+}
+// every storage type by name, the five compute dtypes first; NO default that reads: with a narrower leaf a widening default
+// would run past the array. (An unknown code never gets here — md_vm_check refuses it — and would load nothing.)
+#define MD_VM_LEAF_SWITCH(dt, V, NONE) \
+  switch (dt) {                        \
+    case MDHIP_F32: V(float); break;   \
+    case MDHIP_F64: V(double); break;  \
+    case MDHIP_BOOL: V(uint8_t); break; \
+    case MDHIP_I32: V(int32_t); break; \
+    case MDHIP_I64: V(int64_t); break; \
+    case MDHIP_F16: V(f16); break;     \
+    case MDHIP_I8: V(int8_t); break;   \
+    case MDHIP_U8: V(u8v); break;      \
+    case MDHIP_I16: V(int16_t); break; \
+    case MDHIP_U16: V(uint16_t); break; \
+    case MDHIP_U32: V(uint32_t); break; \
+    case MDHIP_U64: V(uint64_t); break; \
+    default: NONE; break;              \
+  }
+
+// leaf load for VG element groups of the (rows, inner) geometry: VG independent vector loads
 struct VmBatch {  // batched column reductions: per leaf, the elements from one batch to the next
   int64_t bs[MDHIP_VM_MAX_LEAVES];
 };
@@ -55,22 +84,19 @@ template <class T> struct FastLoader {
 #pragma unroll
     for (int g = 0; g < VG; ++g)
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        if constexpr (md_same<S, uint8_t>::value) d[4 * g + j] = (T)(v[g].v[j] != 0);
-        else d[4 * g + j] = (T)v[g].v[j];
-      }
+      for (int j = 0; j < 4; ++j) d[4 * g + j] = vm_cvt<T, S>(v[g].v[j]);
+  }
+  __device__ __forceinline__ void none(T (&d)[VW]) const {
+#pragma unroll
+    for (int j = 0; j < VW; ++j) d[j] = (T)0;
   }
   __device__ __forceinline__ void operator()(int l, T (&d)[VW]) const {
     const MdVmLeaf &L = P.leaf[l];
     const int64_t bo = bs ? batch * bs[l] : 0;
     if (L.is) {
-      switch (L.dtype) {
-        case MDHIP_F32: vec<float>(L, bo, d); break;
-        case MDHIP_F64: vec<double>(L, bo, d); break;
-        case MDHIP_BOOL: vec<uint8_t>(L, bo, d); break;
-        case MDHIP_I32: vec<int32_t>(L, bo, d); break;
-        default: vec<int64_t>(L, bo, d); break;
-      }
+#define MD_VM_V(S) vec<S>(L, bo, d)
+      MD_VM_LEAF_SWITCH(L.dtype, MD_VM_V, none(d))
+#undef MD_VM_V
     } else {
 #pragma unroll
       for (int g = 0; g < VG; ++g) {
@@ -185,22 +211,19 @@ template <class T> struct AxesLoader {
   template <class S> __device__ __forceinline__ void vec(const MdVmLeaf &L, int64_t off, T (&d)[4]) const {
     const MdVec<S, 4> v = *reinterpret_cast<const MdVec<S, 4> *>((const S *)L.p + off + c);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      if constexpr (md_same<S, uint8_t>::value) d[j] = (T)(v.v[j] != 0);
-      else d[j] = (T)v.v[j];
-    }
+    for (int j = 0; j < 4; ++j) d[j] = vm_cvt<T, S>(v.v[j]);
+  }
+  __device__ __forceinline__ void none(T (&d)[4]) const {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) d[j] = (T)0;
   }
   __device__ __forceinline__ void operator()(int l, T (&d)[4]) const {
     const MdVmLeaf &L = P.leaf[l];
     const int64_t off = r0 * A.st[l][0] + r1 * A.st[l][1] + r2 * A.st[l][2];
     if (L.is) {
-      switch (L.dtype) {
-        case MDHIP_F32: vec<float>(L, off, d); break;
-        case MDHIP_F64: vec<double>(L, off, d); break;
-        case MDHIP_BOOL: vec<uint8_t>(L, off, d); break;
-        case MDHIP_I32: vec<int32_t>(L, off, d); break;
-        default: vec<int64_t>(L, off, d); break;
-      }
+#define MD_VM_V(S) vec<S>(L, off, d)
+      MD_VM_LEAF_SWITCH(L.dtype, MD_VM_V, none(d))
+#undef MD_VM_V
     } else {
       const T s = md_load<T>(L.p, L.dtype, off);
 #pragma unroll
@@ -507,7 +530,8 @@ static bool axes_geometry(const MdVmIter &it, const mdhip_vm_program *pr, const 
   return true;
 }
 
-template <class T> static int eval_typed(const mdhip_vm_program *pr, const mdhip_array *out) {
+// To: the compute type, b8 (truth values) or f16 (the chain's value rounded ONCE to binary16 in the same pass: astype(chain, float16))
+template <class T, class To> static int eval_typed(const mdhip_vm_program *pr, const mdhip_array *out) {
   MdVmIter it;
   MD_TRY(md_vm_build_iter(&it, pr, out, out));
   if (it.total == 0) return MDHIP_OK;
@@ -515,7 +539,7 @@ template <class T> static int eval_typed(const mdhip_vm_program *pr, const mdhip
   to_dev(pr, &D);
   hipStream_t st = md_stream();
   int64_t rows, inner;
-  const bool to_bool = out->dtype == MDHIP_BOOL;
+  constexpr bool to_bool = md_same<To, b8>::value, to_f16 = md_same<To, f16>::value;
   if (fast_geometry(it, pr->n_leaves, pr, true, &D, &rows, &inner) && al_for(out->data, out->dtype)) {
     if (jit::enabled() && it.total >= jit::min_elems()) {
       // the streamed bytes of this launch: output + distinct vector leaves
@@ -527,6 +551,7 @@ template <class T> static int eval_typed(const mdhip_vm_program *pr, const mdhip
       jit::spec_single(&S, pr);
       jit::spec_modes(&S, D, rows);
       S.out_bool = to_bool;
+      S.out_f16 = to_f16;
       S.nt = bytes > ((int64_t)320 << 20);
       jit::eval_shape(&S);
       if (hipFunction_t fn = jit::get(S)) {
@@ -538,8 +563,7 @@ template <class T> static int eval_typed(const mdhip_vm_program *pr, const mdhip
       }
     }
     const int64_t work = (rows * (inner >> 2) + VG - 1) / VG + (rows == 1 ? 4 : 0);
-    if (to_bool) k_vm_eval_fast<T, b8><<<md_grid_for(work), MD_BLOCK, 0, st>>>(D, (b8 *)out->data, rows, inner);
-    else k_vm_eval_fast<T, T><<<md_grid_for(work), MD_BLOCK, 0, st>>>(D, (T *)out->data, rows, inner);
+    k_vm_eval_fast<T, To><<<md_grid_for(work), MD_BLOCK, 0, st>>>(D, (To *)out->data, rows, inner);
     return MD_LAUNCH_CHECK("vm_eval(fast)");
   }
   VmAxes A;
@@ -549,18 +573,17 @@ template <class T> static int eval_typed(const mdhip_vm_program *pr, const mdhip
       S.kind = jit::EVAL;
       jit::spec_single(&S, pr);
       S.out_bool = to_bool;
+      S.out_f16 = to_f16;
       jit::spec_axes(&S, D, A, (int64_t)md_dtype_size(out->dtype));
       if (hipFunction_t fn = jit::get(S)) {
         void *outs[1] = {out->data};
         return jit::launch_axes(fn, S, D, A, pr->imm, outs);
       }
     }
-    if (to_bool) k_vm_eval_axes<T, b8><<<md_grid_for(it.total >> 2), MD_BLOCK, 0, st>>>(D, A, (b8 *)out->data);
-    else k_vm_eval_axes<T, T><<<md_grid_for(it.total >> 2), MD_BLOCK, 0, st>>>(D, A, (T *)out->data);
+    k_vm_eval_axes<T, To><<<md_grid_for(it.total >> 2), MD_BLOCK, 0, st>>>(D, A, (To *)out->data);
     return MD_LAUNCH_CHECK("vm_eval(axes)");
   }
-  if (to_bool) k_vm_eval_generic<T, b8><<<md_grid_for(it.total), MD_BLOCK, 0, st>>>(D, it, (b8 *)out->data);
-  else k_vm_eval_generic<T, T><<<md_grid_for(it.total), MD_BLOCK, 0, st>>>(D, it, (T *)out->data);
+  k_vm_eval_generic<T, To><<<md_grid_for(it.total), MD_BLOCK, 0, st>>>(D, it, (To *)out->data);
   return MD_LAUNCH_CHECK("vm_eval(generic)");
 }
 
@@ -1092,16 +1115,19 @@ extern "C" {
 
 int mdhip_vm_eval(const mdhip_vm_program *pr, const mdhip_array *out) {
   MD_TRY(md_vm_check(pr));
-  MD_TRY(md_check_array(out, "vm out"));
-  if (out->dtype != pr->compute_dtype && out->dtype != MDHIP_BOOL)
-    return md_fail(MDHIP_ETYPE, "vm_eval: out dtype must be the compute dtype or bool");
-  return pr->compute_dtype == MDHIP_F32 ? eval_typed<float>(pr, out) : eval_typed<double>(pr, out);
+  MD_TRY(md_check_any_array(out, "vm out"));
+  const bool f32 = pr->compute_dtype == MDHIP_F32;
+  if (out->dtype == MDHIP_BOOL) return f32 ? eval_typed<float, b8>(pr, out) : eval_typed<double, b8>(pr, out);
+  if (out->dtype == MDHIP_F16) return f32 ? eval_typed<float, f16>(pr, out) : eval_typed<double, f16>(pr, out);
+  if (out->dtype != pr->compute_dtype) return md_fail(MDHIP_ETYPE, "vm_eval: out dtype must be the compute dtype, bool or float16");
+  return f32 ? eval_typed<float, float>(pr, out) : eval_typed<double, double>(pr, out);
 }
 
 int mdhip_vm_eval_multi(const mdhip_vm_program *progs, const mdhip_array *outs, int n) {
   if (n < 1) return md_fail(MDHIP_EVALUE, "vm_eval_multi: no programs");
   for (int k = 0; k < n; ++k) {
     MD_TRY(md_vm_check(&progs[k]));
+    if (outs[k].dtype == MDHIP_F16) return md_fail(MDHIP_EVALUE, "vm_eval_multi: float16 outputs are stored by mdhip_vm_eval only");
     MD_TRY(md_check_array(&outs[k], "vm out"));
   }
   bool done = false;
@@ -1147,7 +1173,8 @@ int mdhip_vm_jit_probe(const mdhip_vm_program *pr, int kind, int reduce_op, int 
   else if (!probe_modes_axis(&S, pr)) return md_fail(MDHIP_EVALUE, "jit probe: kinds 8 and 9 take a 3-D program (its axis 1 is the reduced one)");
   if (kind == 5) probe_axes(&S, pr, true);
   S.rop = reduce_op;
-  S.out_bool = out_is_bool != 0 && (kind == 0 || kind == 5);
+  S.out_bool = out_is_bool != 0 && out_is_bool != 2 && (kind == 0 || kind == 5);
+  S.out_f16 = out_is_bool == 2 && (kind == 0 || kind == 5);   // (2: the float16 store of mdhip_vm_eval)
   S.store = kind == 4;
   S.Q = 4;
   S.RU = 2;
@@ -1163,6 +1190,8 @@ int mdhip_vm_jit_probe(const mdhip_vm_program *pr, int kind, int reduce_op, int 
 
 int mdhip_vm_eval_reduce_cols(const mdhip_vm_program *pr, int op, const mdhip_array *out_eval, const mdhip_array *out_red) {
   MD_TRY(md_vm_check(pr));
+  if (out_eval->dtype == MDHIP_F16 || out_red->dtype == MDHIP_F16)
+    return md_fail(MDHIP_EVALUE, "vm_eval_reduce_cols: float16 outputs are stored by mdhip_vm_eval only");
   MD_TRY(md_check_array(out_eval, "vm out"));
   MD_TRY(md_check_array(out_red, "vm out"));
   if (out_eval->dtype != pr->compute_dtype || out_red->dtype != pr->compute_dtype)

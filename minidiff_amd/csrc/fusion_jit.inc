@@ -130,14 +130,24 @@ static const char *binary_expr(int op) {
   }
   return "a";
 }
+// the type a leaf is read in (jcvt converts it to T): every dtype by name — a default that widened would make a narrower leaf's
+// vector load run past the array. An unknown code (md_vm_check refuses it) names no type: the source does not compile.
 static const char *storage_name(int dt) {
   switch (dt) {
-    case MDHIP_BOOL: return "uint8_t";
+    case MDHIP_BOOL: return "uint8_t";   // truth values: jcvt gives x != 0
     case MDHIP_I32: return "int32_t";
     case MDHIP_I64: return "int64_t";
     case MDHIP_F32: return "float";
+    case MDHIP_F64: return "double";
+    case MDHIP_F16: return "f16";
+    case MDHIP_I8: return "int8_t";
+    case MDHIP_U8: return "ju8";         // a uint8 VALUE
+    case MDHIP_I16: return "int16_t";
+    case MDHIP_U16: return "uint16_t";
+    case MDHIP_U32: return "uint32_t";
+    case MDHIP_U64: return "uint64_t";
   }
-  return "double";
+  return "jno_such_dtype";
 }
 static const char *reduce_name(int op) {
   switch (op) {
@@ -151,7 +161,7 @@ static const char *reduce_name(int op) {
 // ---- what one generated kernel is ----------------------------------------------------------------
 // How a leaf is read is a compile-time property of the generated kernel (part of the cache key), so
 // that the loads of one trip are unconditional and issue back to back:
-//   LM_VEC    unit inner stride: one 16-B (4-B for bool) vector load per group of 4 elements (RED_ROWS: also the row-invariant
+//   LM_VEC    unit inner stride: one vector load per group of 4 elements (16 B; 8 / 4 B for 2- / 1-byte leaves, 2 x 16 B for 8-byte ones) (RED_ROWS: also the row-invariant
 //             vector, at row stride 0 — every row re-reads it from the caches)
 //   LM_ROWB   inner stride 0, row stride != 0 (a column broadcast): one scalar load per row
 //   LM_CONST  ONE device element behind a stride-0 view (the backward seed): read once in the prologue
@@ -172,6 +182,7 @@ struct Spec {
   int leaf_dtype[MDHIP_VM_MAX_LEAVES] = {};
   int leaf_mode[MDHIP_VM_MAX_LEAVES] = {};
   bool f32 = true, out_bool = false, nt = false;
+  bool out_f16 = false;             // EVAL, one output: the value is rounded once to binary16 and stored as such (8-byte vectors)
   bool nt_store = false;            // non-temporal stores although the loads are cached (SWEEP with store, see sweep_cols)
   int rop = MDHIP_R_SUM;
   bool store = false;               // SWEEP: also write the evaluated value (eval + reduce-to-shape in one pass)
@@ -295,7 +306,7 @@ static void gen_prelude(std::ostringstream &o, const Spec &S, const std::string 
   o << "constexpr bool JNT = " << (S.nt ? "true" : "false") << ";  // non-temporal 16-B loads (streams larger than the Infinity Cache)\n";
   o << "constexpr bool JNT_ST = " << ((S.nt || S.nt_store) ? "true" : "false") << ";  // non-temporal 16-B stores\n";
   o << "typedef " << (S.f32 ? "float" : "double") << " T;\n";
-  o << "typedef " << (S.out_bool ? "b8" : "T") << " To;\n";
+  o << "typedef " << (S.out_bool ? "b8" : S.out_f16 ? "f16" : "T") << " To;\n";
   o << "typedef " << reduce_name(S.rop) << " R;\n";
   o << R"(
 template <class S, int N> struct alignas(sizeof(S) * N > 16 ? 16 : sizeof(S) * N) JVec { S v[N]; };
@@ -304,6 +315,9 @@ struct JArgs { JLeaf leaf[8]; double imm[48]; void *out; long long rows, inner; 
 struct JAxArgs : JArgs { long long e1, e2; long long st[8][3]; };
 template <class S> __device__ __forceinline__ T jcvt(S x) { return (T)x; }
 template <> __device__ __forceinline__ T jcvt<uint8_t>(uint8_t x) { return (T)(x != 0); }
+struct ju8 { uint8_t v; };
+template <> __device__ __forceinline__ T jcvt<ju8>(ju8 x) { return (T)x.v; }
+template <> __device__ __forceinline__ T jcvt<f16>(f16 x) { return md_cast<T>(x); }
 template <class V> __device__ __forceinline__ V jld(const V *p) {
   if constexpr (JNT && sizeof(V) == 16) {
     typedef int i32x4 __attribute__((ext_vector_type(4)));
@@ -500,7 +514,7 @@ static std::string kind_tag(const Spec &S) {
   switch (S.kind) {
     case EVAL: {
       const std::string form = S.axes ? "evalaxes" : "eval";
-      return S.n > 1 ? form + std::to_string(S.n) : (S.out_bool && !S.axes ? "evalb" : form);
+      return S.n > 1 ? form + std::to_string(S.n) : (S.out_bool && !S.axes ? "evalb" : S.out_f16 ? form + "h" : form);
     }
     case RED_ALL: return "redall";
     case RED_COLS: return S.batch ? "redcolsb" : "redcols";
@@ -848,6 +862,7 @@ static std::string make_key(const Spec &S) {
   std::ostringstream k;
   k << S.kind << ':' << (int)S.f32 << (int)S.out_bool << (int)S.nt << (int)S.nt_store << (int)S.store << ':' << S.rop << ':' << S.Q << ':' << S.RU << ':' << S.U << ':' << S.n << ':' << S.axes << (int)S.wide << ':' << S.NV;
   if (S.batch) k << 'b';
+  if (S.out_f16) k << 'h';
   for (int p = 0; p < S.n; ++p) {
     k << '/';
     for (int i = 0; i < S.pr[p]->n_instr; ++i) k << std::hex << S.pr[p]->ctrl[i] << ',';

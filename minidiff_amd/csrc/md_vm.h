@@ -215,7 +215,8 @@ static inline int md_vm_check(const mdhip_vm_program *pr) {
     if (depth > MDHIP_VM_STACK) return md_fail(MDHIP_EVALUE, "vm: stack depth %d exceeds %d", depth, MDHIP_VM_STACK);
   }
   if (depth != 1) return md_fail(MDHIP_EVALUE, "vm: program leaves %d values on the stack", depth);
-  for (int l = 0; l < pr->n_leaves; ++l) MD_TRY(md_check_array(&pr->leaves[l], "vm leaf"));
+  // a leaf has any of the twelve dtypes: it is read in its own storage type and converted to the compute dtype on load
+  for (int l = 0; l < pr->n_leaves; ++l) MD_TRY(md_check_any_array(&pr->leaves[l], "vm leaf"));
   return MDHIP_OK;
 }
 

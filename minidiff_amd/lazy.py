@@ -19,7 +19,17 @@ constant carry it inside the instruction, so a chain costs one instruction per
 operator. A tree that would exceed the bounds materialises its larger operand
 first. Values are computed in ONE float type per program (float32 or float64 —
 whatever NumPy's loop resolution gave each op); bool results travel as 0/1.
-Integer loops are never fused.
+Integer loops are never fused, and neither are loops whose dtype is storage-only
+itself (float16 + float16, int8 * int8).
+
+A LEAF may have any of the twelve dtypes: an operand of a float32 / float64 loop
+is read in its own storage type (float16, int8/16, uint8/16/32/64, as bool, int32
+and int64 always were) and converted on load — NumPy's cast of the operand to the
+loop dtype. ``astype(narrow array, float32 | float64)`` is such a leaf by itself
+(a pending array whose expression is the LEAF node: consumers read the narrow bytes
+and the float copy exists only if its bytes are needed), and
+``astype(pending float chain, float16)`` stores the chain's value as float16 in the
+same pass (``mdhip_vm_eval`` with a float16 ``out``: one rounding to nearest even).
 """
 from __future__ import annotations
 

@@ -970,8 +970,10 @@ def _binary(ufunc, code, a, b, out=None):
                 raise ValueError(f"non-broadcastable output operand with shape {out.shape} doesn't match the broadcast shape {shape}")
             _copy_into(out, const)      # (bool casts safely into every dtype)
             return out
-    if _LAZY and out is None and _prod(shape) >= _LAZY_MIN and not ((a_arr and a._code >= _NARROW_MIN) or (b_arr and b._code >= _NARROW_MIN)):
-        # (storage-only operands are never leaves of a fused program: the interpreter and the generated kernels read the five compute dtypes)
+    if _LAZY and out is None and _prod(shape) >= _LAZY_MIN and \
+            (cdt in _FLOAT_DT or not ((a_arr and a._code >= _NARROW_MIN) or (b_arr and b._code >= _NARROW_MIN))):
+        # (a storage-only operand is a leaf of a float32 / float64 loop — read in its own type, converted on load, NumPy's cast to the
+        # loop dtype; loops whose dtype is storage-only itself — float16 + float16, int8 * int8 — stay eager)
         pcdt = _FLOAT_DT.get(cdt)
         if pcdt is None and cdt.kind == "b" and code >= _capi.B_LAND:
             # logical op on bool operands: join the program of a pending operand
@@ -1073,10 +1075,12 @@ def _unary(ufunc, code, x):
             dtype_code(dt)
         _RESOLVE_CACHE[key] = loop
     # (sin(bool array): NumPy answers in float16 — computed in float32, rounded once, as NumPy's own half loops do: csrc/narrow.hip)
-    if _LAZY and code != _capi.U_INVERT and x.size > 0 and x.size >= _LAZY_MIN and x._code < _NARROW_MIN:
+    if _LAZY and code != _capi.U_INVERT and x.size > 0 and x.size >= _LAZY_MIN:
+        # (a storage-only operand joins when its loop is float32 / float64 — sin(int16), sqrt(uint32); float16 loops stay eager)
         pcdt = _FLOAT_DT.get(loop[0])
         if pcdt is not None and (loop[1] == loop[0] or loop[1] == np.bool_) and x.dtype.kind in "fb" or \
-                (pcdt is not None and x.dtype.kind == "i" and pcdt == _capi.F64):
+                (pcdt is not None and x.dtype.kind == "i" and pcdt == _capi.F64) or \
+                (pcdt is not None and x._code >= _NARROW_MIN and x.dtype.kind in "iu"):
             res = _lazy_node(_lz.UNARY, code, (x,), pcdt, x.shape, loop[1])
             if res is not None:
                 return res
@@ -1313,7 +1317,8 @@ def where(condition, x=None, y=None):
     shape = arrs[0].shape
     for v in arrs[1:]:
         shape = _broadcast_shapes(shape, v.shape)
-    if _LAZY and _prod(shape) > 0 and _prod(shape) >= _LAZY_MIN and not builtins_any(v._code >= _NARROW_MIN for v in arrs):
+    if _LAZY and _prod(shape) > 0 and _prod(shape) >= _LAZY_MIN:
+        # (storage-only operands included: a float32 / float64 result reads each in its own type)
         pcdt = _FLOAT_DT.get(odt)
         if pcdt is not None:
             res = _lazy_node(_lz.WHERE, 0, (c, a, b), pcdt, shape, odt)
@@ -1360,11 +1365,36 @@ def astype(a, dtype, copy=True, **kw):
     dtype = np.dtype(dtype)
     if dtype == a.dtype and not copy:
         return a
+    if _LAZY and a.size > 0 and a.size >= _LAZY_MIN:
+        e = a._expr
+        if e is None and a._code >= _NARROW_MIN and dtype in _FLOAT_DT:
+            # a storage-only array widened to float32 / float64: pending, its expression the leaf itself — consumers read the
+            # narrow bytes directly and the float copy exists only if somebody needs it in memory (a write into `a` evaluates it first)
+            return DeviceArray._pending(_lz.leaf(a, _FLOAT_DT[dtype]), a.shape, dtype)
+        if e is not None and dtype == np.float16 and e.kind != _lz.GEMM and _FLOAT_DT.get(a.dtype) == e.cdt:
+            res = _eval_as_float16(a, e)
+            if res is not None:
+                return res
     res = DeviceArray.empty(a.shape, dtype)
     if a._code >= _NARROW_MIN or res._code >= _NARROW_MIN:
         _lib().convert(a.desc(), res.desc())
     else:
         _lib().unary(_capi.U_COPY, a.desc(), res.desc())
+    return res
+
+
+def _eval_as_float16(a, e):
+    """astype(pending float32 / float64 chain, float16): the program stores its value as float16 in the same pass (one rounding to
+    nearest even from either float type) — the wide intermediate is never written; `a` stays pending. None: the library
+    refused (the CPU double checks the dtype of `out`) and the caller evaluates, then converts."""
+    prog, keep = _lz.build_program(e, a.shape)
+    res = DeviceArray.empty(a.shape, np.float16)
+    try:
+        _lib().vm_eval(prog, res.desc())
+    except (TypeError, ValueError):
+        return None
+    FUSION_STATS["vm_eval"] += 1
+    del keep
     return res
 
 
