@@ -2018,7 +2018,7 @@ static int run_step(const GemmStep &s, const void *const *tmp, int *skip) {
     case S_BX_SPLIT_ROWS:
     case S_BX_SPLIT_COLS:   // launched plainly, as the repack: attached events wait for the product
       return md_gemm_bf16x3_split((const float *)g.a, s.kind == S_BX_SPLIT_ROWS, g.M, g.K, g.a_ms, g.c, (unsigned *)const_cast<void *>(g.b));
-    case S_BX_GEMM: return md_gemm_bf16x3(g.a, at(s.b_planes), (float *)g.c, g.M, g.N, g.K, g.c_ms, (const unsigned *)g.b);
+    case S_BX_GEMM: return md_gemm_bf16x3(g.a, at(s.b_planes), (float *)g.c, g.M, g.N, g.K, g.c_ms, (const unsigned *)g.b, (int)md_opt(MD_OPT_GEMM_BF16X3_LOOP));
     case S_NGENERIC: return s.wide ? md_gemm_widen_generic(g, s.dtype) : md_gemm_narrow_generic(g, s.dtype);
     case S_NCONV: {
       mdhip_array sd{}, dd{};

@@ -16,7 +16,18 @@
 // rows: six plane tiles (3 x 256 + 3 x 128 rows) = 72 KiB per k-tile, two buffers = 144 KiB of the 160 KiB LDS, one block per CU and
 // two waves per SIMD. Each plane tile is staged ONCE per k-tile (global_load_lds_dwordx4: scalar base + 32-bit lane offset, a 1-KiB
 // piece = 16 rows per wave instruction, nine pieces per wave and k-tile) and serves all its products: per k16 step a wave reads 12
-// fragments (3 planes x 2 row blocks of A and of B, one ds_read_b128 each) for 24 MFMAs. No VALU work in the k16 steps; 64 adds per wave fold a k-tile's sum into the running sum.
+// fragments (3 planes x 2 row blocks of A and of B, one ds_read_b128 each) for 24 MFMAs; 64 adds per wave fold a k-tile's sum into the running sum.
+// Two k loops in one build (template argument, option gemm_bf16x3_loop), the same bits from both. Loop 0 is the loop the kernel was
+// first measured with: all nine DMAs in front of the k-tile's reads, their addresses formed anew per k-tile, the fold behind the last
+// MFMA. Loop 1 (the default; bx_tile) forms the nine piece bases once and writes the k-tile's program order out, every MFMA behind a
+// scheduling fence with what issues in its shadow: one DMA, two fragment reads of step 1, or four of the fold's adds; step 1 runs
+// sub-tile by sub-tile so that a finished sub-tile's adds go under the next one's MFMAs, and the last sub-tile's sum is added under
+// the NEXT k-tile's first MFMAs. Measured (profiles/gemm_bf16x3_loop_after.txt): the kernel 604 min / 662 median us -> 573 / 625 us per
+// 4096^3 product in the trace of bench.py; in one process, split passes included: loop 0 754 - 761 us, loop 1 709 - 726 us. Built, timed and dropped: the DMAs in one clump in front of the reads with the rest of loop
+// 1 (751 us against 711 in that run), the DMAs under step 1's MFMAs instead (789), one DMA per two or three MFMAs (724 - 732 against
+// 726: no difference), the fold as packed adds (723 against 711), and the last sub-tile's six step-1 MFMAs carried over the barrier
+// to cover the first reads' latency (719 against 709). What is left between loop 1 and the MFMA floor is the time in which both
+// waves of a SIMD stand in the same phase (barrier, first reads, DMA issue): the case for de-phasing them.
 // LDS image (as gemm_narrow.hip's KC image, for 64-B rows): [row][64 B], 16-B chunk c of row r in slot c ^ ((r >> 2) & 3), swizzled
 // through the per-lane SOURCE address; the 16 lanes of a read group hit 16 distinct bank slots.
 // The buffers are separate __shared__ objects and the k loop is unrolled by two, as in gemm_narrow.hip. Whole tiles only. The k order
@@ -144,6 +155,15 @@ __device__ __forceinline__ bx_bf16x8 bx_frag(const char *S, int rb, int s) {
   return __builtin_bit_cast(bx_bf16x8, *(const bx_i32x4 *)(S + r * BX_ROWB + ((c ^ ((r >> 2) & 3)) << 4)));
 }
 
+// the same operand from the lane's offset (bx_read_off) and the half (0, 1: rows 0 .. 31, 32 .. 63 of the wave's 64)
+__device__ __forceinline__ bx_bf16x8 bx_frag_at(const char *S, uint32_t off, int half) {
+  return __builtin_bit_cast(bx_bf16x8, *(const bx_i32x4 *)(S + off + half * 32 * BX_ROWB));
+}
+__device__ __forceinline__ uint32_t bx_read_off(int rb, int s) {
+  const int l = threadIdx.x & 63, r = rb + (l & 31), c = 2 * s + (l >> 5);
+  return (uint32_t)(r * BX_ROWB + ((c ^ ((r >> 2) & 3)) << 4));
+}
+
 // One k-tile. The matrix instruction's float32 accumulation TRUNCATES (measured: all-positive operands came out low by 2e-9 K of their
 // value with one accumulator over all of K), so the k-tile's 12 accumulations per element start from zero in a fresh accumulator and
 // the k-tile's sum is folded into the running sum with VALU adds (round to nearest), outside the k16 steps: the bias is that of 12
@@ -181,6 +201,110 @@ __device__ __forceinline__ void bx_mma(const Bx3Bufs &S, int wm, int wn, bx_f32x
     for (int j = 0; j < 2; ++j) acc[i][j] += part[i][j];
 }
 
+// ---- loop 1 ----------------------------------------------------------------------------------------------------------------------
+// The arithmetic of bx_mma per output element — 12 accumulations per k-tile in the same order into a fresh accumulator, one
+// round-to-nearest add into the running sum — with everything that is not an MFMA placed under the MFMAs:
+//   * the nine wave-uniform piece bases of a wave are formed ONCE (Bx3Src); a DMA adds the k offset with scalar adds, no multiply;
+//   * a k-tile's program order is written out and pinned with fences (bx_fence). Step 0's 12 reads go out in the order its MFMAs
+//     first need them, so the waits the compiler inserts are counted (the first MFMA waits for three reads, not twelve). Step 0 runs
+//     product by product as bx_mma does; behind its MFMAs 0 .. 3 the carried sum's adds, behind 4 .. 12 the next tile's DMAs, behind
+//     12 .. 17 step 1's reads. Step 1 runs sub-tile by sub-tile (six dependent MFMAs each, which cost no throughput); the 16 adds of a
+//     finished sub-tile go behind MFMAs 2 .. 5 of the next, and the last sub-tile's sum is carried over the barrier;
+//   * the compiler counts no LDS read past a pending DMA (its waits turn into lgkmcnt(0)), so the one full wait is taken by hand
+//     behind the last DMA, where step 0's reads are long back, and step 1's reads, issued behind it, are seven MFMAs old at theirs.
+struct Bx3Src { const char *a[3][2], *b[3]; };   // piece bases at k = 0, in SGPRs
+struct Bx3Dst { char *a[3][2], *b[3]; };         // and where they land
+
+__device__ __forceinline__ void bx_fence() { __builtin_amdgcn_sched_barrier(0); }
+
+__device__ __forceinline__ void bx_dma(const char *base, int kb, uint32_t lane_off, char *S) {
+  uint32_t off = lane_off;
+  asm("" : "+v"(off) : "s"(kb));
+  const char *src = bx_uniform(base + kb) + off;
+  __builtin_amdgcn_global_load_lds((bx_gbl_void *)src, (bx_lds_void *)S, 16, 0, 0);
+}
+
+// piece n (0 .. 8) of the next tile
+__device__ __forceinline__ void bx_dma_n(const Bx3Src &src, const Bx3Dst &dst, int n, int kb, uint32_t lane_off) {
+  const int p = n / 3, i = n % 3;
+  if (i < 2) bx_dma(src.a[p][i], kb, lane_off, dst.a[p][i]);
+  else bx_dma(src.b[p], kb, lane_off, dst.b[p]);
+}
+
+// acc[e0 .. e0 + 4) += part[e0 .. e0 + 4) as four scalar adds, pinned where they stand: the empty statement holds the four sums, so
+// that the adds neither move nor pair up into packed ones (measured slower beside MFMAs, see the header)
+__device__ __forceinline__ void bx_fold4(bx_f32x16 &acc, const bx_f32x16 &part, int e0) {
+  float r0 = acc[e0] + part[e0], r1 = acc[e0 + 1] + part[e0 + 1], r2 = acc[e0 + 2] + part[e0 + 2], r3 = acc[e0 + 3] + part[e0 + 3];
+  asm volatile("" : "+v"(r0), "+v"(r1), "+v"(r2), "+v"(r3));
+  acc[e0] = r0; acc[e0 + 1] = r1; acc[e0 + 2] = r2; acc[e0 + 3] = r3;
+}
+
+// One k-tile of loop 1: 48 MFMAs, each behind a fence with what issues in its shadow.
+template <bool STAGE>
+__device__ __forceinline__ void bx_tile(const Bx3Bufs &S, const Bx3Src &src, const Bx3Dst &dst, int kb, uint32_t lane_off, const uint32_t (&rd)[4],
+                                        bx_f32x16 (&acc)[2][2], bx_f32x16 &carry) {
+  constexpr int PA[6] = {0, 0, 1, 0, 1, 2}, PB[6] = {0, 1, 0, 2, 1, 0};
+  bx_f32x16 part[2][2];
+  bx_bf16x8 a0[3][2], b0[3][2], a1[3][2], b1[3][2];
+  // the lane's read offsets (A step 0 / 1, B step 0 / 1), opaque per tile: the twelve plane addresses of a tile are then one add each
+  // here, not two dozen registers held over the loop
+  uint32_t ra0 = rd[0], ra1 = rd[1], rb0 = rd[2], rb1 = rd[3];
+  asm volatile("" : "+v"(ra0), "+v"(ra1), "+v"(rb0), "+v"(rb1));
+  // step 0's fragments in the order a1b1, a1b2, a2b1, a1b3, (a2b2,) a3b1 first need them
+  a0[0][0] = bx_frag_at(S.a[0], ra0, 0); b0[0][0] = bx_frag_at(S.b[0], rb0, 0); b0[0][1] = bx_frag_at(S.b[0], rb0, 1); a0[0][1] = bx_frag_at(S.a[0], ra0, 1);
+  b0[1][0] = bx_frag_at(S.b[1], rb0, 0); b0[1][1] = bx_frag_at(S.b[1], rb0, 1);
+  a0[1][0] = bx_frag_at(S.a[1], ra0, 0); a0[1][1] = bx_frag_at(S.a[1], ra0, 1);
+  b0[2][0] = bx_frag_at(S.b[2], rb0, 0); b0[2][1] = bx_frag_at(S.b[2], rb0, 1);
+  a0[2][0] = bx_frag_at(S.a[2], ra0, 0); a0[2][1] = bx_frag_at(S.a[2], ra0, 1);
+  bx_fence();
+  // step 0: product-major as bx_mma. Under it: the carried sum (MFMAs 0 .. 3), step 1's fragments in the order its sub-tiles need them
+  // (two reads behind each of MFMAs 12 .. 17: the last is seven MFMAs old when step 1 starts)
+#pragma unroll
+  for (int q = 0; q < 6; ++q)
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const int n = q * 4 + i * 2 + j;
+        if (q == 0) {
+          const bx_f32x16 zero = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+          part[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0[0][i], b0[0][j], zero, 0, 0, 0);
+        } else {
+          part[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0[PA[q]][i], b0[PB[q]][j], part[i][j], 0, 0, 0);
+        }
+        if (n < 4) bx_fold4(acc[1][1], carry, 4 * n);
+        if (n >= 4 && n <= 12) {   // the next tile's nine pieces, one behind each of MFMAs 4 .. 12
+          if (STAGE) bx_dma_n(src, dst, n - 4, kb, lane_off);
+          // The compiler counts no fragment read past a pending DMA: every wait behind one is lgkmcnt(0). Taken here, where step 0's
+          // reads are a dozen MFMAs old, it is free, and the waits on step 1's reads behind it are counted again.
+          if (n == 12) __builtin_amdgcn_s_waitcnt(0xC07F);
+        }
+        switch (n) {
+          case 12: a1[0][0] = bx_frag_at(S.a[0], ra1, 0); b1[0][0] = bx_frag_at(S.b[0], rb1, 0); break;
+          case 13: b1[1][0] = bx_frag_at(S.b[1], rb1, 0); a1[1][0] = bx_frag_at(S.a[1], ra1, 0); break;
+          case 14: b1[2][0] = bx_frag_at(S.b[2], rb1, 0); a1[2][0] = bx_frag_at(S.a[2], ra1, 0); break;
+          case 15: b1[0][1] = bx_frag_at(S.b[0], rb1, 1); b1[1][1] = bx_frag_at(S.b[1], rb1, 1); break;
+          case 16: b1[2][1] = bx_frag_at(S.b[2], rb1, 1); a1[0][1] = bx_frag_at(S.a[0], ra1, 1); break;
+          case 17: a1[1][1] = bx_frag_at(S.a[1], ra1, 1); a1[2][1] = bx_frag_at(S.a[2], ra1, 1); break;
+          default: break;
+        }
+        bx_fence();
+      }
+  // step 1: sub-tile by sub-tile; a sub-tile's 16 adds go under MFMAs 2 .. 5 of the next one (its last result is two MFMAs old by then)
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    const int i = t >> 1, j = t & 1;
+#pragma unroll
+    for (int q = 0; q < 6; ++q) {
+      part[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1[PA[q]][i], b1[PB[q]][j], part[i][j], 0, 0, 0);
+      if (t > 0 && q >= 2) bx_fold4(acc[(t - 1) >> 1][(t - 1) & 1], part[(t - 1) >> 1][(t - 1) & 1], 4 * (q - 2));
+      bx_fence();
+    }
+  }
+  carry = part[1][1];
+}
+
+template <int LOOP>
 __global__ void __launch_bounds__(BX_NT) k_gemm_bf16x3(Bx3Args g) {
   __shared__ __attribute__((aligned(16))) char sA00[BX_BM * BX_ROWB];
   __shared__ __attribute__((aligned(16))) char sA01[BX_BM * BX_ROWB];
@@ -210,15 +334,56 @@ __global__ void __launch_bounds__(BX_NT) k_gemm_bf16x3(Bx3Args g) {
     for (int j = 0; j < 2; ++j)
 #pragma unroll
       for (int e = 0; e < 16; ++e) acc[i][j][e] = 0;
-  bx_stage(g, m0, n0, 0, S0, lane_off);
-  for (int kt = 0; kt < nk; kt += 2) {
-    __syncthreads();   // tile kt is in buffer 0 (the barrier's vmcnt(0) retires the DMAs); every wave is done with buffer 1
-    if (kt + 1 < nk) bx_stage(g, m0, n0, kt + 1, S1, lane_off);
-    bx_mma(S0, wm, wn, acc);
-    if (kt + 1 >= nk) break;
+  if constexpr (LOOP == 0) {
+    bx_stage(g, m0, n0, 0, S0, lane_off);
+    for (int kt = 0; kt < nk; kt += 2) {
+      __syncthreads();   // tile kt is in buffer 0 (the barrier's vmcnt(0) retires the DMAs); every wave is done with buffer 1
+      if (kt + 1 < nk) bx_stage(g, m0, n0, kt + 1, S1, lane_off);
+      bx_mma(S0, wm, wn, acc);
+      if (kt + 1 >= nk) break;
+      __syncthreads();
+      if (kt + 2 < nk) bx_stage(g, m0, n0, kt + 2, S0, lane_off);
+      bx_mma(S1, wm, wn, acc);
+    }
+  } else {
+    const int uw = __builtin_amdgcn_readfirstlane(wave);
+    const int64_t rs = g.K * 2;
+    Bx3Src src;
+    Bx3Dst d0, d1;
+#pragma unroll
+    for (int p = 0; p < 3; ++p) {
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        src.a[p][i] = bx_uniform(g.A + p * g.a_plane + (m0 + 16 * (uw + 8 * i)) * rs);
+        d0.a[p][i] = S0.a[p] + (uw + 8 * i) * 1024;
+        d1.a[p][i] = S1.a[p] + (uw + 8 * i) * 1024;
+      }
+      src.b[p] = bx_uniform(g.B + p * g.b_plane + (n0 + 16 * uw) * rs);
+      d0.b[p] = S0.b[p] + uw * 1024;
+      d1.b[p] = S1.b[p] + uw * 1024;
+    }
+    const uint32_t rd[4] = {bx_read_off(wm * 64, 0), bx_read_off(wm * 64, 1), bx_read_off(wn * 64, 0), bx_read_off(wn * 64, 1)};
+    // the sum carried into the first tile: +0 into a running sum that starts at +0 and is never -0 changes no bit
+    bx_f32x16 carry = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+    for (int n = 0; n < 9; ++n) bx_dma_n(src, d0, n, 0, lane_off);
+    int kt = 0;
+    for (; kt + 2 < nk; kt += 2) {   // whole pairs with a tile behind them: every tile of the loop stages the next one
+      __syncthreads();   // tile kt is in buffer 0 (the barrier's vmcnt(0) retires the DMAs); every wave is done with buffer 1
+      bx_tile<true>(S0, src, d1, (kt + 1) * BX_ROWB, lane_off, rd, acc, carry);
+      __syncthreads();
+      bx_tile<true>(S1, src, d0, (kt + 2) * BX_ROWB, lane_off, rd, acc, carry);
+    }
     __syncthreads();
-    if (kt + 2 < nk) bx_stage(g, m0, n0, kt + 2, S0, lane_off);
-    bx_mma(S1, wm, wn, acc);
+    if (kt + 1 < nk) {
+      bx_tile<true>(S0, src, d1, (kt + 1) * BX_ROWB, lane_off, rd, acc, carry);
+      __syncthreads();
+      bx_tile<false>(S1, src, d0, 0, lane_off, rd, acc, carry);
+    } else {
+      bx_tile<false>(S0, src, d1, 0, lane_off, rd, acc, carry);
+    }
+#pragma unroll
+    for (int e = 0; e < 16; e += 4) bx_fold4(acc[1][1], carry, e);
   }
   // accumulator element e of lane l: row (e & 3) + 8 (e >> 2) + 4 (l >> 5), column l & 31 of the 32 x 32 tile; one wave store writes
   // 32 consecutive floats of two rows (whole 128-B lines), as k_gemm_widen_mfma
@@ -248,7 +413,7 @@ int md_gemm_bf16x3_split(const float *src, bool k_contig, int64_t rows, int64_t 
   return MD_LAUNCH_CHECK("matmul(bf16x3 split)");
 }
 
-int md_gemm_bf16x3(const void *a_planes, const void *b_planes, float *c, int64_t M, int64_t N, int64_t K, int64_t c_ms, const unsigned *flag) {
+int md_gemm_bf16x3(const void *a_planes, const void *b_planes, float *c, int64_t M, int64_t N, int64_t K, int64_t c_ms, const unsigned *flag, int loop) {
   Bx3Args a{};
   a.A = (const char *)a_planes; a.B = (const char *)b_planes; a.C = c;
   a.K = K; a.c_ms = c_ms;
@@ -256,6 +421,10 @@ int md_gemm_bf16x3(const void *a_planes, const void *b_planes, float *c, int64_t
   a.tiles_m = (int)(M / BX_BM); a.tiles_n = (int)(N / BX_BN);
   a.flag = flag;
   md_opt_table()[MD_OPT_GEMM_BF16X3_RUNS] += 1;
-  MD_LAUNCH(k_gemm_bf16x3, dim3((unsigned)(a.tiles_m * a.tiles_n)), BX_NT, a);
+  const dim3 grid((unsigned)(a.tiles_m * a.tiles_n));
+  switch (loop) {
+    case 0: MD_LAUNCH(k_gemm_bf16x3<0>, grid, BX_NT, a); break;
+    default: MD_LAUNCH(k_gemm_bf16x3<1>, grid, BX_NT, a); break;
+  }
   return MD_LAUNCH_CHECK("matmul(f32 as bf16x3)");
 }

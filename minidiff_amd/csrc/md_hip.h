@@ -23,7 +23,7 @@ int md_gemm_widen_generic(const MdGemm &g, int dtype);
 // `stride` floats between rows, else between k-rows) -> three rows x K bfloat16 planes at `planes`, ORs 1 into *flag on an inf / NaN;
 // the product: C (M x N, c_ms floats between rows) from the planes, nothing when *flag != 0
 int md_gemm_bf16x3_split(const float *src, bool k_contig, int64_t rows, int64_t K, int64_t stride, void *planes, unsigned *flag);
-int md_gemm_bf16x3(const void *a_planes, const void *b_planes, float *c, int64_t M, int64_t N, int64_t K, int64_t c_ms, const unsigned *flag);
+int md_gemm_bf16x3(const void *a_planes, const void *b_planes, float *c, int64_t M, int64_t N, int64_t K, int64_t c_ms, const unsigned *flag, int loop);
 unsigned *md_tickets();                                   // MD_TICKET_WORDS zeroed counters (md_ticket.h)
 bool md_capturing();                                      // a stream capture is recording (mdhip_graph_begin .. _end)
 int *md_sticky();                                         // host-mapped word a CAPTURED gather / scatter sets on an out-of-bounds index

@@ -22,6 +22,8 @@ if os.environ.get("GEMM_GLDS_AB"):   # every config twice: register staging / di
     CFGS = {(99 if k == -1 else k) + 100 * g: v + (" +glds" if g else "") for k, v in CFGS.items() for g in (0, 1)}   # (99 = auto)
 if os.environ.get("GEMM_BF16X3_AB"):   # every config twice: fp32 fma chain / six bf16 products of pre-split planes on every eligible shape (option gemm_bf16x3)
     CFGS = {(99 if k == -1 else k) + 100000 * g: v + (" bf16x3" if g else " fp32") for k, v in CFGS.items() for g in (0, 1)}
+if os.environ.get("GEMM_BF16X3_LOOP_AB"):   # every config twice, on the six bf16 products wherever they are eligible: the product kernel's loop 0 / loop 1 (option gemm_bf16x3_loop; same bits)
+    CFGS = {(99 if k == -1 else k) + 1000000 * g: v + " bf16x3 loop %d" % g for k, v in CFGS.items() for g in (0, 1)}
 
 
 REPS = int(os.environ.get("GEMM_REPS", "5"))   # launches per timing (small shapes: more, the gaps between 5 short launches weigh)
@@ -55,6 +57,9 @@ def main():
                     opt("gemm_peel", (cfg // 10000) % 10)
                 if os.environ.get("GEMM_BF16X3_AB"):
                     opt("gemm_bf16x3", 2 * ((cfg // 100000) % 10))
+                if os.environ.get("GEMM_BF16X3_LOOP_AB"):
+                    opt("gemm_bf16x3", 2)
+                    opt("gemm_bf16x3_loop", (cfg // 1000000) % 10)
                 if cfg % 100 == 99 or cfg == -1:
                     opt("gemm_cfg", -1)      # the library's own choice
                 else:
@@ -80,7 +85,7 @@ def main():
         print(f"M={M} K={K} N={N}")
         for cfg, name in CFGS.items():
             print("   %-22s " % name + "  ".join("%s med %6.1f min %6.1f max %6.1f TF" % (t, sorted(res[(cfg, t)])[len(res[(cfg, t)]) // 2], min(res[(cfg, t)]), max(res[(cfg, t)])) for t in (("NN", "NT", "TN", "TT") if os.environ.get("GEMM_TT") else ("NN", "NT", "TN"))))
-    opt("gemm_cfg", -1); opt("gemm_glds", 1); opt("gemm_nbuf", 0); opt("gemm_peel", 1); opt("gemm_bf16x3", 1)
+    opt("gemm_cfg", -1); opt("gemm_glds", 1); opt("gemm_nbuf", 0); opt("gemm_peel", 1); opt("gemm_bf16x3", 1); opt("gemm_bf16x3_loop", 1)
 
 
 if __name__ == "__main__":

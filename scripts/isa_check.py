@@ -49,8 +49,9 @@ def disassemble(obj, wanted=()):
         shutil.rmtree(tmp, ignore_errors=True)
 
 
-def analyse(name, raw_lines):
-    """raw_lines: the kernel's lines WITH addresses (as objdump prints them)."""
+def main_loop(raw_lines):
+    """raw_lines: the kernel's lines WITH addresses (as objdump prints them) -> (all instructions, those of the main loop: the
+    backward branch's span that holds the most MFMAs)."""
     ins, addr = [], []
     for ln in raw_lines:
         body, _, tail = ln.partition("//")
@@ -69,7 +70,12 @@ def analyse(name, raw_lines):
                 if j is not None:
                     loops.append((j, i))
     best = max(loops, key=lambda ab: sum(1 for s in ins[ab[0]:ab[1]] if s.startswith("v_mfma")), default=None)
-    body = ins[best[0]:best[1] + 1] if best else []
+    return ins, (ins[best[0]:best[1] + 1] if best else [])
+
+
+def analyse(name, raw_lines):
+    """raw_lines: the kernel's lines WITH addresses (as objdump prints them)."""
+    ins, body = main_loop(raw_lines)
     dma = [s for s in body if s.startswith("global_load_lds")]
     saddr = [s for s in dma if re.search(r"global_load_lds_dwordx4\s+v\d+,\s*s\[", s)]
     vaddr = [s for s in dma if re.search(r"global_load_lds_dwordx4\s+v\[\d+:\d+\],\s*off", s)]
@@ -127,7 +133,52 @@ def report(obj=None):
     return res
 
 
+BF16X3_LOOP1 = "k_gemm_bf16x3ILi1EE"   # the loop-1 instantiation of gemm_bf16x3.hip's product kernel
+
+
+def vgpr_count(obj, frag):
+    """.vgpr_count of the one kernel of `obj` whose name contains `frag`, from the code objects' metadata notes."""
+    tmp = tempfile.mkdtemp(prefix="mdhip_isa_")
+    try:
+        local = os.path.join(tmp, "in.o")
+        shutil.copy(obj, local)
+        subprocess.run([f"{LLVM}/llvm-objdump", "--offloading", local], cwd=tmp, check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+        found = []
+        for co in sorted(f for f in os.listdir(tmp) if "gfx950" in f):
+            notes = subprocess.run([f"{LLVM}/llvm-readelf", "--notes", os.path.join(tmp, co)], check=True, capture_output=True, text=True).stdout
+            for k in re.split(r"\n\s*- \.agpr_count:", notes)[1:]:   # one chunk per kernel (.agpr_count is a kernel's first key)
+                name, n = re.search(r"\.name:\s+(\S+)", k), re.search(r"\.vgpr_count:\s+(\d+)", k)
+                if name and n and frag in name.group(1):
+                    found.append(int(n.group(1)))
+        if len(found) != 1:
+            raise RuntimeError(f"{len(found)} kernels match {frag}")
+        return found[0]
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+
+
+def report_bf16x3(obj=None):
+    """Facts about loop 1 of k_gemm_bf16x3 (tests/test_isa_bf16x3.py): analyse()'s, and of the main loop the scalar multiplies, the
+    fold's adds by form and the explicit waits; the kernel's VGPR count."""
+    obj = obj or os.path.join(ROOT, "minidiff_amd", "libmdhip.so")
+    ks = raw_kernels(disassemble(obj, (BF16X3_LOOP1,)))
+    names = [n for n in ks if BF16X3_LOOP1 in n]
+    if len(names) != 1:
+        raise RuntimeError(f"{len(names)} kernels match {BF16X3_LOOP1}")
+    res = analyse(names[0], ks[names[0]])
+    _, body = main_loop(ks[names[0]])
+    res["s_mul_loop"] = sum(1 for s in body if s.startswith("s_mul"))
+    res["v_add_f32_loop"] = sum(1 for s in body if s.startswith("v_add_f32"))
+    res["v_pk_add_f32_loop"] = sum(1 for s in body if s.startswith("v_pk_add_f32"))
+    res["barrier_loop"] = sum(1 for s in body if s.startswith("s_barrier"))
+    res["vgprs"] = vgpr_count(obj, BF16X3_LOOP1)
+    return res
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "--bf16x3":
+        print(report_bf16x3(sys.argv[2] if len(sys.argv) > 2 else None))
+        sys.exit(0)
     r = report(sys.argv[1] if len(sys.argv) > 1 else None)
     for label, d in r.items():
         print(label, d)
