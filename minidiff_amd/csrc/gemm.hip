@@ -2080,20 +2080,27 @@ struct HipExec {
 // mdhip_matmul_bias_relu_sum: the plain product's tile choice (and summation order: a mask recomputed from `a @ b + bias` agrees bit
 // for bit), restricted to tiles that divide the problem; the fused DMA kernel takes whole k-tiles only. false: not covered.
 static bool plan_epi(GemmPlan &p, GemmArgs ga) {
-  {  // a shape whose plain product runs as bf16x3 (past the hand-offs, which take no such shape, and the k ranges) is not covered: the
-     // caller's plain product and fused tail keep product and mask bit-identical; an epilogue form of that kernel is not built
+  // The promise is kept by planning the plain product itself: covered only when that is ONE fp32 MFMA launch over all of k — not a
+  // long-k hand-off, k ranges, in-kernel split-K, a peeled product (other orders of summation) or bf16x3 (no epilogue form of that
+  // kernel is built) — and the fused kernel is of the same family (below): the caller's plain product and fused tail otherwise.
+  bool plain_kc;
+  {
     MdGemm g{1, ga.M, ga.N, ga.K, ga.A, ga.B, ga.C, 0, ga.a_ms, ga.a_ks, 0, ga.b_ks, ga.b_ns, 0, ga.c_ms, ga.c_ns};
-    int64_t splits, k_chunk;
-    if (!kranges_shape(g, &splits, &k_chunk) && bf16x3_takes(g)) {
-      GemmPlan q;
-      if (plan_bf16x3(q, g)) return false;
-    }
+    GemmPlan q;
+    if (md_longk_shape(g) || plan_kranges(q, g)) return false;
+    plan_f32(q, g);
+    if (q.n != 1 || q.step[0].kind != S_F32 || q.step[0].splits != 1) return false;
+    plain_kc = q.step[0].staging != ST_REG;   // k_gemm_f32_kc_glds (whole or ragged tiles): k pairs (0, 4), (1, 5), .. of every eight
   }
   const bool priced = dma_priced(ga, true, false, true) && ga.K % 32 == 0;
   const int cfg = pick_cfg(ga.M, ga.N, ga.K, 1, false, priced);
   auto divides = [&](Tile t) { return t.bm && ga.M % t.bm == 0 && ga.N % t.bn == 0; };
   const bool dma = priced && divides(kTiles[cfg].dma[0]);
   if (dma && !dma_strides(ga, true, false, kLane32)) return false;   // (a tile chosen at its DMA rate does not fall back)
+  // the register-staged kernels feed the MFMA the k pairs (0, 1), (2, 3), ..: a register-staged epilogue under a plain product on the
+  // direct-to-LDS kernel (K % 32 != 0, or a tile that does not divide the problem: its ragged forms) would round differently, and a
+  // pre-activation within an ulp of 0 would get another mask bit than `a @ b + bias > 0` (tests/test_matmul_paths.py: test_epilogue)
+  if (dma != plain_kc) return false;
   int row = dma ? cfg : -1;
   // else the register-staged tile of the choice, then smaller ones: 128x128 after 256x128, 128x64 after all but 64x64, 64x64
   for (const int c : {cfg, cfg == CFG_256x128x16 ? (int)CFG_128x128x16 : -1, cfg != CFG_64x64x16 ? (int)CFG_128x64x16 : -1, (int)CFG_64x64x16})
