@@ -1679,14 +1679,17 @@ static bool plan_bf16x3(GemmPlan &p, const MdGemm &g) {
   char *buf = (char *)p.temp(256 + a_bytes + b_bytes);
   char *ap = buf + 256, *bp = ap + a_bytes;
   p.add(S_BX_CLEAR, "matmul(bf16x3 flag)").g.b = buf;
+  const int layout = md_opt(MD_OPT_GEMM_BF16X3_PLANES) != 0;   // the plane image (md_bf16x3_layout.h), one for the three steps: GemmStep::cfg
   auto split = [&](const void *src, int64_t rows, int64_t rs, int64_t ks, void *dst) {
-    MdGemm &x = p.add(ks == 1 ? S_BX_SPLIT_ROWS : S_BX_SPLIT_COLS, "matmul(bf16x3 split)").g;
+    GemmStep &st = p.add(ks == 1 ? S_BX_SPLIT_ROWS : S_BX_SPLIT_COLS, "matmul(bf16x3 split)");
+    st.cfg = layout;
+    MdGemm &x = st.g;
     x.a = src; x.b = buf; x.c = dst; x.M = rows; x.K = g.K; x.a_ms = ks == 1 ? rs : ks;
   };
   split(g.a, g.M, g.a_ms, g.a_ks, ap);
   split(g.b, g.N, g.b_ns, g.b_ks, bp);
   GemmStep &m = p.add(S_BX_GEMM, "matmul(f32 as bf16x3)");
-  m.g = g; m.g.a = ap; m.g.b = buf; m.b_planes = bp;
+  m.g = g; m.g.a = ap; m.g.b = buf; m.b_planes = bp; m.cfg = layout;
   for (int i = 0; i < q.n; ++i) {
     GemmStep &s = p.step[p.n++] = q.step[i];
     if (s.kind == S_F32) s.ga.run_if_set = (const unsigned *)buf;
@@ -2017,8 +2020,10 @@ static int run_step(const GemmStep &s, const void *const *tmp, int *skip) {
     case S_BX_CLEAR: return md_hip_check(hipMemsetAsync(const_cast<void *>(g.b), 0, 4, md_stream()), s.what);
     case S_BX_SPLIT_ROWS:
     case S_BX_SPLIT_COLS:   // launched plainly, as the repack: attached events wait for the product
-      return md_gemm_bf16x3_split((const float *)g.a, s.kind == S_BX_SPLIT_ROWS, g.M, g.K, g.a_ms, g.c, (unsigned *)const_cast<void *>(g.b));
-    case S_BX_GEMM: return md_gemm_bf16x3(g.a, at(s.b_planes), (float *)g.c, g.M, g.N, g.K, g.c_ms, (const unsigned *)g.b, (int)md_opt(MD_OPT_GEMM_BF16X3_LOOP));
+      return md_gemm_bf16x3_split((const float *)g.a, s.kind == S_BX_SPLIT_ROWS, g.M, g.K, g.a_ms, g.c, (unsigned *)const_cast<void *>(g.b), s.cfg);
+    case S_BX_GEMM:
+      return md_gemm_bf16x3(g.a, at(s.b_planes), (float *)g.c, g.M, g.N, g.K, g.c_ms, (const unsigned *)g.b, (int)md_opt(MD_OPT_GEMM_BF16X3_LOOP), s.cfg,
+                            (int)md_opt(MD_OPT_GEMM_BF16X3_BAND));
     case S_NGENERIC: return s.wide ? md_gemm_widen_generic(g, s.dtype) : md_gemm_narrow_generic(g, s.dtype);
     case S_NCONV: {
       mdhip_array sd{}, dd{};

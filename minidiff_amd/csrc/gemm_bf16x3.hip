@@ -7,8 +7,22 @@
 // Planned by gemm.hip (plan_bf16x3): split A, split B, the product, and behind it the fp32 kernel that runs instead when a split saw
 // an inf or a NaN (the flag word).
 //
-// Split pass (one per operand, streaming): reads the float32 operand once, writes three row-major [rows][K] bfloat16 planes, the k
-// axis contiguous whatever the operand's layout — k_bf16x3_split_rows for an operand whose k axis is contiguous, k_bf16x3_split_cols
+// Plane image (md_bf16x3_layout.h; option gemm_bf16x3_planes, chosen by plan_bf16x3 for the split passes and the product alike):
+// k-tile-major [K / 32][rows][64 B] by default — the 32 k of one k-tile of one row are 64 contiguous bytes and the rows of a k-tile
+// follow each other, so one 1-KiB DMA piece (16 rows) is eight whole 128-B lines that no other k-tile shares — or [rows][K] (0: the
+// image the kernel was merged with, where the same piece is 16 half-used lines 2 K bytes apart). One addressing serves both: rows
+// `rs` bytes apart, k-tiles `a_kstep` / `b_kstep` bytes apart (64 B x the operand's rows under the default: A and B step differently).
+// Measured at 4096^3 (profiles/gemm_bf16x3_layout_after.txt): the L2's read requests to the fabric halve (26.1 M -> 13.4 M per
+// launch); with the walk below the kernel 573 min / 618 median us -> 450 / 525 us in the trace of bench.py, cfg2 484 -> 560 passes/s.
+// Tile walk (md_bf16x3_tile; option gemm_bf16x3_band): an XCD's blocks take consecutive tiles of a grouped order with bands of gm
+// tile rows; gm = 1 is the row-major walk the kernel was merged with. 4 x 8 bands (band 0, the default: gm chosen from the CU count)
+// take the fabric reads from 1.59 to 0.75 GiB per launch and the hit rate from 64 to 82 %, as modelled, and return 1.4 % under the
+// default image at 4096 and 8192 rows, nothing at 1024 rows (7.5 % under [rows][K]): a narrow win. Halving the bytes again for
+// 1.4 % says that the memory path is not what this kernel waits for once its pieces are contiguous.
+//
+// Split pass (one per operand, streaming): reads the float32 operand once, writes three bfloat16 planes in the plan's image
+// whatever the operand's layout — k_bf16x3_split_rows ([rows][K]) / k_bf16x3_split_rows_kt (k-tile-major: two adjacent rows per wave,
+// so that a wave store still writes whole lines) for an operand whose k axis is contiguous, k_bf16x3_split_cols
 // (64 rows x 32 k patches transposed through LDS) for one that is contiguous along its rows (A of TN, B of NN, both of TT). 16-B
 // loads and stores. A block that saw a non-finite element ORs 1 into the flag word (an ordinary vector atomic).
 //
@@ -24,7 +38,7 @@
 // sub-tile by sub-tile so that a finished sub-tile's adds go under the next one's MFMAs, and the last sub-tile's sum is added under
 // the NEXT k-tile's first MFMAs. Measured (profiles/gemm_bf16x3_loop_after.txt): the kernel 604 min / 662 median us -> 573 / 625 us per
 // 4096^3 product in the trace of bench.py; in one process, split passes included: loop 0 754 - 761 us, loop 1 709 - 726 us. Built, timed and dropped: the DMAs in one clump in front of the reads with the rest of loop
-// 1 (751 us against 711 in that run), the DMAs under step 1's MFMAs instead (789), one DMA per two or three MFMAs (724 - 732 against
+// 1 (all these on [rows][K] planes; 751 us against 711 in that run), the DMAs under step 1's MFMAs instead (789), one DMA per two or three MFMAs (724 - 732 against
 // 726: no difference), the fold as packed adds (723 against 711), and the last sub-tile's six step-1 MFMAs carried over the barrier
 // to cover the first reads' latency (719 against 709). What is left between loop 1 and the MFMA floor is the time in which both
 // waves of a SIMD stand in the same phase (barrier, first reads, DMA issue): the case for de-phasing them.
@@ -34,6 +48,7 @@
 // and the product order are fixed: an output element's bits do not depend on M, N or where its tile lies. No float atomics.
 #include "md_hip.h"
 #include "md_bf16x3.h"
+#include "md_bf16x3_layout.h"
 
 namespace {
 
@@ -67,7 +82,8 @@ __device__ __forceinline__ bool bx_split8(const float (&x)[8], bx_i32x4 *q1, bx_
   return bad;
 }
 
-// src: rows x K float32, k unit-stride, `rs` floats between rows. dst: three planes of rows x K bfloat16, `plane` BYTES apart.
+// src: rows x K float32, k unit-stride, `rs` floats between rows. dst: three planes of rows x K bfloat16 in layout 0 ([rows][K]),
+// `plane` BYTES apart.
 __global__ void __launch_bounds__(256) k_bf16x3_split_rows(const float *__restrict__ src, int64_t rows, int64_t K, int64_t rs, char *__restrict__ dst,
                                                            int64_t plane, unsigned *flag) {
   bool bad = false;
@@ -78,16 +94,38 @@ __global__ void __launch_bounds__(256) k_bf16x3_split_rows(const float *__restri
       const float x[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
       bx_i32x4 q1, q2, q3;
       bad |= bx_split8(x, &q1, &q2, &q3);
-      char *d = dst + (r * K + k) * 2;
+      char *d = dst + md_bf16x3_plane_off(r, k, K * 2, 64);
       *(bx_i32x4 *)d = q1; *(bx_i32x4 *)(d + plane) = q2; *(bx_i32x4 *)(d + 2 * plane) = q3;
     }
   }
   if (__syncthreads_or(bad) && threadIdx.x == 0) atomicOr(flag, 1u);
 }
 
-// src: K x rows float32, the rows unit-stride, `ks` floats between k-rows. One block: 64 rows x 32 k.
+// The same pass into layout 1 ([K / 32][rows][64 B]), where a k-tile's 64 B of one row are followed by the next ROW's: a wave takes
+// two adjacent rows (rows is even: a multiple of the block tile) x eight k-tiles — lane l row 2 j + ((l >> 2) & 1), k-tile l >> 3,
+// 16-B chunk l & 3 — so that eight lanes store one whole 128-B line and the lanes of one row still load 1 KiB of it in a piece.
+__global__ void __launch_bounds__(256) k_bf16x3_split_rows_kt(const float *__restrict__ src, int64_t rows, int64_t K, int64_t rs, char *__restrict__ dst,
+                                                              int64_t plane, unsigned *flag) {
+  bool bad = false;
+  const int l = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int64_t k = (((int64_t)blockIdx.x * 4 + w) * 8 + (l >> 3)) * 32 + (l & 3) * 8;
+  if (k < K) {
+    for (int64_t r = (int64_t)blockIdx.y * 2 + ((l >> 2) & 1); r < rows; r += (int64_t)gridDim.y * 2) {
+      const bx_f32x4 lo = *(const bx_f32x4 *)(src + r * rs + k), hi = *(const bx_f32x4 *)(src + r * rs + k + 4);
+      const float x[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+      bx_i32x4 q1, q2, q3;
+      bad |= bx_split8(x, &q1, &q2, &q3);
+      char *d = dst + md_bf16x3_plane_off(r, k, 64, rows * 64);
+      *(bx_i32x4 *)d = q1; *(bx_i32x4 *)(d + plane) = q2; *(bx_i32x4 *)(d + 2 * plane) = q3;
+    }
+  }
+  if (__syncthreads_or(bad) && threadIdx.x == 0) atomicOr(flag, 1u);
+}
+
+// src: K x rows float32, the rows unit-stride, `ks` floats between k-rows. One block: 64 rows x 32 k, stored at `prs` bytes between
+// rows and `pks` between k-tiles (either layout; under layout 1 the block's 4 KiB per plane are contiguous).
 __global__ void __launch_bounds__(256) k_bf16x3_split_cols(const float *__restrict__ src, int64_t rows, int64_t K, int64_t ks, char *__restrict__ dst,
-                                                           int64_t plane, unsigned *flag) {
+                                                           int64_t plane, int64_t prs, int64_t pks, unsigned *flag) {
   __shared__ float T[32][66];   // [k][row]; 66: the transposed reads below hit 64 distinct banks
   const int t = threadIdx.x;
   for (int64_t kb = blockIdx.y; kb < K / 32; kb += gridDim.y) {
@@ -105,7 +143,7 @@ __global__ void __launch_bounds__(256) k_bf16x3_split_cols(const float *__restri
     for (int j = 0; j < 8; ++j) x[j] = T[kg * 8 + j][r];
     bx_i32x4 q1, q2, q3;
     const bool bad = bx_split8(x, &q1, &q2, &q3);
-    char *d = dst + ((r0 + r) * K + k0 + kg * 8) * 2;
+    char *d = dst + md_bf16x3_plane_off(r0 + r, k0 + kg * 8, prs, pks);
     *(bx_i32x4 *)d = q1; *(bx_i32x4 *)(d + plane) = q2; *(bx_i32x4 *)(d + 2 * plane) = q3;
     if (__syncthreads_or(bad) && t == 0) atomicOr(flag, 1u);   // (also: every lane is done with T)
   }
@@ -113,11 +151,12 @@ __global__ void __launch_bounds__(256) k_bf16x3_split_cols(const float *__restri
 
 // ---- product ---------------------------------------------------------------------------------------------------------------------
 struct Bx3Args {
-  const char *A, *B;        // plane 1 of each operand; planes 2 and 3 follow a_plane / b_plane BYTES apart; rows of K bfloat16
+  const char *A, *B;        // plane 1 of each operand; planes 2 and 3 follow a_plane / b_plane BYTES apart
   float *C;
   int64_t K, c_ms;          // c_ms in floats
   int64_t a_plane, b_plane;
-  int tiles_m, tiles_n;
+  int64_t rs, a_kstep, b_kstep;   // the plane images (md_bf16x3_layout.h): bytes between rows, and between k-tiles of A / of B
+  int tiles_m, tiles_n, gm; // gm: band height of the tile walk (md_bf16x3_tile)
   const unsigned *flag;     // the split passes' verdict: a non-zero word = nothing to do here (the fp32 kernel behind runs instead)
 };
 
@@ -129,10 +168,10 @@ __device__ __forceinline__ const char *bx_uniform(const char *p) {
 
 // One 1-KiB piece (16 rows x 64 B) of a plane tile: lane l lands in LDS at piece + 16 l = row l >> 2, slot l & 3, so it fetches chunk
 // (l & 3) ^ ((row >> 2) & 3) of its row (the tile row is 16 piece + (l >> 2): (row >> 2) & 3 = (l >> 4) & 3).
-__device__ __forceinline__ void bx_piece(const char *P, int64_t rs, int64_t row, int64_t k0, uint32_t lane_off, char *S) {
+__device__ __forceinline__ void bx_piece(const char *P, int64_t rs, int64_t row, int64_t kstep, int kt, uint32_t lane_off, char *S) {
   uint32_t off = lane_off;
-  asm("" : "+v"(off) : "s"((int)k0));
-  const char *src = bx_uniform(P + row * rs + k0 * 2) + off;
+  asm("" : "+v"(off) : "s"(kt));
+  const char *src = bx_uniform(P + row * rs + kt * kstep) + off;
   __builtin_amdgcn_global_load_lds((bx_gbl_void *)src, (bx_lds_void *)S, 16, 0, 0);
 }
 
@@ -140,12 +179,11 @@ struct Bx3Bufs { char *a[3], *b[3]; };
 
 __device__ __forceinline__ void bx_stage(const Bx3Args &g, int64_t m0, int64_t n0, int kt, const Bx3Bufs &S, uint32_t lane_off) {
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int64_t rs = g.K * 2, k0 = (int64_t)kt * BX_BK;
 #pragma unroll
   for (int p = 0; p < 3; ++p) {
 #pragma unroll
-    for (int i = 0; i < 2; ++i) bx_piece(g.A + p * g.a_plane, rs, m0 + 16 * (wave + 8 * i), k0, lane_off, S.a[p] + (wave + 8 * i) * 1024);
-    bx_piece(g.B + p * g.b_plane, rs, n0 + 16 * wave, k0, lane_off, S.b[p] + wave * 1024);
+    for (int i = 0; i < 2; ++i) bx_piece(g.A + p * g.a_plane, g.rs, m0 + 16 * (wave + 8 * i), g.a_kstep, kt, lane_off, S.a[p] + (wave + 8 * i) * 1024);
+    bx_piece(g.B + p * g.b_plane, g.rs, n0 + 16 * wave, g.b_kstep, kt, lane_off, S.b[p] + wave * 1024);
   }
 }
 
@@ -212,22 +250,24 @@ __device__ __forceinline__ void bx_mma(const Bx3Bufs &S, int wm, int wn, bx_f32x
 //     finished sub-tile go behind MFMAs 2 .. 5 of the next, and the last sub-tile's sum is carried over the barrier;
 //   * the compiler counts no LDS read past a pending DMA (its waits turn into lgkmcnt(0)), so the one full wait is taken by hand
 //     behind the last DMA, where step 0's reads are long back, and step 1's reads, issued behind it, are seven MFMAs old at theirs.
-struct Bx3Src { const char *a[3][2], *b[3]; };   // piece bases at k = 0, in SGPRs
+struct Bx3Src { const char *a[3][2], *b[3]; };   // piece bases of the k-tile staged last, in SGPRs
 struct Bx3Dst { char *a[3][2], *b[3]; };         // and where they land
 
 __device__ __forceinline__ void bx_fence() { __builtin_amdgcn_sched_barrier(0); }
 
-__device__ __forceinline__ void bx_dma(const char *base, int kb, uint32_t lane_off, char *S) {
+// The piece base steps to the next k-tile (a 64-bit scalar add: the step is 64 B under layout 0, 64 B x the operand's rows under
+// layout 1, which fits no 32-bit offset) and the piece is fetched from there.
+__device__ __forceinline__ void bx_dma(const char *&base, int64_t step, uint32_t lane_off, char *S) {
+  base = bx_uniform(base + step);
   uint32_t off = lane_off;
-  asm("" : "+v"(off) : "s"(kb));
-  const char *src = bx_uniform(base + kb) + off;
-  __builtin_amdgcn_global_load_lds((bx_gbl_void *)src, (bx_lds_void *)S, 16, 0, 0);
+  asm("" : "+v"(off));
+  __builtin_amdgcn_global_load_lds((bx_gbl_void *)(base + off), (bx_lds_void *)S, 16, 0, 0);
 }
 
-// piece n (0 .. 8) of the next tile
-__device__ __forceinline__ void bx_dma_n(const Bx3Src &src, const Bx3Dst &dst, int n, int kb, uint32_t lane_off) {
+// piece n (0 .. 8) of the next tile; ka / kb: the k step of A's / of B's pieces
+__device__ __forceinline__ void bx_dma_n(Bx3Src &src, const Bx3Dst &dst, int n, int64_t ka, int64_t kb, uint32_t lane_off) {
   const int p = n / 3, i = n % 3;
-  if (i < 2) bx_dma(src.a[p][i], kb, lane_off, dst.a[p][i]);
+  if (i < 2) bx_dma(src.a[p][i], ka, lane_off, dst.a[p][i]);
   else bx_dma(src.b[p], kb, lane_off, dst.b[p]);
 }
 
@@ -241,7 +281,7 @@ __device__ __forceinline__ void bx_fold4(bx_f32x16 &acc, const bx_f32x16 &part, 
 
 // One k-tile of loop 1: 48 MFMAs, each behind a fence with what issues in its shadow.
 template <bool STAGE>
-__device__ __forceinline__ void bx_tile(const Bx3Bufs &S, const Bx3Src &src, const Bx3Dst &dst, int kb, uint32_t lane_off, const uint32_t (&rd)[4],
+__device__ __forceinline__ void bx_tile(const Bx3Bufs &S, Bx3Src &src, const Bx3Dst &dst, int64_t ka, int64_t kb, uint32_t lane_off, const uint32_t (&rd)[4],
                                         bx_f32x16 (&acc)[2][2], bx_f32x16 &carry) {
   constexpr int PA[6] = {0, 0, 1, 0, 1, 2}, PB[6] = {0, 1, 0, 2, 1, 0};
   bx_f32x16 part[2][2];
@@ -274,7 +314,7 @@ __device__ __forceinline__ void bx_tile(const Bx3Bufs &S, const Bx3Src &src, con
         }
         if (n < 4) bx_fold4(acc[1][1], carry, 4 * n);
         if (n >= 4 && n <= 12) {   // the next tile's nine pieces, one behind each of MFMAs 4 .. 12
-          if (STAGE) bx_dma_n(src, dst, n - 4, kb, lane_off);
+          if (STAGE) bx_dma_n(src, dst, n - 4, ka, kb, lane_off);
           // The compiler counts no fragment read past a pending DMA: every wait behind one is lgkmcnt(0). Taken here, where step 0's
           // reads are a dozen MFMAs old, it is free, and the waits on step 1's reads behind it are counted again.
           if (n == 12) __builtin_amdgcn_s_waitcnt(0xC07F);
@@ -323,10 +363,12 @@ __global__ void __launch_bounds__(BX_NT) k_gemm_bf16x3(Bx3Args g) {
   // XCD-aware order, as gemm_narrow.hip: the blocks that share an XCD take a contiguous band of output tiles
   const int nwg = g.tiles_m * g.tiles_n, bid = blockIdx.x, xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
   const int wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-  const int64_t m0 = (int64_t)(wg / g.tiles_n) * BX_BM, n0 = (int64_t)(wg % g.tiles_n) * BX_BN;
+  int tm, tn;
+  md_bf16x3_tile(wg, g.tiles_m, g.tiles_n, g.gm, &tm, &tn);
+  const int64_t m0 = (int64_t)tm * BX_BM, n0 = (int64_t)tn * BX_BN;
   const int wave = threadIdx.x >> 6, wm = wave >> 1, wn = wave & 1, l = threadIdx.x & 63;
   const int nk = (int)(g.K / BX_BK);
-  const uint32_t lane_off = (uint32_t)((l >> 2) * (g.K * 2) + (((l & 3) ^ ((l >> 4) & 3)) << 4));
+  const uint32_t lane_off = (uint32_t)((l >> 2) * g.rs + (((l & 3) ^ ((l >> 4) & 3)) << 4));
   bx_f32x16 acc[2][2];
 #pragma unroll
   for (int i = 0; i < 2; ++i)
@@ -347,7 +389,7 @@ __global__ void __launch_bounds__(BX_NT) k_gemm_bf16x3(Bx3Args g) {
     }
   } else {
     const int uw = __builtin_amdgcn_readfirstlane(wave);
-    const int64_t rs = g.K * 2;
+    const int64_t rs = g.rs, ka = g.a_kstep, kb = g.b_kstep;
     Bx3Src src;
     Bx3Dst d0, d1;
 #pragma unroll
@@ -366,21 +408,21 @@ __global__ void __launch_bounds__(BX_NT) k_gemm_bf16x3(Bx3Args g) {
     // the sum carried into the first tile: +0 into a running sum that starts at +0 and is never -0 changes no bit
     bx_f32x16 carry = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
-    for (int n = 0; n < 9; ++n) bx_dma_n(src, d0, n, 0, lane_off);
+    for (int n = 0; n < 9; ++n) bx_dma_n(src, d0, n, 0, 0, lane_off);
     int kt = 0;
     for (; kt + 2 < nk; kt += 2) {   // whole pairs with a tile behind them: every tile of the loop stages the next one
       __syncthreads();   // tile kt is in buffer 0 (the barrier's vmcnt(0) retires the DMAs); every wave is done with buffer 1
-      bx_tile<true>(S0, src, d1, (kt + 1) * BX_ROWB, lane_off, rd, acc, carry);
+      bx_tile<true>(S0, src, d1, ka, kb, lane_off, rd, acc, carry);
       __syncthreads();
-      bx_tile<true>(S1, src, d0, (kt + 2) * BX_ROWB, lane_off, rd, acc, carry);
+      bx_tile<true>(S1, src, d0, ka, kb, lane_off, rd, acc, carry);
     }
     __syncthreads();
     if (kt + 1 < nk) {
-      bx_tile<true>(S0, src, d1, (kt + 1) * BX_ROWB, lane_off, rd, acc, carry);
+      bx_tile<true>(S0, src, d1, ka, kb, lane_off, rd, acc, carry);
       __syncthreads();
-      bx_tile<false>(S1, src, d0, 0, lane_off, rd, acc, carry);
+      bx_tile<false>(S1, src, d0, 0, 0, lane_off, rd, acc, carry);
     } else {
-      bx_tile<false>(S0, src, d1, 0, lane_off, rd, acc, carry);
+      bx_tile<false>(S0, src, d1, 0, 0, lane_off, rd, acc, carry);
     }
 #pragma unroll
     for (int e = 0; e < 16; e += 4) bx_fold4(acc[1][1], carry, e);
@@ -401,24 +443,31 @@ __global__ void __launch_bounds__(BX_NT) k_gemm_bf16x3(Bx3Args g) {
 }  // namespace
 
 // gemm.hip's plan steps: see md_hip.h
-int md_gemm_bf16x3_split(const float *src, bool k_contig, int64_t rows, int64_t K, int64_t stride, void *planes, unsigned *flag) {
+int md_gemm_bf16x3_split(const float *src, bool k_contig, int64_t rows, int64_t K, int64_t stride, void *planes, unsigned *flag, int layout) {
   const int64_t plane = rows * K * 2;
-  if (k_contig) {
+  if (k_contig && layout) {
+    const dim3 grid((unsigned)((K / 32 + 31) / 32), (unsigned)(rows / 2 < 65535 ? rows / 2 : 65535));
+    k_bf16x3_split_rows_kt<<<grid, 256, 0, md_stream()>>>(src, rows, K, stride, (char *)planes, plane, flag);
+  } else if (k_contig) {
     const dim3 grid((unsigned)((K / 8 + 255) / 256), (unsigned)(rows < 65535 ? rows : 65535));
     k_bf16x3_split_rows<<<grid, 256, 0, md_stream()>>>(src, rows, K, stride, (char *)planes, plane, flag);
   } else {
     const dim3 grid((unsigned)(rows / 64), (unsigned)(K / 32 < 65535 ? K / 32 : 65535));
-    k_bf16x3_split_cols<<<grid, 256, 0, md_stream()>>>(src, rows, K, stride, (char *)planes, plane, flag);
+    k_bf16x3_split_cols<<<grid, 256, 0, md_stream()>>>(src, rows, K, stride, (char *)planes, plane, md_bf16x3_row_stride(layout, K),
+                                                       md_bf16x3_k_step(layout, rows), flag);
   }
   return MD_LAUNCH_CHECK("matmul(bf16x3 split)");
 }
 
-int md_gemm_bf16x3(const void *a_planes, const void *b_planes, float *c, int64_t M, int64_t N, int64_t K, int64_t c_ms, const unsigned *flag, int loop) {
+int md_gemm_bf16x3(const void *a_planes, const void *b_planes, float *c, int64_t M, int64_t N, int64_t K, int64_t c_ms, const unsigned *flag, int loop,
+                   int layout, int band) {
   Bx3Args a{};
   a.A = (const char *)a_planes; a.B = (const char *)b_planes; a.C = c;
   a.K = K; a.c_ms = c_ms;
   a.a_plane = M * K * 2; a.b_plane = N * K * 2;
+  a.rs = md_bf16x3_row_stride(layout, K); a.a_kstep = md_bf16x3_k_step(layout, M); a.b_kstep = md_bf16x3_k_step(layout, N);
   a.tiles_m = (int)(M / BX_BM); a.tiles_n = (int)(N / BX_BN);
+  a.gm = md_bf16x3_band(a.tiles_m, MD_NUM_CUS / 8, band);   // (one block per CU: the CUs of an XCD hold that many tiles at a time)
   a.flag = flag;
   md_opt_table()[MD_OPT_GEMM_BF16X3_RUNS] += 1;
   const dim3 grid((unsigned)(a.tiles_m * a.tiles_n));

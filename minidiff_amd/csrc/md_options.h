@@ -42,6 +42,8 @@
   X(GEMM_BF16X3, "gemm_bf16x3", 1, 'x')                /* large float32 products as six bf16 products of pre-split planes: 0 never | 1 above the size floors | 2 every shape the kernels take and whose fp32 plan is plain launches (tests) */ \
   X(GEMM_BF16X3_RUNS, "gemm_bf16x3_runs", 0, 'x')      /* a COUNTER kept in this table so that tests can read it (and, like any entry, write it): the host adds 1 when it ISSUES the bf16x3 product kernel — a graph replay does not count */ \
   X(GEMM_BF16X3_LOOP, "gemm_bf16x3_loop", 1, 'x')      /* k loop of the bf16x3 product kernel: 0 staging in front of the reads, fold behind the MFMAs | 1 staging and fold under the MFMAs (same bits; A/B) */ \
+  X(GEMM_BF16X3_BAND, "gemm_bf16x3_band", 0, 'x')      /* tile walk of the bf16x3 product kernel, tile rows per band of an XCD's tiles: 0 by the CU count | 1 row-major | n forced (same bits; A/B) */ \
+  X(GEMM_BF16X3_PLANES, "gemm_bf16x3_planes", 1, 'x')  /* image of the bf16x3 planes: 0 [rows][K] | 1 k-tile-major [K / 32][rows][64 B] (same bits; A/B) */ \
   X(JIT_U, "jit_u", 0, 'x')                            /* vector groups per lane and trip of the generated streaming kernels (0: by form) */ \
   X(JIT_BLOCKS, "jit_blocks", 0, 'x')                  /* blocks per CU of the generated EVAL kernels (0: by form) */                     \
   X(JIT_AXES_WIDE, "jit_axes_wide", 0, 'x')            /* 1: generated three / four-axis EVAL kernels take the 64-bit index form at any size (tests) */ \

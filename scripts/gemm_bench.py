@@ -24,6 +24,8 @@ if os.environ.get("GEMM_BF16X3_AB"):   # every config twice: fp32 fma chain / si
     CFGS = {(99 if k == -1 else k) + 100000 * g: v + (" bf16x3" if g else " fp32") for k, v in CFGS.items() for g in (0, 1)}
 if os.environ.get("GEMM_BF16X3_LOOP_AB"):   # every config twice, on the six bf16 products wherever they are eligible: the product kernel's loop 0 / loop 1 (option gemm_bf16x3_loop; same bits)
     CFGS = {(99 if k == -1 else k) + 1000000 * g: v + " bf16x3 loop %d" % g for k, v in CFGS.items() for g in (0, 1)}
+if os.environ.get("GEMM_BF16X3_LAYOUT_AB"):   # every config four times, on the six bf16 products wherever they are eligible: plane image [rows][K] / k-tile-major x tile walk row-major / banded (options gemm_bf16x3_planes, gemm_bf16x3_band; same bits)
+    CFGS = {(99 if k == -1 else k) + 10000000 * g: v + " bf16x3 planes %d band %s" % (g >> 1, "auto" if g & 1 else "1") for k, v in CFGS.items() for g in (0, 1, 2, 3)}
 
 
 REPS = int(os.environ.get("GEMM_REPS", "5"))   # launches per timing (small shapes: more, the gaps between 5 short launches weigh)
@@ -32,6 +34,11 @@ REPS = int(os.environ.get("GEMM_REPS", "5"))   # launches per timing (small shap
 def main():
     lib = _capi.load()
     opt = lambda name, v: lib.debug_set_option(name.encode(), int(v))   # noqa: E731
+    layout_defaults = {}   # what the library chose itself, put back at the end
+    for name in ("gemm_bf16x3_planes", "gemm_bf16x3_band"):
+        v = C.c_int64()
+        lib.debug_get_option(name.encode(), C.byref(v))
+        layout_defaults[name] = v.value
     shapes = [(4096, 4096, 4096), (2048, 2048, 2048), (8192, 4096, 4096), (1024, 4096, 4096), (4096, 1024, 4096)]
     if len(sys.argv) > 1:
         shapes = [tuple(int(v) for v in a.split("x")) for a in sys.argv[1:]]
@@ -47,9 +54,14 @@ def main():
         ref = {}   # per bf16x3 arm: the arms differ by their own rounding (each a few 1e-6 from float64 at K = 8192)
         res = {}
         rounds = int(os.environ.get("GEMM_ROUNDS", "5"))
-        for _ in range(6):          # pre-roll: the first milliseconds after an idle gap run at ramping clocks (the med 126 / max 150
+        for _ in range(int(os.environ.get("GEMM_PREROLL", "6"))):          # pre-roll (GEMM_PREROLL=1500: a second of 4096^3 products, where 6 calls leave the first ROUND cold): the first milliseconds after an idle gap run at ramping clocks (the med 126 / max 150
             nd.matmul(A, B)         # spread of round 2's log was the first round of each shape, taken cold)
-        for rnd in range(rounds):
+        # round -1 checks every arm's result and is not timed: the read-back and the comparison leave the GPU idle, and the
+        # timing that followed one ran at ramping clocks (the low first round of every arm in the logs up to gemm_bf16x3_layout)
+        for rnd in range(-1, rounds):
+            if rnd == 0:
+                for _ in range(int(os.environ.get("GEMM_PREROLL", "6"))):
+                    nd.matmul(A, B)
             for cfg in CFGS:
                 if os.environ.get("GEMM_NBUF_AB"):
                     opt("gemm_nbuf", 2 + (cfg // 1000) % 10)
@@ -60,6 +72,10 @@ def main():
                 if os.environ.get("GEMM_BF16X3_LOOP_AB"):
                     opt("gemm_bf16x3", 2)
                     opt("gemm_bf16x3_loop", (cfg // 1000000) % 10)
+                if os.environ.get("GEMM_BF16X3_LAYOUT_AB"):
+                    opt("gemm_bf16x3", 2)
+                    opt("gemm_bf16x3_planes", ((cfg // 10000000) % 10) >> 1)
+                    opt("gemm_bf16x3_band", 0 if (cfg // 10000000) % 2 else 1)
                 if cfg % 100 == 99 or cfg == -1:
                     opt("gemm_cfg", -1)      # the library's own choice
                 else:
@@ -76,16 +92,21 @@ def main():
                     lib.event_record(e1)
                     lib.event_elapsed_ms(e0, e1, C.byref(ms))
                     tf = REPS * 2.0 * M * N * K / (ms.value * 1e-3) / 1e12
-                    res.setdefault((cfg, tag), []).append(tf)
-                    if rnd == 0:
+                    if rnd >= 0:
+                        res.setdefault((cfg, tag), []).append(tf)
+                    else:
                         h = out.get()
                         arm = (cfg // 100000) % 10 if os.environ.get("GEMM_BF16X3_AB") else 0
                         r = ref.setdefault(arm, h)
                         assert np.abs(h - r).max() / np.abs(r).max() < 5e-6, (cfg, tag)
-        print(f"M={M} K={K} N={N}")
+        print(f"M={M} K={K} N={N}" + (" (ms per product, split passes included: 2 M N K / TF / 1e9)" if os.environ.get("GEMM_BF16X3_LAYOUT_AB") else ""))
         for cfg, name in CFGS.items():
+            if os.environ.get("GEMM_BF16X3_LAYOUT_AB"):   # every round, in order: a cold first round shows as such
+                print("   %-22s rounds " % name + "  ".join("%s %s" % (t, " ".join("%.1f" % v for v in res[(cfg, t)])) for t in ("NN", "NT", "TN")))
             print("   %-22s " % name + "  ".join("%s med %6.1f min %6.1f max %6.1f TF" % (t, sorted(res[(cfg, t)])[len(res[(cfg, t)]) // 2], min(res[(cfg, t)]), max(res[(cfg, t)])) for t in (("NN", "NT", "TN", "TT") if os.environ.get("GEMM_TT") else ("NN", "NT", "TN"))))
     opt("gemm_cfg", -1); opt("gemm_glds", 1); opt("gemm_nbuf", 0); opt("gemm_peel", 1); opt("gemm_bf16x3", 1); opt("gemm_bf16x3_loop", 1)
+    for name, v in layout_defaults.items():
+        opt(name, v)
 
 
 if __name__ == "__main__":
