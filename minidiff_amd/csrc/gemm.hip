@@ -89,36 +89,150 @@ struct GemmArgs {
   const unsigned *run_if_set;
 };
 
-// Tile loaders for a ROWS x BK operand tile, NT threads, 16 B per thread per pass.
+// ---- what the MFMA kernels share (f32 and f64, register-staged and direct-to-LDS) ---------------------------------------------------
+// The pieces that stand in a kernel's own body (its tile, the accumulators, the k-tile driver and boundary, the write-out) are MACROS:
+// as inlined functions they left the source equivalent but changed what the compiler made of nearly every kernel — the scalar prologue
+// came out in another order, and with it the register assignment of the k loop — and this file's speed hangs on that (see SPLITK below:
+// "instruction-for-instruction the same but with another register assignment", -2.4 %). Text expanded in place compiles to the code the
+// copies it replaces compiled to. What runs INSIDE a k-tile lambda (md_mfma_slots, the DMA callables) and the tile loaders are functions:
+// those changed nothing (scripts/isa_diff.py, profiles/gemm_shared_helpers_isa.txt).
+template <int V> struct MdInt { static constexpr int value = V; };
+
+// XCD-aware tile order: ids b, b+8, b+16.. share an XCD -> give them neighbours. Declares `bid`.
+#define MD_XCD_BID(bid, nblk)                                          \
+  int bid = blockIdx.x;                                                \
+  if (((nblk) & 7) == 0) bid = (bid & 7) * ((nblk) >> 3) + (bid >> 3);
+// The block's tile of the f32 kernels: the XCD order, then the band numbering (GemmArgs::super_h). Declares `tm`, `tn`.
+// Bands: tiles are numbered column-major inside bands of super_h tile rows, so that the nblk/8 consecutive
+// ids of one XCD form a compact block (8 x 8 tiles at 4096^2 instead of 2 x 32): fewer distinct
+// A/B panels per XCD L2, i.e. less L2 <- fabric traffic for the same work (speed-neutral: the
+// kernel is not fabric-bound)
+#define MD_BLOCK_TILE(g, tm, tn)                                                                              \
+  const int nblk = (g).tiles_m * (g).tiles_n;                                                                 \
+  MD_XCD_BID(bid, nblk)                                                                                       \
+  int tm, tn;                                                                                                 \
+  if ((g).super_h > 1) {                                                                                      \
+    const int band = bid / ((g).super_h * (g).tiles_n), within = bid - band * ((g).super_h * (g).tiles_n);    \
+    const int hgt = (band + 1) * (g).super_h <= (g).tiles_m ? (g).super_h : (g).tiles_m - band * (g).super_h; \
+    tn = within / hgt;                                                                                        \
+    tm = band * (g).super_h + within - tn * hgt;                                                              \
+  } else {                                                                                                    \
+    tm = bid / (g).tiles_n;                                                                                   \
+    tn = bid - tm * (g).tiles_n;                                                                              \
+  }
+// acc[WTM][WTN] of vectors of R elements = 0
+#define MD_ZERO_ACC(acc, WTM, WTN, R)                                   \
+  _Pragma("unroll") for (int i = 0; i < (WTM); ++i)                     \
+    _Pragma("unroll") for (int j = 0; j < (WTN); ++j)                   \
+      _Pragma("unroll") for (int r = 0; r < (R); ++r) acc[i][j][r] = 0;
+// C write-out of a wave's WTM x WTN accumulator tiles (the kernel's constants); GUARD (compile-time): the tile may reach past C (edge
+// and ragged kernels).
+// C/D layout of the 32x32 f32 accumulator: col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5)
+#define MD_STORE_C32(GUARD, acc, C, g, m0, n0, wm, wn, l32, h)                                           \
+  _Pragma("unroll") for (int i = 0; i < WTM; ++i)                                                        \
+    _Pragma("unroll") for (int j = 0; j < WTN; ++j) {                                                    \
+      const int64_t col = n0 + wn * (WTN * 32) + j * 32 + l32;                                           \
+      _Pragma("unroll") for (int r = 0; r < 16; ++r) {                                                   \
+        const int64_t row = m0 + wm * (WTM * 32) + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;              \
+        if (!(GUARD) || (row < (g).M && col < (g).N)) C[row * (g).c_ms + col * (g).c_ns] = acc[i][j][r]; \
+      }                                                                                                  \
+    }
+// C/D of the f64 16x16 tile: col = lane&15, row = (lane>>4) + 4*r
+#define MD_STORE_C64(GUARD, acc, C, g, m0, n0, wm, wn, l16, h)                                           \
+  _Pragma("unroll") for (int i = 0; i < WTM; ++i)                                                        \
+    _Pragma("unroll") for (int j = 0; j < WTN; ++j) {                                                    \
+      const int64_t col = n0 + wn * (WTN * 16) + j * 16 + l16;                                           \
+      _Pragma("unroll") for (int r = 0; r < 4; ++r) {                                                    \
+        const int64_t row = m0 + wm * (WTM * 16) + i * 16 + h + 4 * r;                                   \
+        if (!(GUARD) || (row < (g).M && col < (g).N)) C[row * (g).c_ms + col * (g).c_ns] = acc[i][j][r]; \
+      }                                                                                                  \
+    }
+// The k-tile driver of the direct-to-LDS kernels. ktile(MdInt<CUR>, kn) multiplies the tile in buffer CUR while the DMAs of k-tile
+// kn go out; the loop is unrolled by NBUF so that the buffer is fixed at compile time (see k_gemm_f32_tn_glds). Three buffers:
+// tile T is computed out of buffer T % 3 while the DMAs of tile T + 2 go out (past the end: a discarded re-read of the last tile)
+#define MD_KTILE_ROTATE(NBUF, nk, ktile)                \
+  int64_t kt = 0;                                       \
+  if constexpr ((NBUF) == 2) {                          \
+    for (; kt + 1 < nk; kt += 2) {                      \
+      ktile(MdInt<0>{}, kt + 1);                        \
+      ktile(MdInt<1>{}, kt + 2 < nk ? kt + 2 : nk - 1); \
+    }                                                   \
+    if (kt < nk) ktile(MdInt<0>{}, nk - 1);             \
+  } else {                                              \
+    for (; kt + 2 < nk; kt += 3) {                      \
+      ktile(MdInt<0>{}, kt + 2);                        \
+      ktile(MdInt<1>{}, kt + 3 < nk ? kt + 3 : nk - 1); \
+      ktile(MdInt<2>{}, kt + 4 < nk ? kt + 4 : nk - 1); \
+    }                                                   \
+    if (kt < nk) ktile(MdInt<0>{}, nk - 1);             \
+    if (kt + 1 < nk) ktile(MdInt<1>{}, nk - 1);         \
+  }
+// Publishes the tile computed next. Two buffers: __syncthreads(), which drains the DMAs in flight (vmcnt(0)). Three: a counted wait —
+// this wave's DMAs of the tile computed NEXT are done (issued a whole k-tile ago; in the prologue: tile 0 landed), the PIECES it issued
+// last (the tile after that) may still fly; the barrier then publishes every wave's share of the next tile and frees this tile's buffer.
+// The s_waitcnt immediate of gfx9: vmcnt in bits 3:0 and 15:14; expcnt (7) and lgkmcnt (15) at their maxima, i.e. not waited for.
+constexpr int md_vmcnt_imm(int n) { return (n & 0xF) | ((n >> 4) << 14) | (7 << 4) | (15 << 8); }
+#define MD_PUBLISH_TILE(NBUF, PIECES)                                                                            \
+  if constexpr ((NBUF) == 2) {                                                                                   \
+    __syncthreads();                                                                                             \
+  } else {                                                                                                       \
+    constexpr int NW8 = (PIECES);   /* (a local, as the copies had: without it four kernels' code changed) */    \
+    __builtin_amdgcn_s_waitcnt(md_vmcnt_imm(NW8));                                                               \
+    __builtin_amdgcn_s_barrier();                                                                                \
+  }
+// the buffer the DMAs go to while buffer CUR is multiplied: the one behind CUR in the rotation (the other one of two)
+constexpr int md_dma_buf(int nbuf, int cur) { return (cur + nbuf - 1) % nbuf; }
+// Scheduling slots behind the MPS MFMAs of step `t` of a fragment pair: one MFMA each, behind it a fragment read of the next pair (if
+// there is one: `more_reads`; NRD reads per pair) and a DMA piece (n_dma issued in this step). Tiles with >= 8 MFMAs per step: a read
+// slot behind EVERY MFMA (measured best there); smaller ones: the next pair's reads go behind the FIRST MFMAs of this pair, one each
+// (with a read slot behind every MFMA of the pair the scheduler parked the reads at its end, right in front of the wait for them)
+template <int NRD, int MPS> __device__ __forceinline__ void md_mfma_slots(bool more_reads, int t, int n_dma) {
+  constexpr bool RD_EVERY = MPS >= 8;
+  const int rd_slots = RD_EVERY ? MPS : more_reads ? (NRD - t * MPS < 0 ? 0 : (NRD - t * MPS > MPS ? MPS : NRD - t * MPS)) : 0;
+#pragma unroll
+  for (int m = 0; m < MPS; ++m) {
+    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+    if (m < rd_slots) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+    if (m < n_dma) __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);
+  }
+}
+
+// Tile loaders for a ROWS x BK operand tile of T (float / double), NT threads, 16 B (V elements) per thread per pass.
 // KC = the operand's k axis is the contiguous one in memory (row-major A, or B given as Bt).
-template <int ROWS, int BK, int NT, bool KC, bool EDGE>
-__device__ __forceinline__ void load_tile(const float *__restrict__ P, int64_t rs, int64_t ks, int64_t row0, int64_t k0,
-                                          int64_t rows, int64_t K, f32x4 (&r)[ROWS * BK / (4 * NT)], bool vec_ok = true) {
-  constexpr int PASSES = ROWS * BK / (4 * NT);
-  constexpr int TPR = BK / 4;            // KC: threads per row
+template <class T> struct MdVec16 {
+  static constexpr int N = 16 / sizeof(T);
+  typedef T type __attribute__((ext_vector_type(N)));
+};
+template <int ROWS, int BK, int NT, bool KC, bool EDGE, class T>
+__device__ __forceinline__ void load_tile(const T *__restrict__ P, int64_t rs, int64_t ks, int64_t row0, int64_t k0, int64_t rows, int64_t K,
+                                          typename MdVec16<T>::type (&r)[ROWS * BK / (MdVec16<T>::N * NT)], bool vec_ok = true) {
+  typedef typename MdVec16<T>::type vec;
+  constexpr int V = MdVec16<T>::N;
+  constexpr int PASSES = ROWS * BK / (V * NT);
+  constexpr int TPR = BK / V;            // KC: threads per row
   constexpr int RPP = NT / TPR;          // KC: rows per pass
-  constexpr int TPK = ROWS / 4;          // !KC: threads per k-row
+  constexpr int TPK = ROWS / V;          // !KC: threads per k-row
   constexpr int KPP = NT / TPK;          // !KC: k-rows per pass
   const int t = threadIdx.x;
 #pragma unroll
   for (int i = 0; i < PASSES; ++i) {
     int row, k;
-    if constexpr (KC) { row = t / TPR + RPP * i; k = (t % TPR) * 4; }
-    else { k = t / TPK + KPP * i; row = (t % TPK) * 4; }
+    if constexpr (KC) { row = t / TPR + RPP * i; k = (t % TPR) * V; }
+    else { k = t / TPK + KPP * i; row = (t % TPK) * V; }
     if constexpr (!EDGE) {
-      r[i] = *reinterpret_cast<const f32x4 *>(P + (row0 + row) * rs + (k0 + k) * ks);
+      r[i] = *reinterpret_cast<const vec *>(P + (row0 + row) * rs + (k0 + k) * ks);
     } else {
       // ragged M/N/K: a vector that lies wholly inside the operand is still ONE 16-B load (only the
       // last tile row/column and the K tail take the per-element path); unaligned operands always do
       const int64_t rr0 = row0 + row, kk0 = k0 + k;
-      const bool inside = KC ? (rr0 < rows && kk0 + 3 < K) : (kk0 < K && rr0 + 3 < rows);
+      const bool inside = KC ? (rr0 < rows && kk0 + (V - 1) < K) : (kk0 < K && rr0 + (V - 1) < rows);
       if (vec_ok && inside) {
-        r[i] = *reinterpret_cast<const f32x4 *>(P + rr0 * rs + kk0 * ks);
+        r[i] = *reinterpret_cast<const vec *>(P + rr0 * rs + kk0 * ks);
       } else {
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
+        for (int j = 0; j < V; ++j) {
           const int64_t rr = rr0 + (KC ? 0 : j), kk = kk0 + (KC ? j : 0);
-          r[i][j] = (rr < rows && kk < K) ? P[rr * rs + kk * ks] : 0.0f;
+          r[i][j] = (rr < rows && kk < K) ? P[rr * rs + kk * ks] : (T)0;
         }
       }
     }
@@ -134,20 +248,28 @@ __device__ __forceinline__ void load_tile_pass(const float *__restrict__ P, int6
   else { k = t / TPK + KPP * i; row = (t % TPK) * 4; }
   r[i] = *reinterpret_cast<const f32x4 *>(P + (row0 + row) * rs + (k0 + k) * ks);
 }
-template <int ROWS, int BK, int NT, bool KC>
-__device__ __forceinline__ void store_tile(float (*S)[ROWS + LDP], const f32x4 (&r)[ROWS * BK / (4 * NT)]) {
-  constexpr int PASSES = ROWS * BK / (4 * NT);
-  constexpr int TPR = BK / 4, RPP = NT / TPR, TPK = ROWS / 4, KPP = NT / TPK;
+// the staged tile into its k-major LDS image; PAD = the image's row pad in elements (LDP / LDP64)
+template <int ROWS, int BK, int NT, bool KC, int PAD, class T>
+__device__ __forceinline__ void store_tile(T (*S)[ROWS + PAD], const typename MdVec16<T>::type (&r)[ROWS * BK / (MdVec16<T>::N * NT)]) {
+  typedef typename MdVec16<T>::type vec;
+  constexpr int V = MdVec16<T>::N;
+  constexpr int PASSES = ROWS * BK / (V * NT);
+  constexpr int TPR = BK / V, RPP = NT / TPR, TPK = ROWS / V, KPP = NT / TPK;
   const int t = threadIdx.x;
 #pragma unroll
   for (int i = 0; i < PASSES; ++i) {
     if constexpr (KC) {
-      const int row = t / TPR + RPP * i, k = (t % TPR) * 4;
+      const int row = t / TPR + RPP * i, k = (t % TPR) * V;
+      if constexpr (V == 2) {   // (written out: as a loop of two it changed the f64 kernels' code)
+        S[k][row] = r[i][0];
+        S[k + 1][row] = r[i][1];
+      } else {
 #pragma unroll
-      for (int j = 0; j < 4; ++j) S[k + j][row] = r[i][j];
+        for (int j = 0; j < V; ++j) S[k + j][row] = r[i][j];
+      }
     } else {
-      const int k = t / TPK + KPP * i, row = (t % TPK) * 4;
-      *reinterpret_cast<f32x4 *>(&S[k][row]) = r[i];
+      const int k = t / TPK + KPP * i, row = (t % TPK) * V;
+      *reinterpret_cast<vec *>(&S[k][row]) = r[i];
     }
   }
 }
@@ -261,24 +383,7 @@ __global__ void __launch_bounds__(64 * WM * WN, (EPI != 0 && BM * BN <= 256 * 12
   __shared__ float Bs[2][BK][BN + LDP];
   if (g.run_if_set && *g.run_if_set == 0) return;
 
-  // XCD-aware tile order: ids b, b+8, b+16.. share an XCD -> give them neighbours
-  const int nblk = g.tiles_m * g.tiles_n;
-  int bid = blockIdx.x;
-  if ((nblk & 7) == 0) bid = (bid & 7) * (nblk >> 3) + (bid >> 3);
-  int tm, tn;
-  if (g.super_h > 1) {
-    // tiles are numbered column-major inside bands of super_h tile rows, so that the nblk/8 consecutive
-    // ids of one XCD form a compact block (8 x 8 tiles at 4096^2 instead of 2 x 32): fewer distinct
-    // A/B panels per XCD L2, i.e. less L2 <- fabric traffic for the same work (speed-neutral: the
-    // kernel is not fabric-bound)
-    const int band = bid / (g.super_h * g.tiles_n), within = bid - band * (g.super_h * g.tiles_n);
-    const int hgt = (band + 1) * g.super_h <= g.tiles_m ? g.super_h : g.tiles_m - band * g.super_h;
-    tn = within / hgt;
-    tm = band * g.super_h + within - tn * hgt;
-  } else {
-    tm = bid / g.tiles_n;
-    tn = bid - tm * g.tiles_n;
-  }
+  MD_BLOCK_TILE(g, tm, tn)
   const int64_t m0 = (int64_t)tm * BM, n0 = (int64_t)tn * BN;
   const int64_t bz = blockIdx.z;
   const float *A = g.A + bz * g.a_bs;
@@ -300,12 +405,7 @@ __global__ void __launch_bounds__(64 * WM * WN, (EPI != 0 && BM * BN <= 256 * 12
   if (g.stamp) { st_c = __builtin_amdgcn_s_memtime(); st_r = __builtin_amdgcn_s_memrealtime(); }
 
   f32x16 acc[WTM][WTN];
-#pragma unroll
-  for (int i = 0; i < WTM; ++i)
-#pragma unroll
-    for (int j = 0; j < WTN; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
+  MD_ZERO_ACC(acc, WTM, WTN, 16)
 
   f32x4 ra[BM * BK / (4 * NT)], rb[BN * BK / (4 * NT)];
   const int64_t nk = (Kl + BK - 1) / BK;
@@ -317,8 +417,8 @@ __global__ void __launch_bounds__(64 * WM * WN, (EPI != 0 && BM * BN <= 256 * 12
   const bool vec_ok = g.vec_ok != 0;
   load_tile<BM, BK, NT, A_KC, EDGE>(A, g.a_ms, g.a_ks, m0, 0, g.M, Kl, ra, vec_ok);
   load_tile<BN, BK, NT, B_KC, EDGE>(B, g.b_ns, g.b_ks, n0, 0, g.N, Kl, rb, vec_ok);
-  store_tile<BM, BK, NT, A_KC>(As[0], ra);
-  store_tile<BN, BK, NT, B_KC>(Bs[0], rb);
+  store_tile<BM, BK, NT, A_KC, LDP>(As[0], ra);
+  store_tile<BN, BK, NT, B_KC, LDP>(Bs[0], rb);
   if (nk > 1) {
     load_tile<BM, BK, NT, A_KC, EDGE>(A, g.a_ms, g.a_ks, m0, BK, g.M, Kl, ra, vec_ok);
     load_tile<BN, BK, NT, B_KC, EDGE>(B, g.b_ns, g.b_ks, n0, BK, g.N, Kl, rb, vec_ok);
@@ -351,8 +451,8 @@ __global__ void __launch_bounds__(64 * WM * WN, (EPI != 0 && BM * BN <= 256 * 12
         for (int j = 0; j < WTN; ++j) fb[c ^ 1][j] = Bs[cur][kk + 2 + h][wn * (WTN * 32) + j * 32 + l32];
       }
       if constexpr (SCHED == 0) {
-        if (kk == 0 && more) store_tile<BM, BK, NT, A_KC>(As[cur ^ 1], ra);
-        if (kk == 2 && more) store_tile<BN, BK, NT, B_KC>(Bs[cur ^ 1], rb);
+        if (kk == 0 && more) store_tile<BM, BK, NT, A_KC, LDP>(As[cur ^ 1], ra);
+        if (kk == 2 && more) store_tile<BN, BK, NT, B_KC, LDP>(Bs[cur ^ 1], rb);
         if (kk == 4 && more2) {
           load_tile<BM, BK, NT, A_KC, EDGE>(A, g.a_ms, g.a_ks, m0, (kt + 2) * BK, g.M, Kl, ra, vec_ok);
           load_tile<BN, BK, NT, B_KC, EDGE>(B, g.b_ns, g.b_ks, n0, (kt + 2) * BK, g.N, Kl, rb, vec_ok);
@@ -368,8 +468,8 @@ __global__ void __launch_bounds__(64 * WM * WN, (EPI != 0 && BM * BN <= 256 * 12
         // branch-free body (the staging of the last two tiles is redundant, never wrong: the other
         // LDS buffer is not read again, and the tile index is clamped) so that the whole k-tile is
         // ONE scheduling region, and every MFMA is followed by a slice of the step's memory work
-        if (kk == 0) store_tile<BM, BK, NT, A_KC>(As[cur ^ 1], ra);
-        if (kk == 2) store_tile<BN, BK, NT, B_KC>(Bs[cur ^ 1], rb);
+        if (kk == 0) store_tile<BM, BK, NT, A_KC, LDP>(As[cur ^ 1], ra);
+        if (kk == 2) store_tile<BN, BK, NT, B_KC, LDP>(Bs[cur ^ 1], rb);
         // small tiles (2-4 MFMAs per step): the refill of the staging registers starts the step after they were written to LDS,
         // one 16-B load per step — A's passes from step 1, then B's — instead of all of them in step 4: a load issued in step 4
         // has 4 steps x 2 MFMAs (~1000 cycles at two waves per SIMD) to land before its LDS store, which the memory latency
@@ -420,18 +520,7 @@ __global__ void __launch_bounds__(64 * WM * WN, (EPI != 0 && BM * BN <= 256 * 12
     md_epi_bias_relu<BM, BN, WM, WN, 1>(acc, g, m0, n0, reinterpret_cast<uint32_t *>(&As[0][0][0]), &Bs[0][0][0]);
     return;
   }
-  // C/D layout of the 32x32 accumulator: col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5)
-#pragma unroll
-  for (int i = 0; i < WTM; ++i)
-#pragma unroll
-    for (int j = 0; j < WTN; ++j) {
-      const int64_t col = n0 + wn * (WTN * 32) + j * 32 + l32;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int64_t row = m0 + wm * (WTM * 32) + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-        if (!EDGE || (row < g.M && col < g.N)) C[row * g.c_ms + col * g.c_ns] = acc[i][j][r];
-      }
-    }
+  MD_STORE_C32(EDGE, acc, C, g, m0, n0, wm, wn, l32, h)
 }
 
 // ---- TN products (both operands row-contiguous along the tile's rows) staged global -> LDS directly ------------------
@@ -501,8 +590,6 @@ __device__ __forceinline__ void glds_tile_pass_u(const float *wbase, int64_t ste
   }
 }
 
-template <int V> struct MdInt { static constexpr int value = V; };
-
 // RAGGED: 0 whole tiles | 1 any ragged size (zero-filled lanes, 64-bit lane addresses) | 2 ragged M / N with K % BK == 0 (predicated lanes,
 // scalar-base addresses: the fast form)
 // (NBUF = 3: three LDS buffers, DMA two k-tiles ahead, counted vmcnt at the boundary — see k_gemm_f32_kc_glds)
@@ -524,19 +611,7 @@ __global__ void __launch_bounds__(64 * WM * WN) k_gemm_f32_tn_glds(GemmArgs g) {
   __shared__ __attribute__((aligned(16))) float B2[NBUF == 3 ? BK : 1][BN];
   if (g.run_if_set && *g.run_if_set == 0) return;
 
-  const int nblk = g.tiles_m * g.tiles_n;
-  int bid = blockIdx.x;
-  if ((nblk & 7) == 0) bid = (bid & 7) * (nblk >> 3) + (bid >> 3);   // XCD-aware tile order, as in k_gemm_f32_mfma
-  int tm, tn;
-  if (g.super_h > 1) {
-    const int band = bid / (g.super_h * g.tiles_n), within = bid - band * (g.super_h * g.tiles_n);
-    const int hgt = (band + 1) * g.super_h <= g.tiles_m ? g.super_h : g.tiles_m - band * g.super_h;
-    tn = within / hgt;
-    tm = band * g.super_h + within - tn * hgt;
-  } else {
-    tm = bid / g.tiles_n;
-    tn = bid - tm * g.tiles_n;
-  }
+  MD_BLOCK_TILE(g, tm, tn)
   const int64_t m0 = (int64_t)tm * BM, n0 = (int64_t)tn * BN;
   const int64_t bz = blockIdx.z;
   const float *A = g.A + bz * g.a_bs;
@@ -548,12 +623,7 @@ __global__ void __launch_bounds__(64 * WM * WN) k_gemm_f32_tn_glds(GemmArgs g) {
   const int am = wm * (WTM * 32) + l32, bn = wn * (WTN * 32) + l32;
 
   f32x16 acc[WTM][WTN];
-#pragma unroll
-  for (int i = 0; i < WTM; ++i)
-#pragma unroll
-    for (int j = 0; j < WTN; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
+  MD_ZERO_ACC(acc, WTM, WTN, 16)
 
   const int64_t nk = RAGGED == 1 ? (g.K + BK - 1) / BK : g.K / BK;   // (forms 0 and 2: whole k-tiles only, the launcher checks)
 #pragma unroll
@@ -576,13 +646,7 @@ __global__ void __launch_bounds__(64 * WM * WN) k_gemm_f32_tn_glds(GemmArgs g) {
     pra = m0 + (int64_t)((threadIdx.x & 63) % (BM / 4 > 64 ? 64 : BM / 4)) * 4 < g.M;
     prb = n0 + (int64_t)((threadIdx.x & 63) % (BN / 4 > 64 ? 64 : BN / 4)) * 4 < g.N;
   }
-  if constexpr (NBUF == 3) {
-    constexpr int NW8 = PA + PB;
-    __builtin_amdgcn_s_waitcnt((NW8 & 0xF) | ((NW8 >> 4) << 14) | (7 << 4) | (15 << 8));   // tile 0 landed; tile 1 may still fly
-    __builtin_amdgcn_s_barrier();
-  } else {
-    __syncthreads();
-  }
+  MD_PUBLISH_TILE(NBUF, PA + PB)   // tile 0 landed; with three buffers tile 1 may still fly
 
   // fragments for TWO steps (4 k) per LDS instruction: rows 4p+h and 4p+2+h of the [k][row] image lie 2*ROWS floats apart, a
   // multiple of 64 dwords, so the two loads of a lane fuse into one ds_read2st64_b32 — half the LDS read instructions; MFMA t of
@@ -590,18 +654,32 @@ __global__ void __launch_bounds__(64 * WM * WN) k_gemm_f32_tn_glds(GemmArgs g) {
   typedef float f32x2 __attribute__((ext_vector_type(2)));
   constexpr int NPR = BK / 4;
   f32x2 fa[2][WTM], fb[2][WTN];
+#define MD_TN_BUF(X, BUF) ((BUF) == 0 ? X##0 : (BUF) == 1 ? X##1 : X##2)   /* buffer BUF (compile-time) of operand X */
 #define MD_TN_READ(BUF, p, c)                                                                                          \
   {                                                                                                                    \
     _Pragma("unroll") for (int i = 0; i < WTM; ++i) {                                                                  \
-      fa[c][i][0] = ((BUF) == 0 ? A0 : (BUF) == 1 ? A1 : A2)[4 * (p) + h][am + i * 32];                                                       \
-      fa[c][i][1] = ((BUF) == 0 ? A0 : (BUF) == 1 ? A1 : A2)[4 * (p) + 2 + h][am + i * 32];                                                   \
+      fa[c][i][0] = MD_TN_BUF(A, BUF)[4 * (p) + h][am + i * 32];                                                       \
+      fa[c][i][1] = MD_TN_BUF(A, BUF)[4 * (p) + 2 + h][am + i * 32];                                                   \
     }                                                                                                                  \
     _Pragma("unroll") for (int q = 0; q < WTN; ++q) {                                                                  \
-      fb[c][q][0] = ((BUF) == 0 ? B0 : (BUF) == 1 ? B1 : B2)[4 * (p) + h][bn + q * 32];                                                       \
-      fb[c][q][1] = ((BUF) == 0 ? B0 : (BUF) == 1 ? B1 : B2)[4 * (p) + 2 + h][bn + q * 32];                                                   \
+      fb[c][q][0] = MD_TN_BUF(B, BUF)[4 * (p) + h][bn + q * 32];                                                       \
+      fb[c][q][1] = MD_TN_BUF(B, BUF)[4 * (p) + 2 + h][bn + q * 32];                                                   \
     }                                                                                                                  \
   }
   MD_TN_READ(0, 0, 0)
+  // DMA piece pi of k-tile kn into buffer DST (compile-time), per operand: the addressing form of the RAGGED variant
+  auto dma_a = [&](auto dstc, int64_t kn, int pi) __attribute__((always_inline)) {
+    float *const S = &MD_TN_BUF(A, decltype(dstc)::value)[0][0];
+    if constexpr (RAGGED == 1) glds_tile_pass<BM, BK, NT, true>(A, g.a_ks, m0, kn * BK, S, pi, g.M, g.K, g.zero);
+    else if constexpr (RAGGED == 2) glds_tile_pass_u<BM, BK, NT, true>(wa, sa, kn * BK * g.a_ks, S, pi, la, pra);
+    else glds_tile_pass_u<BM, BK, NT>(wa, sa, kn * BK * g.a_ks, S, pi, la);
+  };
+  auto dma_b = [&](auto dstc, int64_t kn, int pi) __attribute__((always_inline)) {
+    float *const S = &MD_TN_BUF(B, decltype(dstc)::value)[0][0];
+    if constexpr (RAGGED == 1) glds_tile_pass<BN, BK, NT, true>(B, g.b_ks, n0, kn * BK, S, pi, g.N, g.K, g.zero);
+    else if constexpr (RAGGED == 2) glds_tile_pass_u<BN, BK, NT, true>(wb, sb, kn * BK * g.b_ks, S, pi, lb, prb);
+    else glds_tile_pass_u<BN, BK, NT>(wb, sb, kn * BK * g.b_ks, S, pi, lb);
+  };
   auto ktile = [&](auto curc, int64_t kn) {
     constexpr int CUR = decltype(curc)::value;
 #pragma unroll
@@ -616,14 +694,10 @@ __global__ void __launch_bounds__(64 * WM * WN) k_gemm_f32_tn_glds(GemmArgs g) {
         for (int q = 0; q < PPS; ++q) {
           const int pi = sidx * PPS + q;
           if (pi < PA) {
-            if constexpr (RAGGED == 1) glds_tile_pass<BM, BK, NT, true>(A, g.a_ks, m0, kn * BK, (NBUF == 2 ? (CUR ? &A0[0][0] : &A1[0][0]) : (CUR == 0 ? &A2[0][0] : CUR == 1 ? &A0[0][0] : &A1[0][0])), pi, g.M, g.K, g.zero);
-            else if constexpr (RAGGED == 2) glds_tile_pass_u<BM, BK, NT, true>(wa, sa, kn * BK * g.a_ks, (NBUF == 2 ? (CUR ? &A0[0][0] : &A1[0][0]) : (CUR == 0 ? &A2[0][0] : CUR == 1 ? &A0[0][0] : &A1[0][0])), pi, la, pra);
-            else glds_tile_pass_u<BM, BK, NT>(wa, sa, kn * BK * g.a_ks, (NBUF == 2 ? (CUR ? &A0[0][0] : &A1[0][0]) : (CUR == 0 ? &A2[0][0] : CUR == 1 ? &A0[0][0] : &A1[0][0])), pi, la);
+            dma_a(MdInt<md_dma_buf(NBUF, CUR)>{}, kn, pi);
             ++n_dma;
           } else if (pi < PA + PB) {
-            if constexpr (RAGGED == 1) glds_tile_pass<BN, BK, NT, true>(B, g.b_ks, n0, kn * BK, (NBUF == 2 ? (CUR ? &B0[0][0] : &B1[0][0]) : (CUR == 0 ? &B2[0][0] : CUR == 1 ? &B0[0][0] : &B1[0][0])), pi - PA, g.N, g.K, g.zero);
-            else if constexpr (RAGGED == 2) glds_tile_pass_u<BN, BK, NT, true>(wb, sb, kn * BK * g.b_ks, (NBUF == 2 ? (CUR ? &B0[0][0] : &B1[0][0]) : (CUR == 0 ? &B2[0][0] : CUR == 1 ? &B0[0][0] : &B1[0][0])), pi - PA, lb, prb);
-            else glds_tile_pass_u<BN, BK, NT>(wb, sb, kn * BK * g.b_ks, (NBUF == 2 ? (CUR ? &B0[0][0] : &B1[0][0]) : (CUR == 0 ? &B2[0][0] : CUR == 1 ? &B0[0][0] : &B1[0][0])), pi - PA, lb);
+            dma_b(MdInt<md_dma_buf(NBUF, CUR)>{}, kn, pi - PA);
             ++n_dma;
           }
         }
@@ -631,55 +705,17 @@ __global__ void __launch_bounds__(64 * WM * WN) k_gemm_f32_tn_glds(GemmArgs g) {
         for (int i = 0; i < WTM; ++i)
 #pragma unroll
           for (int j = 0; j < WTN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[c][i][t], fb[c][j][t], acc[i][j], 0, 0, 0);
-        constexpr int NRD = WTM + WTN, MPS = WTM * WTN;
-        const int rd_slots = MPS >= 8 ? MPS : p + 1 < NPR ? (NRD - t * MPS < 0 ? 0 : (NRD - t * MPS > MPS ? MPS : NRD - t * MPS)) : 0;
-#pragma unroll
-        for (int m = 0; m < MPS; ++m) {
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-          if (m < rd_slots) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-          if (m < n_dma) __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);
-        }
+        md_mfma_slots<WTM + WTN, WTM * WTN>(p + 1 < NPR, t, n_dma);
       }
     }
-    if constexpr (NBUF == 2) {
-      __syncthreads();
-      MD_TN_READ(CUR ^ 1, 0, 0)
-    } else {
-      constexpr int NW8 = PA + PB;   // (counted wait: the tile computed next is complete, the one just issued may still fly)
-      __builtin_amdgcn_s_waitcnt((NW8 & 0xF) | ((NW8 >> 4) << 14) | (7 << 4) | (15 << 8));
-      __builtin_amdgcn_s_barrier();
-      MD_TN_READ((CUR + 1) % 3, 0, 0)
-    }
+    MD_PUBLISH_TILE(NBUF, PA + PB)
+    MD_TN_READ((CUR + 1) % NBUF, 0, 0)
   };
-  int64_t kt = 0;
-  if constexpr (NBUF == 2) {
-    for (; kt + 1 < nk; kt += 2) {
-      ktile(MdInt<0>{}, kt + 1);
-      ktile(MdInt<1>{}, kt + 2 < nk ? kt + 2 : nk - 1);
-    }
-    if (kt < nk) ktile(MdInt<0>{}, nk - 1);
-  } else {
-    for (; kt + 2 < nk; kt += 3) {
-      ktile(MdInt<0>{}, kt + 2);
-      ktile(MdInt<1>{}, kt + 3 < nk ? kt + 3 : nk - 1);
-      ktile(MdInt<2>{}, kt + 4 < nk ? kt + 4 : nk - 1);
-    }
-    if (kt < nk) ktile(MdInt<0>{}, nk - 1);
-    if (kt + 1 < nk) ktile(MdInt<1>{}, nk - 1);
-  }
+  MD_KTILE_ROTATE(NBUF, nk, ktile)
 #undef MD_TN_READ
+#undef MD_TN_BUF
 
-#pragma unroll
-  for (int i = 0; i < WTM; ++i)
-#pragma unroll
-    for (int j = 0; j < WTN; ++j) {
-      const int64_t col = n0 + wn * (WTN * 32) + j * 32 + l32;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int64_t row = m0 + wm * (WTM * 32) + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-        if (RAGGED == 0 || (row < g.M && col < g.N)) C[row * g.c_ms + col * g.c_ns] = acc[i][j][r];
-      }
-    }
+  MD_STORE_C32(RAGGED != 0, acc, C, g, m0, n0, wm, wn, l32, h)
 }
 
 // ---- NN / NT products: the k-contiguous operand(s) direct to LDS as well -------------------------------------------------
@@ -750,19 +786,7 @@ __global__ void __launch_bounds__(64 * WM * WN) k_gemm_f32_kc_glds(GemmArgs g) {
   __shared__ __attribute__((aligned(16))) float B2[NBUF == 3 ? BN * BK : 4];
   if (g.run_if_set && *g.run_if_set == 0) return;
 
-  const int nblk = g.tiles_m * g.tiles_n;
-  int bid = blockIdx.x;
-  if ((nblk & 7) == 0) bid = (bid & 7) * (nblk >> 3) + (bid >> 3);
-  int tm, tn;
-  if (g.super_h > 1) {
-    const int band = bid / (g.super_h * g.tiles_n), within = bid - band * (g.super_h * g.tiles_n);
-    const int hgt = (band + 1) * g.super_h <= g.tiles_m ? g.super_h : g.tiles_m - band * g.super_h;
-    tn = within / hgt;
-    tm = band * g.super_h + within - tn * hgt;
-  } else {
-    tm = bid / g.tiles_n;
-    tn = bid - tm * g.tiles_n;
-  }
+  MD_BLOCK_TILE(g, tm, tn)
   const int64_t m0 = (int64_t)tm * BM, n0 = (int64_t)tn * BN;
   const int64_t bz = blockIdx.z;
   const float *A = g.A + bz * g.a_bs;
@@ -778,12 +802,7 @@ __global__ void __launch_bounds__(64 * WM * WN) k_gemm_f32_kc_glds(GemmArgs g) {
   const int bbase = B_KC ? (brow >> 4) * (KH * 256) + (brow & 15) * 4 + h * 64 : h * 4 * BN + brow;
 
   f32x16 acc[WTM][WTN];
-#pragma unroll
-  for (int i = 0; i < WTM; ++i)
-#pragma unroll
-    for (int j = 0; j < WTN; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
+  MD_ZERO_ACC(acc, WTM, WTN, 16)
 
   const int64_t nk = RAGGED == 1 ? (g.K + BK - 1) / BK : g.K / BK;
   unsigned long long st_c = 0, st_r = 0;   // diagnostic stamps (MDHIP_GEMM_STAMP=1), as in k_gemm_f32_mfma
@@ -817,29 +836,45 @@ __global__ void __launch_bounds__(64 * WM * WN) k_gemm_f32_kc_glds(GemmArgs g) {
     rlb = (int)(g.N - n0 < (1 << 30) ? g.N - n0 : (1 << 30));
     if constexpr (!B_KC) prb = n0 + (int64_t)((threadIdx.x & 63) % (BN / 4 > 64 ? 64 : BN / 4)) * 4 < g.N;
   }
-  if constexpr (NBUF == 3) {
-    constexpr int NW8 = PA + PB;
-    __builtin_amdgcn_s_waitcnt((NW8 & 0xF) | ((NW8 >> 4) << 14) | (7 << 4) | (15 << 8));   // tile 0 landed; tile 1 may still fly
-    __builtin_amdgcn_s_barrier();
-  } else {
-    __syncthreads();
-  }
+  MD_PUBLISH_TILE(NBUF, PA + PB)   // tile 0 landed; with three buffers tile 1 may still fly
 
   f32x4 fa[2][WTM], fb[2][WTN];
   // fragments of k-pair j out of buffer BUF (compile-time) into register set c
+#define MD_KC_BUF(X, BUF) ((BUF) == 0 ? X##0 : (BUF) == 1 ? X##1 : X##2)   /* buffer BUF (compile-time) of operand X */
 #define MD_KC_READ(BUF, j, c)                                                                                                   \
   {                                                                                                                             \
     const int joff = ((j) >> 1) * 256 + (((2 * (j)) & 3) * 64);   /* (a constant once the pair loop is unrolled) */             \
     _Pragma("unroll") for (int i = 0; i < WTM; ++i)                                                                             \
-      fa[c][i] = *reinterpret_cast<const f32x4 *>(((BUF) == 0 ? A0 : (BUF) == 1 ? A1 : A2) + abase + i * (2 * KH * 256) + joff);                       \
+      fa[c][i] = *reinterpret_cast<const f32x4 *>(MD_KC_BUF(A, BUF) + abase + i * (2 * KH * 256) + joff);                       \
     _Pragma("unroll") for (int q = 0; q < WTN; ++q) {                                                                           \
-      if constexpr (B_KC) fb[c][q] = *reinterpret_cast<const f32x4 *>(((BUF) == 0 ? B0 : (BUF) == 1 ? B1 : B2) + bbase + q * (2 * KH * 256) + joff);   \
+      if constexpr (B_KC) fb[c][q] = *reinterpret_cast<const f32x4 *>(MD_KC_BUF(B, BUF) + bbase + q * (2 * KH * 256) + joff);   \
       else {                                                                                                                    \
-        _Pragma("unroll") for (int t = 0; t < 4; ++t) fb[c][q][t] = ((BUF) == 0 ? B0 : (BUF) == 1 ? B1 : B2)[bbase + (8 * (j) + t) * BN + q * 32];     \
+        _Pragma("unroll") for (int t = 0; t < 4; ++t) fb[c][q][t] = MD_KC_BUF(B, BUF)[bbase + (8 * (j) + t) * BN + q * 32];     \
       }                                                                                                                         \
     }                                                                                                                           \
   }
   MD_KC_READ(0, 0, 0)
+  // DMA piece pi of k-tile kn into buffer DST (compile-time), per operand: the addressing form of the RAGGED variant and, for B, of
+  // its image (B_KC: the k-contiguous pieces, else the [k][n] rows of k_gemm_f32_tn_glds)
+  auto dma_a = [&](auto dstc, int64_t kn, int pi) __attribute__((always_inline)) {
+    float *const S = MD_KC_BUF(A, decltype(dstc)::value);
+    if constexpr (RAGGED == 1) glds_kc_pass<BM, BK, NT, true>(A, g.a_ms, m0, kn * BK, S, pi, g.M, g.K, g.zero);
+    else if constexpr (RAGGED == 2) glds_kc_pass_u<BM, BK, NT, true>(wa, sa, kn * BK, S, pi, la, rla);
+    else glds_kc_pass_u<BM, BK, NT>(wa, sa, kn * BK, S, pi, la);
+  };
+  auto dma_b = [&](auto dstc, int64_t kn, int pi) __attribute__((always_inline)) {
+    float *const S = MD_KC_BUF(B, decltype(dstc)::value);
+    if constexpr (RAGGED == 1) {
+      if constexpr (B_KC) glds_kc_pass<BN, BK, NT, true>(B, g.b_ns, n0, kn * BK, S, pi, g.N, g.K, g.zero);
+      else glds_tile_pass<BN, BK, NT, true>(B, g.b_ks, n0, kn * BK, S, pi, g.N, g.K, g.zero);
+    } else if constexpr (RAGGED == 2) {
+      if constexpr (B_KC) glds_kc_pass_u<BN, BK, NT, true>(wb, sb, kn * BK, S, pi, lb, rlb);
+      else glds_tile_pass_u<BN, BK, NT, true>(wb, sb, kn * BK * g.b_ks, S, pi, lb, prb);
+    } else {
+      if constexpr (B_KC) glds_kc_pass_u<BN, BK, NT>(wb, sb, kn * BK, S, pi, lb);
+      else glds_tile_pass_u<BN, BK, NT>(wb, sb, kn * BK * g.b_ks, S, pi, lb);
+    }
+  };
 
   auto ktile = [&](auto curc, int64_t kn) {
     constexpr int CUR = decltype(curc)::value;
@@ -855,21 +890,10 @@ __global__ void __launch_bounds__(64 * WM * WN) k_gemm_f32_kc_glds(GemmArgs g) {
         for (int q = 0; q < PPS; ++q) {
           const int pi = sidx * PPS + q;
           if (pi < PA) {
-            if constexpr (RAGGED == 1) glds_kc_pass<BM, BK, NT, true>(A, g.a_ms, m0, kn * BK, (NBUF == 2 ? (CUR ? A0 : A1) : (CUR == 0 ? A2 : CUR == 1 ? A0 : A1)), pi, g.M, g.K, g.zero);
-            else if constexpr (RAGGED == 2) glds_kc_pass_u<BM, BK, NT, true>(wa, sa, kn * BK, (NBUF == 2 ? (CUR ? A0 : A1) : (CUR == 0 ? A2 : CUR == 1 ? A0 : A1)), pi, la, rla);
-            else glds_kc_pass_u<BM, BK, NT>(wa, sa, kn * BK, (NBUF == 2 ? (CUR ? A0 : A1) : (CUR == 0 ? A2 : CUR == 1 ? A0 : A1)), pi, la);
+            dma_a(MdInt<md_dma_buf(NBUF, CUR)>{}, kn, pi);
             ++n_dma;
           } else if (pi < PA + PB) {
-            if constexpr (RAGGED == 1) {
-              if constexpr (B_KC) glds_kc_pass<BN, BK, NT, true>(B, g.b_ns, n0, kn * BK, (NBUF == 2 ? (CUR ? B0 : B1) : (CUR == 0 ? B2 : CUR == 1 ? B0 : B1)), pi - PA, g.N, g.K, g.zero);
-              else glds_tile_pass<BN, BK, NT, true>(B, g.b_ks, n0, kn * BK, (NBUF == 2 ? (CUR ? B0 : B1) : (CUR == 0 ? B2 : CUR == 1 ? B0 : B1)), pi - PA, g.N, g.K, g.zero);
-            } else if constexpr (RAGGED == 2) {
-              if constexpr (B_KC) glds_kc_pass_u<BN, BK, NT, true>(wb, sb, kn * BK, (NBUF == 2 ? (CUR ? B0 : B1) : (CUR == 0 ? B2 : CUR == 1 ? B0 : B1)), pi - PA, lb, rlb);
-              else glds_tile_pass_u<BN, BK, NT, true>(wb, sb, kn * BK * g.b_ks, (NBUF == 2 ? (CUR ? B0 : B1) : (CUR == 0 ? B2 : CUR == 1 ? B0 : B1)), pi - PA, lb, prb);
-            } else {
-              if constexpr (B_KC) glds_kc_pass_u<BN, BK, NT>(wb, sb, kn * BK, (NBUF == 2 ? (CUR ? B0 : B1) : (CUR == 0 ? B2 : CUR == 1 ? B0 : B1)), pi - PA, lb);
-              else glds_tile_pass_u<BN, BK, NT>(wb, sb, kn * BK * g.b_ks, (NBUF == 2 ? (CUR ? B0 : B1) : (CUR == 0 ? B2 : CUR == 1 ? B0 : B1)), pi - PA, lb);
-            }
+            dma_b(MdInt<md_dma_buf(NBUF, CUR)>{}, kn, pi - PA);
             ++n_dma;
           }
         }
@@ -877,51 +901,15 @@ __global__ void __launch_bounds__(64 * WM * WN) k_gemm_f32_kc_glds(GemmArgs g) {
         for (int i = 0; i < WTM; ++i)
 #pragma unroll
           for (int q = 0; q < WTN; ++q) acc[i][q] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[c][i][t], fb[c][q][t], acc[i][q], 0, 0, 0);
-        // the next pair's fragment reads go behind the FIRST MFMAs of this pair, one each (with a read slot behind every MFMA
-        // of the pair the scheduler parked the reads at its end, right in front of the wait for them)
-        constexpr int NRD = WTM + (B_KC ? WTN : 4 * WTN), MPS = WTM * WTN;
-        // tiles with >= 8 MFMAs per step: a read slot behind EVERY MFMA (measured best there); smaller ones: only behind the
-        // first MFMAs of the pair, one per read
-        constexpr bool RD_EVERY = MPS >= 8;
-        const int rd_slots = RD_EVERY ? MPS : j + 1 < NP ? (NRD - t * MPS < 0 ? 0 : (NRD - t * MPS > MPS ? MPS : NRD - t * MPS)) : 0;
-#pragma unroll
-        for (int m = 0; m < MPS; ++m) {
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-          if (m < rd_slots) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-          if (m < n_dma) __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);
-        }
+        md_mfma_slots<WTM + (B_KC ? WTN : 4 * WTN), WTM * WTN>(j + 1 < NP, t, n_dma);   // (a b32 image of B: four reads per fragment)
       }
     }
-    if constexpr (NBUF == 2) {
-      __syncthreads();
-      MD_KC_READ(CUR ^ 1, 0, 0)
-    } else {
-      // counted wait: this wave's DMAs of the tile computed NEXT are done (issued a whole k-tile ago), the PA + PB it issued in this
-      // tile may still fly; the barrier then publishes every wave's share of the next tile and frees this tile's buffer
-      constexpr int NW8 = PA + PB;
-      __builtin_amdgcn_s_waitcnt((NW8 & 0xF) | ((NW8 >> 4) << 14) | (7 << 4) | (15 << 8));
-      __builtin_amdgcn_s_barrier();
-      MD_KC_READ((CUR + 1) % 3, 0, 0)
-    }
+    MD_PUBLISH_TILE(NBUF, PA + PB)
+    MD_KC_READ((CUR + 1) % NBUF, 0, 0)
   };
-  int64_t kt = 0;
-  if constexpr (NBUF == 2) {
-    for (; kt + 1 < nk; kt += 2) {
-      ktile(MdInt<0>{}, kt + 1);
-      ktile(MdInt<1>{}, kt + 2 < nk ? kt + 2 : nk - 1);
-    }
-    if (kt < nk) ktile(MdInt<0>{}, nk - 1);
-  } else {
-    // tile T is computed out of buffer T % 3 while the DMAs of tile T + 2 go out (past the end: a discarded re-read of the last tile)
-    for (; kt + 2 < nk; kt += 3) {
-      ktile(MdInt<0>{}, kt + 2);
-      ktile(MdInt<1>{}, kt + 3 < nk ? kt + 3 : nk - 1);
-      ktile(MdInt<2>{}, kt + 4 < nk ? kt + 4 : nk - 1);
-    }
-    if (kt < nk) ktile(MdInt<0>{}, nk - 1);
-    if (kt + 1 < nk) ktile(MdInt<1>{}, nk - 1);
-  }
+  MD_KTILE_ROTATE(NBUF, nk, ktile)
 #undef MD_KC_READ
+#undef MD_KC_BUF
 
   if (g.stamp && threadIdx.x == 0) {
     g.stamp[2 * blockIdx.x] = __builtin_amdgcn_s_memtime() - st_c;
@@ -960,17 +948,7 @@ __global__ void __launch_bounds__(64 * WM * WN) k_gemm_f32_kc_glds(GemmArgs g) {
       }
     return;
   }
-#pragma unroll
-  for (int i = 0; i < WTM; ++i)
-#pragma unroll
-    for (int j = 0; j < WTN; ++j) {
-      const int64_t col = n0 + wn * (WTN * 32) + j * 32 + l32;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int64_t row = m0 + wm * (WTM * 32) + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-        if (RAGGED == 0 || (row < g.M && col < g.N)) C[row * g.c_ms + col * g.c_ns] = acc[i][j][r];
-      }
-    }
+  MD_STORE_C32(RAGGED != 0, acc, C, g, m0, n0, wm, wn, l32, h)
 }
 
 // Repack of a misaligned operand (HipExec::gemm): rows x cols with unit stride along cols and ANY row stride / start -> rows padded to
@@ -1056,53 +1034,6 @@ struct GemmArgs64 {
   int vec_ok;
 };
 
-template <int ROWS, int BK, int NT, bool KC, bool EDGE>
-__device__ __forceinline__ void load_tile64(const double *__restrict__ P, int64_t rs, int64_t ks, int64_t row0, int64_t k0,
-                                            int64_t rows, int64_t K, f64x2 (&r)[ROWS * BK / (2 * NT)], bool vec_ok) {
-  constexpr int PASSES = ROWS * BK / (2 * NT);
-  constexpr int TPR = BK / 2, RPP = NT / TPR;   // KC: threads per row / rows per pass
-  constexpr int TPK = ROWS / 2, KPP = NT / TPK; // !KC: threads per k-row / k-rows per pass
-  const int t = threadIdx.x;
-#pragma unroll
-  for (int i = 0; i < PASSES; ++i) {
-    int row, k;
-    if constexpr (KC) { row = t / TPR + RPP * i; k = (t % TPR) * 2; }
-    else { k = t / TPK + KPP * i; row = (t % TPK) * 2; }
-    if constexpr (!EDGE) {
-      r[i] = *reinterpret_cast<const f64x2 *>(P + (row0 + row) * rs + (k0 + k) * ks);
-    } else {
-      const int64_t rr0 = row0 + row, kk0 = k0 + k;
-      const bool inside = KC ? (rr0 < rows && kk0 + 1 < K) : (kk0 < K && rr0 + 1 < rows);
-      if (vec_ok && inside) {
-        r[i] = *reinterpret_cast<const f64x2 *>(P + rr0 * rs + kk0 * ks);
-      } else {
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          const int64_t rr = rr0 + (KC ? 0 : j), kk = kk0 + (KC ? j : 0);
-          r[i][j] = (rr < rows && kk < K) ? P[rr * rs + kk * ks] : 0.0;
-        }
-      }
-    }
-  }
-}
-template <int ROWS, int BK, int NT, bool KC>
-__device__ __forceinline__ void store_tile64(double (*S)[ROWS + LDP64], const f64x2 (&r)[ROWS * BK / (2 * NT)]) {
-  constexpr int PASSES = ROWS * BK / (2 * NT);
-  constexpr int TPR = BK / 2, RPP = NT / TPR, TPK = ROWS / 2, KPP = NT / TPK;
-  const int t = threadIdx.x;
-#pragma unroll
-  for (int i = 0; i < PASSES; ++i) {
-    if constexpr (KC) {
-      const int row = t / TPR + RPP * i, k = (t % TPR) * 2;
-      S[k][row] = r[i][0];
-      S[k + 1][row] = r[i][1];
-    } else {
-      const int k = t / TPK + KPP * i, row = (t % TPK) * 2;
-      *reinterpret_cast<f64x2 *>(&S[k][row]) = r[i];
-    }
-  }
-}
-
 template <int BM, int BN, int BK, int WM, int WN, bool A_KC, bool B_KC, bool EDGE>
 __global__ void __launch_bounds__(64 * WM * WN) k_gemm_f64_mfma(GemmArgs64 g) {
   constexpr int NT = 64 * WM * WN;
@@ -1110,8 +1041,7 @@ __global__ void __launch_bounds__(64 * WM * WN) k_gemm_f64_mfma(GemmArgs64 g) {
   __shared__ double As[2][BK][BM + LDP64];
   __shared__ double Bs[2][BK][BN + LDP64];
   const int nblk = g.tiles_m * g.tiles_n;
-  int bid = blockIdx.x;
-  if ((nblk & 7) == 0) bid = (bid & 7) * (nblk >> 3) + (bid >> 3);
+  MD_XCD_BID(bid, nblk)
   const int tm = bid / g.tiles_n, tn = bid - tm * g.tiles_n;
   const int64_t m0 = (int64_t)tm * BM, n0 = (int64_t)tn * BN;
   const int64_t bz = blockIdx.z;
@@ -1124,22 +1054,17 @@ __global__ void __launch_bounds__(64 * WM * WN) k_gemm_f64_mfma(GemmArgs64 g) {
   const bool vec_ok = g.vec_ok != 0;
 
   f64x4 acc[WTM][WTN];
-#pragma unroll
-  for (int i = 0; i < WTM; ++i)
-#pragma unroll
-    for (int j = 0; j < WTN; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) acc[i][j][r] = 0.0;
+  MD_ZERO_ACC(acc, WTM, WTN, 4)
 
   f64x2 ra[BM * BK / (2 * NT)], rb[BN * BK / (2 * NT)];
   const int64_t nk = (g.K + BK - 1) / BK;
-  load_tile64<BM, BK, NT, A_KC, EDGE>(A, g.a_ms, g.a_ks, m0, 0, g.M, g.K, ra, vec_ok);
-  load_tile64<BN, BK, NT, B_KC, EDGE>(B, g.b_ns, g.b_ks, n0, 0, g.N, g.K, rb, vec_ok);
-  store_tile64<BM, BK, NT, A_KC>(As[0], ra);
-  store_tile64<BN, BK, NT, B_KC>(Bs[0], rb);
+  load_tile<BM, BK, NT, A_KC, EDGE>(A, g.a_ms, g.a_ks, m0, 0, g.M, g.K, ra, vec_ok);
+  load_tile<BN, BK, NT, B_KC, EDGE>(B, g.b_ns, g.b_ks, n0, 0, g.N, g.K, rb, vec_ok);
+  store_tile<BM, BK, NT, A_KC, LDP64>(As[0], ra);
+  store_tile<BN, BK, NT, B_KC, LDP64>(Bs[0], rb);
   if (nk > 1) {
-    load_tile64<BM, BK, NT, A_KC, EDGE>(A, g.a_ms, g.a_ks, m0, BK, g.M, g.K, ra, vec_ok);
-    load_tile64<BN, BK, NT, B_KC, EDGE>(B, g.b_ns, g.b_ks, n0, BK, g.N, g.K, rb, vec_ok);
+    load_tile<BM, BK, NT, A_KC, EDGE>(A, g.a_ms, g.a_ks, m0, BK, g.M, g.K, ra, vec_ok);
+    load_tile<BN, BK, NT, B_KC, EDGE>(B, g.b_ns, g.b_ks, n0, BK, g.N, g.K, rb, vec_ok);
   }
   __syncthreads();
 
@@ -1162,12 +1087,12 @@ __global__ void __launch_bounds__(64 * WM * WN) k_gemm_f64_mfma(GemmArgs64 g) {
 #pragma unroll
         for (int j = 0; j < WTN; ++j) fb[c ^ 1][j] = Bs[cur][kk + 4 + h][wn * (WTN * 16) + j * 16 + l16];
       }
-      if (kk == 0) store_tile64<BM, BK, NT, A_KC>(As[cur ^ 1], ra);
-      if (kk == 4) store_tile64<BN, BK, NT, B_KC>(Bs[cur ^ 1], rb);
+      if (kk == 0) store_tile<BM, BK, NT, A_KC, LDP64>(As[cur ^ 1], ra);
+      if (kk == 4) store_tile<BN, BK, NT, B_KC, LDP64>(Bs[cur ^ 1], rb);
       if (kk == 8) {
         const int64_t ktl = more2 ? kt + 2 : nk - 1;
-        load_tile64<BM, BK, NT, A_KC, EDGE>(A, g.a_ms, g.a_ks, m0, ktl * BK, g.M, g.K, ra, vec_ok);
-        load_tile64<BN, BK, NT, B_KC, EDGE>(B, g.b_ns, g.b_ks, n0, ktl * BK, g.N, g.K, rb, vec_ok);
+        load_tile<BM, BK, NT, A_KC, EDGE>(A, g.a_ms, g.a_ks, m0, ktl * BK, g.M, g.K, ra, vec_ok);
+        load_tile<BN, BK, NT, B_KC, EDGE>(B, g.b_ns, g.b_ks, n0, ktl * BK, g.N, g.K, rb, vec_ok);
       }
 #pragma unroll
       for (int i = 0; i < WTM; ++i)
@@ -1188,18 +1113,7 @@ __global__ void __launch_bounds__(64 * WM * WN) k_gemm_f64_mfma(GemmArgs64 g) {
 #pragma unroll
     for (int j = 0; j < WTN; ++j) fb[0][j] = Bs[cur][h][wn * (WTN * 16) + j * 16 + l16];
   }
-  // C/D of the f64 16x16 tile: col = lane&15, row = (lane>>4) + 4*r
-#pragma unroll
-  for (int i = 0; i < WTM; ++i)
-#pragma unroll
-    for (int j = 0; j < WTN; ++j) {
-      const int64_t col = n0 + wn * (WTN * 16) + j * 16 + l16;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int64_t row = m0 + wm * (WTM * 16) + i * 16 + h + 4 * r;
-        if (!EDGE || (row < g.M && col < g.N)) C[row * g.c_ms + col * g.c_ns] = acc[i][j][r];
-      }
-    }
+  MD_STORE_C64(EDGE, acc, C, g, m0, n0, wm, wn, l16, h)
 }
 
 // ---- float64 TN on the direct-to-LDS scheme (round 3) -------------------------------------------------------------------
@@ -1229,8 +1143,7 @@ __global__ void __launch_bounds__(256, 2) k_gemm_f64_tn_glds(GemmArgs64 g) {
   __shared__ __attribute__((aligned(16))) double B0[BK * F64_TILE_LD];
   __shared__ __attribute__((aligned(16))) double B1[BK * F64_TILE_LD];
   const int nblk = g.tiles_m * g.tiles_n;
-  int bid = blockIdx.x;
-  if ((nblk & 7) == 0) bid = (bid & 7) * (nblk >> 3) + (bid >> 3);   // XCD-aware tile order
+  MD_XCD_BID(bid, nblk)
   const int tm = bid / g.tiles_n, tn = bid - tm * g.tiles_n;
   const int64_t m0 = (int64_t)tm * BM, n0 = (int64_t)tn * BN;
   const int64_t bz = blockIdx.z;
@@ -1243,12 +1156,7 @@ __global__ void __launch_bounds__(256, 2) k_gemm_f64_tn_glds(GemmArgs64 g) {
   const uint32_t lo = (uint32_t)(lane * 16);
 
   f64x4 acc[WTM][WTN];
-#pragma unroll
-  for (int i = 0; i < WTM; ++i)
-#pragma unroll
-    for (int j = 0; j < WTN; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) acc[i][j][r] = 0.0;
+  MD_ZERO_ACC(acc, WTM, WTN, 4)
 
   const int64_t nk = g.K / BK;
 #pragma unroll
@@ -1293,25 +1201,9 @@ __global__ void __launch_bounds__(256, 2) k_gemm_f64_tn_glds(GemmArgs64 g) {
     __syncthreads();
     MD_F64_READ(CUR ^ 1, 0, 0)
   };
-  int64_t kt = 0;
-  for (; kt + 1 < nk; kt += 2) {
-    ktile(MdInt<0>{}, kt + 1);
-    ktile(MdInt<1>{}, kt + 2 < nk ? kt + 2 : nk - 1);
-  }
-  if (kt < nk) ktile(MdInt<0>{}, nk - 1);
+  MD_KTILE_ROTATE(2, nk, ktile)
 #undef MD_F64_READ
-  // C/D of the f64 16x16 tile: col = lane & 15, row = (lane >> 4) + 4 r
-#pragma unroll
-  for (int i = 0; i < WTM; ++i)
-#pragma unroll
-    for (int j = 0; j < WTN; ++j) {
-      const int64_t col = n0 + wn * 64 + j * 16 + l16;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int64_t row = m0 + wm * 64 + i * 16 + h + 4 * r;
-        C[row * g.c_ms + col * g.c_ns] = acc[i][j][r];
-      }
-    }
+  MD_STORE_C64(false, acc, C, g, m0, n0, wm, wn, l16, h)
 }
 
 // ======================= host side: plan, then run ===============================================================================
@@ -1840,7 +1732,7 @@ static bool md_longk_shape(const MdGemm &g) {
 // The route the product had before it ran natively — convert both operands to the wide type (float32 / int32: the same bits of the
 // result), the wide plan with its hand-offs (skinny / long-k streaming kernels, split-k), convert the result back — for the shapes whose
 // wide kernels beat one launch of the narrow ones: thin or long-k products, unaligned operands of a large float16 product.
-// `keep_wide`: c has the wide type itself (plan_widen) — the wide plan writes straight into it, no conversion back.
+// `keep_wide`: c has the wide type itself (plan_narrow's wide_out) — the wide plan writes straight into it, no conversion back.
 static void plan_widened(GemmPlan &p, const MdGemm &g, int dtype, int wide, bool keep_wide = false) {
   const size_t wsz = md_dtype_size(wide);
   const int64_t ba = g.a_bs ? g.batch : 1, bb = g.b_bs ? g.batch : 1, M = g.M, N = g.N, K = g.K;
@@ -1866,54 +1758,35 @@ static void plan_widened(GemmPlan &p, const MdGemm &g, int dtype, int wide, bool
 // float16 / int8 / uint8: the MFMA kernels (gemm_narrow.hip) for what they take, unless the product is thin (<= 8 rows or columns: the
 // streaming kernels of skinny.hip after a conversion) or float16 of a few tiles under a long k (split-k in the wide plan); small or odd-stride
 // products on the generic narrow kernel; the rest the widened route.
-static void plan_narrow(GemmPlan &p, const MdGemm &g, int dtype) {
+// `wide_out`: float16 @ float16 -> float32, int8 @ int8 -> int32 (`dtype`: the operands') — the same choices with the carrier kept: the
+// wide-output MFMA / generic kernels of gemm_narrow.hip, or the widened route without its conversion back. The few-tile / long-k
+// cut-over is the narrow output's fit (same k loop; the 4-byte C adds to the epilogue only): profiles/gemm_bench_widen_few_tiles.txt shows
+// no shape slower than the conversion route beyond its run-to-run spread, so it was kept. Option gemm_widen = 0: the route a caller had
+// before — convert both operands, the wide plan — for every wide-output product with a k.
+static void plan_narrow(GemmPlan &p, const MdGemm &g, int dtype, bool wide_out) {
   const int esz = dtype == MDHIP_F16 ? 2 : 1, wide = dtype == MDHIP_F16 ? MDHIP_F32 : MDHIP_I32;
   const NarrowLayout L = md_narrow_layout(g, esz);
   const int64_t blocks = ((g.M + 127) / 128) * ((g.N + 127) / 128) * g.batch;
+  const bool native = !wide_out || md_opt(MD_OPT_GEMM_WIDEN) != 0;
   // A float16 product of a few tiles runs its whole k loop on a few CUs (no k split: ~10.4 us per 1024 of k, whatever the tile
   // count up to a full chip), the widened route splits k over the chip for ~25 us of fixed cost plus ~(1.6 + 0.5 tiles) us per 1024
   // of k (fit to profiles/gemm_bench_narrow_few_tiles_before.txt, NN / NT / TN of 128^2 .. 1024^2 x 1024 .. 8192): the wide route when it
   // is the faster one — 1 tile from k ~ 2.7 K, 4 tiles from ~3.4 K, 9 from ~5 K, never from 18 tiles on.
   const double kk = (double)g.K / 1024.0;
   const bool thin = g.M <= 8 || g.N <= 8, few_long = esz == 2 && kk * (8.8 - 0.5 * (double)blocks) > 22.5;
-  if (L.ok && g.K > 0 && !thin && !few_long && !(esz == 1 && md_longk_shape(g))) {
-    GemmStep &s = p.add(S_NMFMA, esz == 2 ? "matmul(f16 mfma)" : "matmul(i8 mfma)");
-    s.dtype = dtype; s.g = g; s.a_kc = L.a_kc; s.b_kc = L.b_kc; s.edge = L.edge;
+  if (native && L.ok && g.K > 0 && !thin && !few_long && !(esz == 1 && md_longk_shape(g))) {
+    GemmStep &s = p.add(S_NMFMA, wide_out ? (esz == 2 ? "matmul(f16 -> f32 mfma)" : "matmul(i8 -> i32 mfma)") : (esz == 2 ? "matmul(f16 mfma)" : "matmul(i8 mfma)"));
+    s.dtype = dtype; s.g = g; s.a_kc = L.a_kc; s.b_kc = L.b_kc; s.edge = L.edge; s.wide = wide_out;
     return;
   }
   const bool small = g.K <= 512 && g.batch * g.M * g.N * g.K <= (1ll << 22);
   // (int8 / uint8 ran on the generic int64 kernel before: the narrow one is the same loop on 1-byte loads; long-k shapes keep long-k)
-  if (g.K == 0 || small || (esz == 1 && !md_longk_shape(g))) {
-    GemmStep &s = p.add(S_NGENERIC, "matmul(narrow generic)");
-    s.dtype = dtype; s.g = g;
-    return;
-  }
-  plan_widened(p, g, dtype, wide);
-}
-// float16 @ float16 -> float32, int8 @ int8 -> int32 (`dtype`: the operands'): plan_narrow's choices with the carrier kept — the
-// wide-output MFMA / generic kernels of gemm_narrow.hip, or the widened route without its conversion back. The few-tile / long-k
-// cut-over is plan_narrow's fit (same k loop; the 4-byte C adds to the epilogue only): profiles/gemm_bench_widen_few_tiles.txt shows
-// no shape slower than the conversion route beyond its run-to-run spread, so it was kept. Option gemm_widen = 0: the route a caller had
-// before — convert both operands, the wide plan — for every product with a k.
-static void plan_widen(GemmPlan &p, const MdGemm &g, int dtype) {
-  const int esz = dtype == MDHIP_F16 ? 2 : 1, wide = dtype == MDHIP_F16 ? MDHIP_F32 : MDHIP_I32;
-  const NarrowLayout L = md_narrow_layout(g, esz);
-  const int64_t blocks = ((g.M + 127) / 128) * ((g.N + 127) / 128) * g.batch;
-  const double kk = (double)g.K / 1024.0;
-  const bool native = md_opt(MD_OPT_GEMM_WIDEN) != 0;
-  const bool thin = g.M <= 8 || g.N <= 8, few_long = esz == 2 && kk * (8.8 - 0.5 * (double)blocks) > 22.5;
-  if (native && L.ok && g.K > 0 && !thin && !few_long && !(esz == 1 && md_longk_shape(g))) {
-    GemmStep &s = p.add(S_NMFMA, esz == 2 ? "matmul(f16 -> f32 mfma)" : "matmul(i8 -> i32 mfma)");
-    s.dtype = dtype; s.g = g; s.a_kc = L.a_kc; s.b_kc = L.b_kc; s.edge = L.edge; s.wide = true;
-    return;
-  }
-  const bool small = g.K <= 512 && g.batch * g.M * g.N * g.K <= (1ll << 22);
   if (g.K == 0 || (native && (small || (esz == 1 && !md_longk_shape(g))))) {
-    GemmStep &s = p.add(S_NGENERIC, "matmul(wide-output generic)");
-    s.dtype = dtype; s.g = g; s.wide = true;
+    GemmStep &s = p.add(S_NGENERIC, wide_out ? "matmul(wide-output generic)" : "matmul(narrow generic)");
+    s.dtype = dtype; s.g = g; s.wide = wide_out;
     return;
   }
-  plan_widened(p, g, dtype, wide, true);
+  plan_widened(p, g, dtype, wide, wide_out);
 }
 // ---- run ---------------------------------------------------------------------------------------------------------------------------
 typedef void (*GemmKernel)(GemmArgs);
@@ -2064,23 +1937,16 @@ static int run_plan(const GemmPlan &p) {
   return rc;
 }
 struct HipExec {
-  template <class T> static int gemm(const MdGemm &g) {
+  template <class Plan> static int run(const MdGemm &g, Plan &&plan) {
     if (g.batch > 65535) return md_fail(MDHIP_EVALUE, "matmul: batch extent %lld exceeds 65535", (long long)g.batch);
-    GemmPlan p; plan_gemm(p, g, md_dtype_of<T>::value);
+    GemmPlan p; plan(p);
     return run_plan(p);
   }
+  template <class T> static int gemm(const MdGemm &g) { return run(g, [&](GemmPlan &p) { plan_gemm(p, g, md_dtype_of<T>::value); }); }
   // float16 / int8 / uint8 (md_matmul_dispatch): the same planner, its narrow steps
-  static int gemm_narrow(const MdGemm &g, int dtype) {
-    if (g.batch > 65535) return md_fail(MDHIP_EVALUE, "matmul: batch extent %lld exceeds 65535", (long long)g.batch);
-    GemmPlan p; plan_narrow(p, g, dtype);
-    return run_plan(p);
-  }
+  static int gemm_narrow(const MdGemm &g, int dtype) { return run(g, [&](GemmPlan &p) { plan_narrow(p, g, dtype, false); }); }
   // float16 -> float32, int8 -> int32 (md_matmul_dispatch; `dtype`: the operands')
-  static int gemm_widen(const MdGemm &g, int dtype) {
-    if (g.batch > 65535) return md_fail(MDHIP_EVALUE, "matmul: batch extent %lld exceeds 65535", (long long)g.batch);
-    GemmPlan p; plan_widen(p, g, dtype);
-    return run_plan(p);
-  }
+  static int gemm_widen(const MdGemm &g, int dtype) { return run(g, [&](GemmPlan &p) { plan_narrow(p, g, dtype, true); }); }
 };
 // mdhip_matmul_bias_relu_sum: the plain product's tile choice (and summation order: a mask recomputed from `a @ b + bias` agrees bit
 // for bit), restricted to tiles that divide the problem; the fused DMA kernel takes whole k-tiles only. false: not covered.
