@@ -353,13 +353,19 @@ enum {
 };
 /* operand sources of a BINARY (and the rhs of PUSH) */
 enum { MDHIP_VM_SRC_STACK = 0, MDHIP_VM_SRC_LEAF = 1, MDHIP_VM_SRC_CONST = 2 };
-/* ctrl word: kind[0:2] op[3:7] lhs_src[8:9] lhs_leaf[10:12] rhs_src[13:14] rhs_leaf[15:17].
+/* ctrl word: kind[0:2] op[3:7] lhs_src[8:9] lhs_leaf[10:12] rhs_src[13:14] rhs_leaf[15:17] round16[18].
  * BINARY: value = op(lhs, rhs). Both STACK: lhs = s1, rhs = s0, pops one. One STACK:
  * it is s0, replaced in place (the common "x = op(x, leaf|const)" costs no stack traffic).
  * None STACK: the result is pushed. A CONST operand reads imm[pc] (so at most one per
  * instruction). */
 #define MDHIP_VM_CTRL(kind, op, ls, ll, rs, rl) \
   ((uint32_t)(kind) | ((uint32_t)(op) << 3) | ((uint32_t)(ls) << 8) | ((uint32_t)(ll) << 10) | ((uint32_t)(rs) << 13) | ((uint32_t)(rl) << 15))
+/* Flag, OR-ed into the ctrl word of a UNARY or BINARY of a float32 program: the value the instruction produces is rounded to
+ * binary16 (nearest even: the conversion of the eager float16 kernels, so subnormals, overflow to infinity and NaN behave as
+ * there) and widened back before it reaches the stack. This is how a recorded float16 loop runs on the float32 carrier: NumPy's
+ * half loops compute in float32 and round once per call. Refused (MDHIP_EVALUE) under compute_dtype F64 and on PUSH / WHERE,
+ * which compute nothing. */
+#define MDHIP_VM_RND16 (1u << 18)
 typedef struct mdhip_vm_program {
   int32_t n_instr, n_leaves, compute_dtype, _pad;
   uint32_t ctrl[MDHIP_VM_MAX_INSTR];

@@ -69,9 +69,12 @@ VM_PUSH, VM_UNARY, VM_BINARY, VM_WHERE = range(4)
 VM_SRC_STACK, VM_SRC_LEAF, VM_SRC_CONST = range(3)
 
 
-def vm_ctrl(kind, op=0, ls=0, ll=0, rs=0, rl=0) -> int:
-    """MDHIP_VM_CTRL of include/mdhip.h."""
-    return kind | (op << 3) | (ls << 8) | (ll << 10) | (rs << 13) | (rl << 15)
+VM_RND16 = 1 << 18   # MDHIP_VM_RND16: the instruction's value is rounded through binary16 (UNARY / BINARY of float32 programs)
+
+
+def vm_ctrl(kind, op=0, ls=0, ll=0, rs=0, rl=0, rnd16=False) -> int:
+    """MDHIP_VM_CTRL of include/mdhip.h, with MDHIP_VM_RND16 when `rnd16`."""
+    return kind | (op << 3) | (ls << 8) | (ll << 10) | (rs << 13) | (rl << 15) | (VM_RND16 if rnd16 else 0)
 
 
 class VmProgram(C.Structure):

@@ -261,22 +261,30 @@ static std::string gen_body(const Spec &S, int k, const TrigUse &tu) {
   for (int pc = 0; pc < pr->n_instr; ++pc) {
     const uint32_t c = pr->ctrl[pc];
     const uint32_t kd = MD_VM_KIND(c), op = MD_VM_OP(c), ls = MD_VM_LS(c), rs = MD_VM_RS(c);
+    const bool r16 = (c & MDHIP_VM_RND16) != 0;  // the instruction's value goes through binary16 (md_vm.h: md_vm_round16)
+    static const char *const rnd[2] = {"(", "jr16("};
     if (kd == MDHIP_VM_PUSH) {
       st.push_back(operand(rs, MD_VM_RL(c), pc));
     } else if (kd == MDHIP_VM_UNARY) {
       std::string x = st.back();
       st.pop_back();
       if ((op == MDHIP_U_SIN || op == MDHIP_U_COS) && x.size() >= 2 && x[0] == 'l' && x.find_first_not_of("0123456789", 1) == std::string::npos) {
-        st.push_back((op == MDHIP_U_SIN ? "sn" : "cs") + x.substr(1));  // hoisted
+        const std::string h = (op == MDHIP_U_SIN ? "sn" : "cs") + x.substr(1);  // hoisted
+        if (r16) {  // the hoisted value is shared with unflagged uses: round it where this instruction takes it
+          o << "  const T t" << pc << " = jr16(" << h << ");\n";
+          st.push_back("t" + std::to_string(pc));
+        } else {
+          st.push_back(h);
+        }
         continue;
       }
-      o << "  T t" << pc << "; { const T x = " << x << "; t" << pc << " = " << unary_expr(op) << "; }\n";
+      o << "  T t" << pc << "; { const T x = " << x << "; t" << pc << " = " << rnd[r16] << unary_expr(op) << "); }\n";
       st.push_back("t" + std::to_string(pc));
     } else if (kd == MDHIP_VM_BINARY) {
       std::string a, b;
       if (rs == MDHIP_VM_SRC_STACK) { b = st.back(); st.pop_back(); } else b = operand(rs, MD_VM_RL(c), pc);
       if (ls == MDHIP_VM_SRC_STACK) { a = st.back(); st.pop_back(); } else a = operand(ls, MD_VM_LL(c), pc);
-      o << "  T t" << pc << "; { const T a = " << a << ", b = " << b << "; t" << pc << " = " << binary_expr(op) << "; }\n";
+      o << "  T t" << pc << "; { const T a = " << a << ", b = " << b << "; t" << pc << " = " << rnd[r16] << binary_expr(op) << "); }\n";
       st.push_back("t" + std::to_string(pc));
     } else {
       std::string z = st.back(); st.pop_back();
@@ -318,6 +326,7 @@ template <> __device__ __forceinline__ T jcvt<uint8_t>(uint8_t x) { return (T)(x
 struct ju8 { uint8_t v; };
 template <> __device__ __forceinline__ T jcvt<ju8>(ju8 x) { return (T)x.v; }
 template <> __device__ __forceinline__ T jcvt<f16>(f16 x) { return md_cast<T>(x); }
+__device__ __forceinline__ T jr16(T x) { return md_cast<T>(md_cast<f16>(x)); }  // MDHIP_VM_RND16: through binary16, nearest even
 template <class V> __device__ __forceinline__ V jld(const V *p) {
   if constexpr (JNT && sizeof(V) == 16) {
     typedef int i32x4 __attribute__((ext_vector_type(4)));
@@ -865,6 +874,7 @@ static std::string make_key(const Spec &S) {
   if (S.out_f16) k << 'h';
   for (int p = 0; p < S.n; ++p) {
     k << '/';
+    // whole ctrl words, MDHIP_VM_RND16 (bit 18) included: a program that rounds through binary16 never shares a kernel with its unflagged twin
     for (int i = 0; i < S.pr[p]->n_instr; ++i) k << std::hex << S.pr[p]->ctrl[i] << ',';
     k << '@';
     for (int l = 0; l < S.pr[p]->n_leaves; ++l) k << S.leaf_map[p][l];

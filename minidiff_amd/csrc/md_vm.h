@@ -117,6 +117,17 @@ MD_HD void md_vm_operand(uint32_t src, uint32_t leaf, double imm, Loader &load, 
   }
 }
 
+// MDHIP_VM_RND16: the instruction's value goes through binary16 (md_vm_check admits the bit in float32 programs only, so the
+// float64 interpreters carry no code for it). The flag is part of the program: one more wave-uniform branch per step.
+template <class T, int W> MD_HD void md_vm_round16(uint32_t c, T (&s0)[W]) {
+  if constexpr (md_same<T, float>::value) {
+    if (c & MDHIP_VM_RND16) {
+#pragma unroll
+      for (int j = 0; j < W; ++j) s0[j] = md_cast<float>(md_cast<f16>(s0[j]));
+    }
+  }
+}
+
 // Fetch concept: void operator()(int pc, uint32_t &ctrl, double &imm); prefetch(int pc).
 template <class T, int W, class Fetch, class Loader>
 MD_HD void md_vm_run(const int32_t n_instr, Fetch &fetch, Loader &load, T (&s0)[W]) {
@@ -157,8 +168,10 @@ MD_HD void md_vm_run(const int32_t n_instr, Fetch &fetch, Loader &load, T (&s0)[
         for (int j = 0; j < W; ++j) { s3[j] = s2[j]; s2[j] = s1[j]; s1[j] = s0[j]; }
         md_vm_binary<T, W>(op, o1, o2, s0);
       }
+      md_vm_round16<T, W>(c, s0);
     } else if (k == MDHIP_VM_UNARY) {
       md_vm_unary<T, W>(MD_VM_OP(c), s0);
+      md_vm_round16<T, W>(c, s0);
     } else if (k == MDHIP_VM_PUSH) {
 #pragma unroll
       for (int j = 0; j < W; ++j) { s3[j] = s2[j]; s2[j] = s1[j]; s1[j] = s0[j]; }
@@ -191,6 +204,10 @@ static inline int md_vm_check(const mdhip_vm_program *pr) {
     if (ls == MDHIP_VM_SRC_LEAF && (int)MD_VM_LL(c) >= pr->n_leaves) return md_fail(MDHIP_EVALUE, "vm: leaf index out of range at %d", pc);
     if (rs == MDHIP_VM_SRC_LEAF && (int)MD_VM_RL(c) >= pr->n_leaves) return md_fail(MDHIP_EVALUE, "vm: leaf index out of range at %d", pc);
     if (ls > MDHIP_VM_SRC_CONST || rs > MDHIP_VM_SRC_CONST) return md_fail(MDHIP_EVALUE, "vm: bad operand source at %d", pc);
+    if (c & MDHIP_VM_RND16) {
+      if (pr->compute_dtype != MDHIP_F32) return md_fail(MDHIP_EVALUE, "vm: round-to-binary16 needs a float32 program (at %d)", pc);
+      if (k != MDHIP_VM_UNARY && k != MDHIP_VM_BINARY) return md_fail(MDHIP_EVALUE, "vm: round-to-binary16 on an instruction that computes nothing (at %d)", pc);
+    }
     switch (k) {
       case MDHIP_VM_PUSH:
         if (rs == MDHIP_VM_SRC_STACK) return md_fail(MDHIP_EVALUE, "vm: PUSH needs a leaf or const at %d", pc);

@@ -20,7 +20,12 @@ operator. A tree that would exceed the bounds materialises its larger operand
 first. Values are computed in ONE float type per program (float32 or float64 —
 whatever NumPy's loop resolution gave each op); bool results travel as 0/1.
 Integer loops are never fused, and neither are loops whose dtype is storage-only
-itself (float16 + float16, int8 * int8).
+itself (float16 + float16, int8 * int8) — except, behind a switch of its own
+(``MDHIP_LAZY_F16=1`` / ``ndarray.set_lazy_float16(True)``), float16 loops: they are
+recorded into a float32 program whose instructions carry MDHIP_VM_RND16, so every
+recorded call rounds its value to binary16 once, as NumPy's half loops and the eager
+kernels (csrc/narrow.hip) do. That is not ``astype(float32 chain, float16)``, which
+rounds once at the end.
 
 A LEAF may have any of the twelve dtypes: an operand of a float32 / float64 loop
 is read in its own storage type (float16, int8/16, uint8/16/32/64, as bool, int32
@@ -42,13 +47,14 @@ MAX_INSTR, MAX_LEAVES, MAX_DEPTH = 44, 8, 4
 
 class Expr:
     """Node of a pending expression. `cdt` is the program's float type code (F32/F64);
-    `n` / `depth` are the instruction count and stack need of its emitted form."""
+    `n` / `depth` are the instruction count and stack need of its emitted form. `r16`: the node is a recorded
+    float16 call with a float16 result — its instruction rounds the value through binary16 (MDHIP_VM_RND16)."""
 
-    __slots__ = ("kind", "code", "args", "n", "depth", "leaves", "cdt", "owner")
+    __slots__ = ("kind", "code", "args", "n", "depth", "leaves", "cdt", "owner", "r16")
 
-    def __init__(self, kind, code, args, n, depth, leaves, cdt):
+    def __init__(self, kind, code, args, n, depth, leaves, cdt, r16=False):
         self.kind, self.code, self.args = kind, code, args
-        self.n, self.depth, self.leaves, self.cdt = n, depth, leaves, cdt
+        self.n, self.depth, self.leaves, self.cdt, self.r16 = n, depth, leaves, cdt, r16
         self.owner = None  # weakref to the pending DeviceArray this node is the value of (set by DeviceArray._pending)
 
 
@@ -71,14 +77,14 @@ def _simple(e) -> bool:
     return e.kind == LEAF or e.kind == CONST
 
 
-def combine(kind, code, parts, cdt):
+def combine(kind, code, parts, cdt, r16=False):
     leaves = {}
     for p in parts:
         if p.leaves:
             leaves.update(p.leaves)
     if kind == UNARY:
         (a,) = parts
-        return Expr(kind, code, (a,), a.n + 1, a.depth, leaves, cdt)
+        return Expr(kind, code, (a,), a.n + 1, a.depth, leaves, cdt, r16)
     if kind == BINARY:
         a, b = parts
         sa, sb = _simple(a), _simple(b)
@@ -93,7 +99,7 @@ def combine(kind, code, parts, cdt):
             n, depth = b.n + 1, b.depth
         else:
             n, depth = a.n + b.n + 1, max(a.depth, b.depth + 1)
-        return Expr(kind, code, (a, b), n, depth, leaves, cdt)
+        return Expr(kind, code, (a, b), n, depth, leaves, cdt, r16)
     c, a, b = parts  # WHERE: all three go through the stack
     n = c.n + a.n + b.n + 1
     depth = max(c.depth, a.depth + 1, b.depth + 2)
@@ -135,30 +141,30 @@ class _Emitter:
             self.put(vm_ctrl(VM_PUSH, 0, 0, 0, s, l), v)
         elif x.kind == UNARY:
             self.walk(x.args[0])
-            self.put(vm_ctrl(VM_UNARY, x.code))
+            self.put(vm_ctrl(VM_UNARY, x.code, rnd16=x.r16))
         elif x.kind == BINARY:
             a, b = x.args
             sa, sb = _simple(a), _simple(b)
             if sa and sb and a.kind == CONST and b.kind == CONST:
                 self.walk(a)
                 s, l, v = self.src(b)
-                self.put(vm_ctrl(VM_BINARY, x.code, VM_SRC_STACK, 0, s, l), v)
+                self.put(vm_ctrl(VM_BINARY, x.code, VM_SRC_STACK, 0, s, l, x.r16), v)
             elif sa and sb:
                 s1, l1, v1 = self.src(a)
                 s2, l2, v2 = self.src(b)
-                self.put(vm_ctrl(VM_BINARY, x.code, s1, l1, s2, l2), v1 if s1 == VM_SRC_CONST else v2)
+                self.put(vm_ctrl(VM_BINARY, x.code, s1, l1, s2, l2, x.r16), v1 if s1 == VM_SRC_CONST else v2)
             elif sb:
                 self.walk(a)
                 s, l, v = self.src(b)
-                self.put(vm_ctrl(VM_BINARY, x.code, VM_SRC_STACK, 0, s, l), v)
+                self.put(vm_ctrl(VM_BINARY, x.code, VM_SRC_STACK, 0, s, l, x.r16), v)
             elif sa:
                 self.walk(b)
                 s, l, v = self.src(a)
-                self.put(vm_ctrl(VM_BINARY, x.code, s, l, VM_SRC_STACK, 0), v)
+                self.put(vm_ctrl(VM_BINARY, x.code, s, l, VM_SRC_STACK, 0, x.r16), v)
             else:
                 self.walk(a)
                 self.walk(b)
-                self.put(vm_ctrl(VM_BINARY, x.code, VM_SRC_STACK, 0, VM_SRC_STACK, 0))
+                self.put(vm_ctrl(VM_BINARY, x.code, VM_SRC_STACK, 0, VM_SRC_STACK, 0, x.r16))
         else:
             for p in x.args:
                 self.walk(p)

@@ -79,6 +79,24 @@ def lazy_enabled() -> bool:
     return _LAZY
 
 
+# Sub-switch of lazy mode (acts only while it is on): float16 loops — float16 + float16, sqrt(int8), where(m, x16, y16) — are
+# recorded too, into float32 programs that round every recorded call through binary16 (MDHIP_VM_RND16, minidiff_amd/lazy.py).
+# Off: such calls launch the eager kernel of csrc/narrow.hip, lazy mode or not.
+_LAZY_F16 = os.environ.get("MDHIP_LAZY_F16", "0") == "1"
+_F16_DT = np.dtype(np.float16)
+
+
+def set_lazy_float16(flag: bool) -> bool:
+    """Switch the recording of float16 loops in lazy mode on/off; returns the previous setting."""
+    global _LAZY_F16
+    prev, _LAZY_F16 = _LAZY_F16, py_bool(flag)
+    return prev
+
+
+def lazy_float16_enabled() -> bool:
+    return _LAZY_F16
+
+
 # launches issued for pending expressions (tests assert that fusion really happened)
 FUSION_STATS = {"vm_eval": 0, "vm_reduce": 0, "vm_reduce_rows": 0, "vm_reduce_axis": 0, "vm_eval_multi": 0, "vm_eval_reduce_cols": 0, "deferred_cols": 0, "gemm_deferred": 0, "gemm_epilogue": 0}
 
@@ -324,7 +342,10 @@ class DeviceArray(_fp.ArrayBase if _fp is not None else object):
                     except ValueError:  # shape not covered by the one-pass kernel
                         pass
                 if fused is None:
-                    _lib().vm_eval(prog, self.desc())
+                    if self._code == _capi.F16:
+                        _eval_float16_chain(prog, self)
+                    else:
+                        _lib().vm_eval(prog, self.desc())
                     FUSION_STATS["vm_eval"] += 1
                 for k, t in enumerate(tasks):
                     if t is not fused:  # from the materialised value (one more read, same result)
@@ -907,8 +928,34 @@ def _register_reader(buf, arr):
     deps[key] = weakref.ref(arr, lambda _r, k=key, d=deps: d.pop(k, None))  # (arrays are unhashable)
 
 
-def _as_expr(x, cdt):
-    """operand -> expression node of a program computing in float type `cdt`."""
+def _eval_float16_chain(prog, out):
+    """Evaluate a recorded float16 chain into its float16 block. Every value of the program is a binary16 already (its last
+    call rounded it), so the store is exact. A library that stores the compute dtype only (the CPU double) gets a float32
+    temporary, converted afterwards: the same bits."""
+    try:
+        _lib().vm_eval(prog, out.desc())
+    except (TypeError, ValueError):
+        tmp = DeviceArray.empty(out.shape, np.float32)
+        _lib().vm_eval(prog, tmp.desc())
+        _lib().convert(tmp.desc(), out.desc())
+
+
+def _const16(v) -> float:
+    """A scalar operand of a float16 loop as the float16 VALUE NumPy makes of it before the arithmetic (x16 * 0.1 multiplies
+    by 0.0999755859375, x16 + 1e5 adds infinity) — the rule of the eager route, md_scalar_in_loop_dtype in csrc/md_narrow.h."""
+    if isinstance(v, np.generic):
+        v = v.item()
+    if v >= 65520:          # rounds to infinity (nearest even: 65520 is the midpoint above the largest finite value)
+        return float("inf")
+    if v <= -65520:
+        return float("-inf")
+    return float(np.float16(v))
+
+
+def _as_expr(x, cdt, c16=False):
+    """operand -> expression node of a program computing in float type `cdt` (c16: the operand of a float16 loop)."""
+    if c16 and not isinstance(x, DeviceArray):
+        return _lz.const(_const16(x), cdt)
     if isinstance(x, DeviceArray):
         e = x._expr
         if e is not None:
@@ -923,12 +970,13 @@ def _as_expr(x, cdt):
     return _lz.const(x, cdt)
 
 
-def _lazy_node(kind, code, operands, cdt, shape, odt):
+def _lazy_node(kind, code, operands, cdt, shape, odt, f16=False):
     """Build a pending result, materialising the largest pending operand(s) while the
-    program would not fit the interpreter."""
+    program would not fit the interpreter. f16: the call is a float16 loop on the float32 carrier — scalars are float16
+    values, and a float16 result of a UNARY / BINARY is rounded through binary16 (comparisons give 0/1, WHERE selects)."""
     while True:
-        parts = [_as_expr(x, cdt) for x in operands]
-        e = _lz.combine(kind, code, parts, cdt)
+        parts = [_as_expr(x, cdt, f16) for x in operands]
+        e = _lz.combine(kind, code, parts, cdt, f16 and kind != _lz.WHERE and odt == _F16_DT)
         if _lz.fits(e):
             return DeviceArray._pending(e, shape, odt)
         big = None
@@ -985,6 +1033,12 @@ def _binary(ufunc, code, a, b, out=None):
             res = _lazy_node(_lz.BINARY, code, (a, b), pcdt, shape, odt)
             if res is not None:
                 return res
+    if _LAZY_F16 and _LAZY and out is None and cdt == _F16_DT and _prod(shape) > 0 and _prod(shape) >= _LAZY_MIN:
+        # a float16 loop (operands: float16, bool, int8, uint8 arrays — exact in float32 — and float16-valued scalars), recorded
+        # on the float32 carrier; its value is rounded to binary16 once, as the eager kernel's is (comparisons: 0/1, no rounding)
+        res = _lazy_node(_lz.BINARY, code, (a, b), _capi.F32, shape, odt, True)
+        if res is not None:
+            return res
     if a_arr:
         a = _straighten(a)
     if b_arr:
@@ -1082,6 +1136,11 @@ def _unary(ufunc, code, x):
                 (pcdt is not None and x.dtype.kind == "i" and pcdt == _capi.F64) or \
                 (pcdt is not None and x._code >= _NARROW_MIN and x.dtype.kind in "iu"):
             res = _lazy_node(_lz.UNARY, code, (x,), pcdt, x.shape, loop[1])
+            if res is not None:
+                return res
+        if _LAZY_F16 and pcdt is None and loop[0] == _F16_DT and (loop[1] == _F16_DT or loop[1] == np.bool_):
+            # a float16 loop — exp(x16), sqrt(int8), isnan(x16) — on the float32 carrier, rounded to binary16 once (see _binary)
+            res = _lazy_node(_lz.UNARY, code, (x,), _capi.F32, x.shape, loop[1], True)
             if res is not None:
                 return res
     res = DeviceArray._new(x.shape, loop[1])
@@ -1324,6 +1383,12 @@ def where(condition, x=None, y=None):
             res = _lazy_node(_lz.WHERE, 0, (c, a, b), pcdt, shape, odt)
             if res is not None:
                 return res
+        elif _LAZY_F16 and odt == _F16_DT and isinstance(c, DeviceArray) and c.dtype == np.bool_:
+            # a float16 selection under a bool mask: branches are float16 / bool / int8 / uint8 arrays or float16-valued scalars,
+            # all exact in the float32 carrier; nothing is computed, so nothing is rounded
+            res = _lazy_node(_lz.WHERE, 0, (c, a, b), _capi.F32, shape, odt, True)
+            if res is not None:
+                return res
     res = DeviceArray._new(shape, odt)
     dc = _operand_desc(c, shape, _capi.I64)
     # (np.where is not a ufunc: a Python int beyond the result type is CAST, wrapping, where a ufunc would raise OverflowError)
@@ -1371,6 +1436,13 @@ def astype(a, dtype, copy=True, **kw):
             # a storage-only array widened to float32 / float64: pending, its expression the leaf itself — consumers read the
             # narrow bytes directly and the float copy exists only if somebody needs it in memory (a write into `a` evaluates it first)
             return DeviceArray._pending(_lz.leaf(a, _FLOAT_DT[dtype]), a.shape, dtype)
+        if e is not None and a._code == _capi.F16 and dtype == np.float32 and e.kind != _lz.GEMM and e.cdt == _capi.F32:
+            # a recorded float16 chain (MDHIP_LAZY_F16) widened to float32: its values are binary16 numbers held in float32
+            # already, so the float32 array IS the same expression — nothing launches, and a reduction of it accumulates in float32
+            own = e.owner
+            res = DeviceArray._pending(e, a.shape, dtype)
+            e.owner = own
+            return res
         if e is not None and dtype == np.float16 and e.kind != _lz.GEMM and _FLOAT_DT.get(a.dtype) == e.cdt:
             res = _eval_as_float16(a, e)
             if res is not None:
