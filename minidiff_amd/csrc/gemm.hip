@@ -1366,7 +1366,7 @@ struct GemmStep {   // only the steps in use are initialised (GemmPlan::add)
   MdGemm g;    // hand-offs, S_GENERIC, S_N*: the product; S_REPACK: a -> c, rows x cols = M x N, a_ms / c_ms row strides; S_SUM: K partials at a;
                // S_NCONV: a (dtype) -> c (dtype_to), batch x M x N with strides a_bs / a_ms / a_ks and c_bs / c_ms / c_ns
                // S_BX_*: b = the flag word; CLEAR: nothing else; SPLIT_*: a (M rows x K, a_ms the row / k-row stride) -> planes at c;
-               // GEMM: planes at a, planes at b_planes, C at c with c_ms
+               // GEMM: planes at a, planes at b_planes, C at c with c_ms; SPLIT_* and GEMM: splits = the plane products (6 / 3 / 1)
   const void *b_planes;
   const char *what;
 };
@@ -1535,7 +1535,21 @@ static void plan_generic(GemmPlan &p, const MdGemm &g, int dtype) { GemmStep &s 
 // the whole product, so panelled and un-panelled gradients stay bit-identical (every output element's bits are the same in both).
 // Floors: the split passes stream 10 bytes per operand element and the 256 x 128 tiles must fill the chip; read off the option 0 / 2 sweep
 // in profiles/gemm_bf16x3_after.txt so that no product with M >= 2048 loses (the 512- and 1024-row panels of such a product do).
+// Option gemm_products (6 | 3 | 1, anything else 6) permits fewer products over fewer, rounded planes (k_gemm_bf16xp): the structure
+// test and the form of the decision are the same in every mode; only the N and K floors are the mode's own. They are read off
+// profiles/matmul_precision.txt by the same rule — the route must beat the default route of the shape (the six products from
+// 4096, the fp32 plan below) at M = 2048 by more than the larger min - max spread: three products win at 2048^3 (94 against 125 us)
+// and at neither 2048 x 1024 x 2048 nor 2048 x 2048 x 1024 (M x K x N); one product wins at K = 1024 too (43 against 66 us) and
+// would at N = 1024 (58 against 91), but no N floor goes below 2048: 512 rows x 2048 columns are the 256 64 x 64 tiles from which
+// the fp32 plan behind the product is one plain launch (plan_bf16x3), so the route cannot depend on M beyond the floor. The 512- and
+// 1024-row panels lose under three products as they do under six (90 against 57 us at 512 x 2048 x 2048) and draw under one.
 constexpr int64_t kBx3FloorN = 4096, kBx3FloorK = 4096;
+constexpr int64_t kBxp3FloorN = 2048, kBxp3FloorK = 2048;   // gemm_products 3
+constexpr int64_t kBxp1FloorN = 2048, kBxp1FloorK = 1024;   // gemm_products 1
+static int bx_products() {
+  const int64_t v = md_opt(MD_OPT_GEMM_PRODUCTS);
+  return v == 3 || v == 1 ? (int)v : 6;
+}
 static bool bf16x3_takes(const MdGemm &g) {
   const int64_t mode = md_opt(MD_OPT_GEMM_BF16X3);
   if (mode == 0 || g.batch != 1 || g.c_ns != 1 || g.c_ms < g.N) return false;
@@ -1547,7 +1561,10 @@ static bool bf16x3_takes(const MdGemm &g) {
     return rs == 1 && ks >= rows && ks % 4 == 0;
   };
   if (!side(g.a, g.M, g.K, g.a_ms, g.a_ks) || !side(g.b, g.N, g.K, g.b_ns, g.b_ks)) return false;
-  return mode == 2 || (g.M >= 512 && g.N >= kBx3FloorN && g.K >= kBx3FloorK);
+  const int products = bx_products();
+  const int64_t floor_n = products == 6 ? kBx3FloorN : products == 3 ? kBxp3FloorN : kBxp1FloorN;
+  const int64_t floor_k = products == 6 ? kBx3FloorK : products == 3 ? kBxp3FloorK : kBxp1FloorK;
+  return mode == 2 || (g.M >= 512 && g.N >= floor_n && g.K >= floor_k);
 }
 static void plan_f32(GemmPlan &p, const MdGemm &g_in, bool top = true);
 // flag word = 0, split A, split B, the product, and behind it the fp32 plan of the same product with run_if_set: when a split pass
@@ -1567,21 +1584,22 @@ static bool plan_bf16x3(GemmPlan &p, const MdGemm &g) {
     // (a hand-off in front of a peeled strip declines every strip of >= 128 rows and columns: md_gemm_skinny)
     if (!(s.kind == S_F32 && s.splits == 1 && !s.epi) && s.kind != S_SKINNY) return false;
   }
-  const size_t a_bytes = (size_t)(3 * g.M * g.K) * 2, b_bytes = (size_t)(3 * g.N * g.K) * 2;
+  const int products = bx_products(), nplanes = products == 6 ? 3 : products == 3 ? 2 : 1;
+  const size_t a_bytes = (size_t)(nplanes * g.M * g.K) * 2, b_bytes = (size_t)(nplanes * g.N * g.K) * 2;
   char *buf = (char *)p.temp(256 + a_bytes + b_bytes);
   char *ap = buf + 256, *bp = ap + a_bytes;
   p.add(S_BX_CLEAR, "matmul(bf16x3 flag)").g.b = buf;
   const int layout = md_opt(MD_OPT_GEMM_BF16X3_PLANES) != 0;   // the plane image (md_bf16x3_layout.h), one for the three steps: GemmStep::cfg
   auto split = [&](const void *src, int64_t rows, int64_t rs, int64_t ks, void *dst) {
     GemmStep &st = p.add(ks == 1 ? S_BX_SPLIT_ROWS : S_BX_SPLIT_COLS, "matmul(bf16x3 split)");
-    st.cfg = layout;
+    st.cfg = layout; st.splits = products;
     MdGemm &x = st.g;
     x.a = src; x.b = buf; x.c = dst; x.M = rows; x.K = g.K; x.a_ms = ks == 1 ? rs : ks;
   };
   split(g.a, g.M, g.a_ms, g.a_ks, ap);
   split(g.b, g.N, g.b_ns, g.b_ks, bp);
   GemmStep &m = p.add(S_BX_GEMM, "matmul(f32 as bf16x3)");
-  m.g = g; m.g.a = ap; m.g.b = buf; m.b_planes = bp; m.cfg = layout;
+  m.g = g; m.g.a = ap; m.g.b = buf; m.b_planes = bp; m.cfg = layout; m.splits = products;
   for (int i = 0; i < q.n; ++i) {
     GemmStep &s = p.step[p.n++] = q.step[i];
     if (s.kind == S_F32) s.ga.run_if_set = (const unsigned *)buf;
@@ -1699,7 +1717,10 @@ static void plan_gemm(GemmPlan &p, const MdGemm &g, int dtype) {
     GemmStep &s = p.add(h ? S_SKINNY : S_LONGK);
     s.dtype = dtype; s.g = g;
   }
-  if (dtype == MDHIP_F32 && !plan_kranges(p, g)) plan_f32(p, g);
+  // (a reduced mode's floors reach the k ranges' shapes — N = 2048 under K >= 4096, which M <= 1024 alone would send there: what
+  // the reduced route takes stays off the k ranges, so that a row panel and its whole product keep one route)
+  const bool reduced = dtype == MDHIP_F32 && bx_products() != 6 && bf16x3_takes(g);
+  if (dtype == MDHIP_F32 && (reduced || !plan_kranges(p, g))) plan_f32(p, g);
   else if (dtype == MDHIP_F64) plan_f64(p, g);
   else if (dtype != MDHIP_F32) plan_generic(p, g, dtype);
   for (int h = h0; h < h0 + handoffs; ++h) p.step[h].skip = p.n - h - 1;
@@ -1893,10 +1914,11 @@ static int run_step(const GemmStep &s, const void *const *tmp, int *skip) {
     case S_BX_CLEAR: return md_hip_check(hipMemsetAsync(const_cast<void *>(g.b), 0, 4, md_stream()), s.what);
     case S_BX_SPLIT_ROWS:
     case S_BX_SPLIT_COLS:   // launched plainly, as the repack: attached events wait for the product
-      return md_gemm_bf16x3_split((const float *)g.a, s.kind == S_BX_SPLIT_ROWS, g.M, g.K, g.a_ms, g.c, (unsigned *)const_cast<void *>(g.b), s.cfg);
+      return md_gemm_bf16x3_split((const float *)g.a, s.kind == S_BX_SPLIT_ROWS, g.M, g.K, g.a_ms, g.c, (unsigned *)const_cast<void *>(g.b), s.cfg,
+                                  s.splits == 6 ? 3 : s.splits == 3 ? 2 : 1);
     case S_BX_GEMM:
       return md_gemm_bf16x3(g.a, at(s.b_planes), (float *)g.c, g.M, g.N, g.K, g.c_ms, (const unsigned *)g.b, (int)md_opt(MD_OPT_GEMM_BF16X3_LOOP), s.cfg,
-                            (int)md_opt(MD_OPT_GEMM_BF16X3_BAND));
+                            (int)md_opt(MD_OPT_GEMM_BF16X3_BAND), s.splits);
     case S_NGENERIC: return s.wide ? md_gemm_widen_generic(g, s.dtype) : md_gemm_narrow_generic(g, s.dtype);
     case S_NCONV: {
       mdhip_array sd{}, dd{};

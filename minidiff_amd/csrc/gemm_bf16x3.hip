@@ -42,6 +42,22 @@
 // 726: no difference), the fold as packed adds (723 against 711), and the last sub-tile's six step-1 MFMAs carried over the barrier
 // to cover the first reads' latency (719 against 709). What is left between loop 1 and the MFMA floor is the time in which both
 // waves of a SIMD stand in the same phase (barrier, first reads, DMA issue): the case for de-phasing them.
+// Reduced products (option gemm_products 3 / 1 = ndarray.set_matmul_precision "high" / "medium"; the default 6 is everything above,
+// with unchanged machine code). The product list is ordered so that its prefixes are the cheaper forms: k_gemm_bf16xp<3> forms
+// a1b1 + a1b2 + a2b1 over two planes per operand, k_gemm_bf16xp<1> a1b1 over one. Their planes are ROUNDED (md_bf16x3_split_rn:
+// p1 = RN(x), p2 = RN(x - p1)), not truncated: a truncated plane leans every term towards zero. Split passes k_bf16xp_split_*<NP>
+// write only the planes in use, same images (4 + 2 NP bytes per operand element instead of 10), and also raise the flag for a finite
+// element that rounds up to inf. The kernels are the loop-0 form of the kernel above (bx_stage / bx_mma over the plane count and the
+// product prefix) with its tile, swizzle, tile walk, flag word and write-out, and only the LDS they use (96 / 48 KiB): a fresh
+// accumulator per k-tile (2 NPROD truncating accumulations) folded with one rounded add, fixed product and k order. Contract, against
+// float64 with mass = |a| @ |b| and u8 = 2^-8: medium (2 u8 + u8^2) mass, high (3 u8^2 + 2^-23) mass, plus the accumulation term
+// (2 NPROD 2^-23 + K / 32 x 2^-24) mass; integer operands whose sums stay below 2^24 give the integer product of the rounded planes
+// exactly (tests/test_matmul_precision.py). A permission, not a promise: what plan_bf16x3 does not take runs as under 6.
+// Measured (profiles/matmul_precision.txt, one process, arms interleaved), 4096^3 NN, us per product with its split passes / the
+// kernel alone / the MFMA floor at an assumed 2.0 GHz: six products 630 / 567 / 394, three 409 / 348 / 197, one 217 / 172 / 66; the
+// fp32 fma chain 920. 2048^3: fp32 125, three 94, one 60. The fewer the products, the more the DMAs, reads, fold and barrier of a
+// k-tile weigh (8 MFMAs per wave against 3 pieces and 8 reads under one product): loop 1's order, a deeper k-tile and two blocks per
+// CU are not built.
 // LDS image (as gemm_narrow.hip's KC image, for 64-B rows): [row][64 B], 16-B chunk c of row r in slot c ^ ((r >> 2) & 3), swizzled
 // through the per-lane SOURCE address; the 16 lanes of a read group hit 16 distinct bank slots.
 // The buffers are separate __shared__ objects and the k loop is unrolled by two, as in gemm_narrow.hip. Whole tiles only. The k order
@@ -149,6 +165,94 @@ __global__ void __launch_bounds__(256) k_bf16x3_split_cols(const float *__restri
   }
 }
 
+// ---- split pass of the reduced products (option gemm_products 3 / 1) ------------------------------------------------------------------
+// The three passes above for NP = 2 / 1 planes of the ROUNDING split (md_bf16x3_split_rn): the same images, grids and flag word, only
+// the planes in use written (4 + 2 NP bytes per operand element instead of 10). The flag also rises for a finite element that
+// rounds to inf. (Written out again, not shared with the kernels above: routed through a plane-count template those came out with
+// another register allocation, and this change leaves their machine code as it was — profiles/matmul_precision_isa.txt.)
+template <int NP>
+__device__ __forceinline__ bool bxp_split8(const float (&x)[8], bx_i32x4 (&q)[NP]) {
+  bool bad = false;
+  uint32_t h[NP][8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    uint32_t p[2];
+    bad |= md_bf16x3_split_rn(x[j], NP, &p[0], &p[1]);
+#pragma unroll
+    for (int i = 0; i < NP; ++i) h[i][j] = p[i] >> 16;
+  }
+#pragma unroll
+  for (int p = 0; p < NP; ++p)
+#pragma unroll
+    for (int w = 0; w < 4; ++w) q[p][w] = (int)(h[p][2 * w] | (h[p][2 * w + 1] << 16));
+  return bad;
+}
+template <int NP>
+__device__ __forceinline__ void bxp_put(char *d, int64_t plane, const bx_i32x4 (&q)[NP]) {
+#pragma unroll
+  for (int p = 0; p < NP; ++p) *(bx_i32x4 *)(d + p * plane) = q[p];
+}
+
+template <int NP>
+__global__ void __launch_bounds__(256) k_bf16xp_split_rows(const float *__restrict__ src, int64_t rows, int64_t K, int64_t rs, char *__restrict__ dst,
+                                                           int64_t plane, unsigned *flag) {
+  bool bad = false;
+  const int64_t k = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 8;
+  if (k < K) {
+    for (int64_t r = blockIdx.y; r < rows; r += gridDim.y) {
+      const bx_f32x4 lo = *(const bx_f32x4 *)(src + r * rs + k), hi = *(const bx_f32x4 *)(src + r * rs + k + 4);
+      const float x[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+      bx_i32x4 q[NP];
+      bad |= bxp_split8<NP>(x, q);
+      bxp_put<NP>(dst + md_bf16x3_plane_off(r, k, K * 2, 64), plane, q);
+    }
+  }
+  if (__syncthreads_or(bad) && threadIdx.x == 0) atomicOr(flag, 1u);
+}
+
+template <int NP>
+__global__ void __launch_bounds__(256) k_bf16xp_split_rows_kt(const float *__restrict__ src, int64_t rows, int64_t K, int64_t rs, char *__restrict__ dst,
+                                                              int64_t plane, unsigned *flag) {
+  bool bad = false;
+  const int l = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int64_t k = (((int64_t)blockIdx.x * 4 + w) * 8 + (l >> 3)) * 32 + (l & 3) * 8;
+  if (k < K) {
+    for (int64_t r = (int64_t)blockIdx.y * 2 + ((l >> 2) & 1); r < rows; r += (int64_t)gridDim.y * 2) {
+      const bx_f32x4 lo = *(const bx_f32x4 *)(src + r * rs + k), hi = *(const bx_f32x4 *)(src + r * rs + k + 4);
+      const float x[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+      bx_i32x4 q[NP];
+      bad |= bxp_split8<NP>(x, q);
+      bxp_put<NP>(dst + md_bf16x3_plane_off(r, k, 64, rows * 64), plane, q);
+    }
+  }
+  if (__syncthreads_or(bad) && threadIdx.x == 0) atomicOr(flag, 1u);
+}
+
+template <int NP>
+__global__ void __launch_bounds__(256) k_bf16xp_split_cols(const float *__restrict__ src, int64_t rows, int64_t K, int64_t ks, char *__restrict__ dst,
+                                                           int64_t plane, int64_t prs, int64_t pks, unsigned *flag) {
+  __shared__ float T[32][66];   // [k][row], as k_bf16x3_split_cols
+  const int t = threadIdx.x;
+  for (int64_t kb = blockIdx.y; kb < K / 32; kb += gridDim.y) {
+    const int64_t r0 = (int64_t)blockIdx.x * 64, k0 = kb * 32;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int idx = t + 256 * i, kk = idx >> 4, r4 = (idx & 15) * 4;
+      const bx_f32x4 v = *(const bx_f32x4 *)(src + (k0 + kk) * ks + r0 + r4);
+      T[kk][r4] = v[0]; T[kk][r4 + 1] = v[1]; T[kk][r4 + 2] = v[2]; T[kk][r4 + 3] = v[3];
+    }
+    __syncthreads();
+    const int kg = t & 3, r = t >> 2;
+    float x[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) x[j] = T[kg * 8 + j][r];
+    bx_i32x4 q[NP];
+    const bool bad = bxp_split8<NP>(x, q);
+    bxp_put<NP>(dst + md_bf16x3_plane_off(r0 + r, k0 + kg * 8, prs, pks), plane, q);
+    if (__syncthreads_or(bad) && t == 0) atomicOr(flag, 1u);   // (also: every lane is done with T)
+  }
+}
+
 // ---- product ---------------------------------------------------------------------------------------------------------------------
 struct Bx3Args {
   const char *A, *B;        // plane 1 of each operand; planes 2 and 3 follow a_plane / b_plane BYTES apart
@@ -177,10 +281,12 @@ __device__ __forceinline__ void bx_piece(const char *P, int64_t rs, int64_t row,
 
 struct Bx3Bufs { char *a[3], *b[3]; };
 
+// the NP plane tiles of k-tile kt (NP = 3: the six-product kernel; 2 / 1: the reduced ones)
+template <int NP>
 __device__ __forceinline__ void bx_stage(const Bx3Args &g, int64_t m0, int64_t n0, int kt, const Bx3Bufs &S, uint32_t lane_off) {
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
 #pragma unroll
-  for (int p = 0; p < 3; ++p) {
+  for (int p = 0; p < NP; ++p) {
 #pragma unroll
     for (int i = 0; i < 2; ++i) bx_piece(g.A + p * g.a_plane, g.rs, m0 + 16 * (wave + 8 * i), g.a_kstep, kt, lane_off, S.a[p] + (wave + 8 * i) * 1024);
     bx_piece(g.B + p * g.b_plane, g.rs, n0 + 16 * wave, g.b_kstep, kt, lane_off, S.b[p] + wave * 1024);
@@ -206,6 +312,8 @@ __device__ __forceinline__ uint32_t bx_read_off(int rb, int s) {
 // value with one accumulator over all of K), so the k-tile's 12 accumulations per element start from zero in a fresh accumulator and
 // the k-tile's sum is folded into the running sum with VALU adds (round to nearest), outside the k16 steps: the bias is that of 12
 // truncations whatever K is. The chunk is the k-tile, so the bits of an element still depend on k alone.
+// NPROD: the first 6 / 3 / 1 products of the list over NP = 3 / 2 / 1 planes (2 NPROD accumulations per k-tile).
+template <int NP, int NPROD>
 __device__ __forceinline__ void bx_mma(const Bx3Bufs &S, int wm, int wn, bx_f32x16 (&acc)[2][2]) {
   bx_f32x16 part[2][2];
 #pragma unroll
@@ -216,9 +324,9 @@ __device__ __forceinline__ void bx_mma(const Bx3Bufs &S, int wm, int wn, bx_f32x
       for (int e = 0; e < 16; ++e) part[i][j][e] = 0;
 #pragma unroll
   for (int s = 0; s < 2; ++s) {
-    bx_bf16x8 a[3][2], b[3][2];
+    bx_bf16x8 a[NP][2], b[NP][2];
 #pragma unroll
-    for (int p = 0; p < 3; ++p)
+    for (int p = 0; p < NP; ++p)
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
         a[p][i] = bx_frag(S.a[p], wm * 64 + i * 32, s);
@@ -227,7 +335,7 @@ __device__ __forceinline__ void bx_mma(const Bx3Bufs &S, int wm, int wn, bx_f32x
     // a1b1, a1b2, a2b1, a1b3, a2b2, a3b1 — each over the four sub-tiles, so that consecutive MFMAs write different accumulators
     constexpr int PA[6] = {0, 0, 1, 0, 1, 2}, PB[6] = {0, 1, 0, 2, 1, 0};
 #pragma unroll
-    for (int q = 0; q < 6; ++q)
+    for (int q = 0; q < NPROD; ++q)
 #pragma unroll
       for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -344,6 +452,29 @@ __device__ __forceinline__ void bx_tile(const Bx3Bufs &S, Bx3Src &src, const Bx3
   carry = part[1][1];
 }
 
+// The tile walk and the write-out of k_gemm_bf16x3 below, as functions for k_gemm_bf16xp (the six-product kernel keeps them in its
+// body: called from there they changed its register allocation). The block's tile:
+__device__ __forceinline__ void bx_origin(const Bx3Args &g, int64_t *m0, int64_t *n0) {
+  const int nwg = g.tiles_m * g.tiles_n, bid = blockIdx.x, xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
+  const int wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
+  int tm, tn;
+  md_bf16x3_tile(wg, g.tiles_m, g.tiles_n, g.gm, &tm, &tn);
+  *m0 = (int64_t)tm * BX_BM; *n0 = (int64_t)tn * BX_BN;
+}
+// accumulator element e of lane l: row (e & 3) + 8 (e >> 2) + 4 (l >> 5), column l & 31 of the 32 x 32 tile; one wave store writes
+// 32 consecutive floats of two rows (whole 128-B lines), as k_gemm_widen_mfma
+__device__ __forceinline__ void bx_write_c(const Bx3Args &g, int64_t m0, int64_t n0, int wm, int wn, int l, const bx_f32x16 (&acc)[2][2]) {
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const int64_t m = m0 + wm * 64 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * (l >> 5), n = n0 + wn * 64 + j * 32 + (l & 31);
+        g.C[m * g.c_ms + n] = acc[i][j][e];
+      }
+}
+
 template <int LOOP>
 __global__ void __launch_bounds__(BX_NT) k_gemm_bf16x3(Bx3Args g) {
   __shared__ __attribute__((aligned(16))) char sA00[BX_BM * BX_ROWB];
@@ -377,15 +508,15 @@ __global__ void __launch_bounds__(BX_NT) k_gemm_bf16x3(Bx3Args g) {
 #pragma unroll
       for (int e = 0; e < 16; ++e) acc[i][j][e] = 0;
   if constexpr (LOOP == 0) {
-    bx_stage(g, m0, n0, 0, S0, lane_off);
+    bx_stage<3>(g, m0, n0, 0, S0, lane_off);
     for (int kt = 0; kt < nk; kt += 2) {
       __syncthreads();   // tile kt is in buffer 0 (the barrier's vmcnt(0) retires the DMAs); every wave is done with buffer 1
-      if (kt + 1 < nk) bx_stage(g, m0, n0, kt + 1, S1, lane_off);
-      bx_mma(S0, wm, wn, acc);
+      if (kt + 1 < nk) bx_stage<3>(g, m0, n0, kt + 1, S1, lane_off);
+      bx_mma<3, 6>(S0, wm, wn, acc);
       if (kt + 1 >= nk) break;
       __syncthreads();
-      if (kt + 2 < nk) bx_stage(g, m0, n0, kt + 2, S0, lane_off);
-      bx_mma(S1, wm, wn, acc);
+      if (kt + 2 < nk) bx_stage<3>(g, m0, n0, kt + 2, S0, lane_off);
+      bx_mma<3, 6>(S1, wm, wn, acc);
     }
   } else {
     const int uw = __builtin_amdgcn_readfirstlane(wave);
@@ -440,27 +571,81 @@ __global__ void __launch_bounds__(BX_NT) k_gemm_bf16x3(Bx3Args g) {
       }
 }
 
+// ---- reduced products (option gemm_products 3 / 1) ---------------------------------------------------------------------------------
+// The first NPROD = 3 (a1b1 + a1b2 + a2b1) or 1 (a1b1) products of the list over NP = 2 / 1 ROUNDED planes per operand
+// (md_bf16x3_split_rn): the loop-0 form of the kernel above with its tile, swizzle, walk, flag word and write-out. Per k-tile and
+// element 2 NPROD truncating accumulations into a fresh accumulator and one rounded add into the running sum, in a fixed order. LDS:
+// two buffers of NP x (256 + 128) rows x 64 B = 96 / 48 KiB.
+template <int NPROD>
+__global__ void __launch_bounds__(BX_NT) k_gemm_bf16xp(Bx3Args g) {
+  constexpr int NP = NPROD == 1 ? 1 : 2;
+  __shared__ __attribute__((aligned(16))) char sA0[NP * BX_BM * BX_ROWB];
+  __shared__ __attribute__((aligned(16))) char sB0[NP * BX_BN * BX_ROWB];
+  __shared__ __attribute__((aligned(16))) char sA1[NP * BX_BM * BX_ROWB];
+  __shared__ __attribute__((aligned(16))) char sB1[NP * BX_BN * BX_ROWB];
+  if (g.flag && *g.flag != 0) return;   // (uniform: one scalar load and branch)
+  // (plane 2's entries point one plane tile on; under NP = 1 they are never read)
+  const Bx3Bufs S0{{sA0, sA0 + (NP - 1) * BX_BM * BX_ROWB, nullptr}, {sB0, sB0 + (NP - 1) * BX_BN * BX_ROWB, nullptr}};
+  const Bx3Bufs S1{{sA1, sA1 + (NP - 1) * BX_BM * BX_ROWB, nullptr}, {sB1, sB1 + (NP - 1) * BX_BN * BX_ROWB, nullptr}};
+  int64_t m0, n0;
+  bx_origin(g, &m0, &n0);
+  const int wave = threadIdx.x >> 6, wm = wave >> 1, wn = wave & 1, l = threadIdx.x & 63;
+  const int nk = (int)(g.K / BX_BK);
+  const uint32_t lane_off = (uint32_t)((l >> 2) * g.rs + (((l & 3) ^ ((l >> 4) & 3)) << 4));
+  bx_f32x16 acc[2][2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0;
+  bx_stage<NP>(g, m0, n0, 0, S0, lane_off);
+  for (int kt = 0; kt < nk; kt += 2) {
+    __syncthreads();   // tile kt is in buffer 0 (the barrier's vmcnt(0) retires the DMAs); every wave is done with buffer 1
+    if (kt + 1 < nk) bx_stage<NP>(g, m0, n0, kt + 1, S1, lane_off);
+    bx_mma<NP, NPROD>(S0, wm, wn, acc);
+    if (kt + 1 >= nk) break;
+    __syncthreads();
+    if (kt + 2 < nk) bx_stage<NP>(g, m0, n0, kt + 2, S0, lane_off);
+    bx_mma<NP, NPROD>(S1, wm, wn, acc);
+  }
+  bx_write_c(g, m0, n0, wm, wn, l, acc);
+}
+
 }  // namespace
 
 // gemm.hip's plan steps: see md_hip.h
-int md_gemm_bf16x3_split(const float *src, bool k_contig, int64_t rows, int64_t K, int64_t stride, void *planes, unsigned *flag, int layout) {
+int md_gemm_bf16x3_split(const float *src, bool k_contig, int64_t rows, int64_t K, int64_t stride, void *planes, unsigned *flag, int layout, int nplanes) {
   const int64_t plane = rows * K * 2;
+  char *dst = (char *)planes;
   if (k_contig && layout) {
     const dim3 grid((unsigned)((K / 32 + 31) / 32), (unsigned)(rows / 2 < 65535 ? rows / 2 : 65535));
-    k_bf16x3_split_rows_kt<<<grid, 256, 0, md_stream()>>>(src, rows, K, stride, (char *)planes, plane, flag);
+    switch (nplanes) {
+      case 1: k_bf16xp_split_rows_kt<1><<<grid, 256, 0, md_stream()>>>(src, rows, K, stride, dst, plane, flag); break;
+      case 2: k_bf16xp_split_rows_kt<2><<<grid, 256, 0, md_stream()>>>(src, rows, K, stride, dst, plane, flag); break;
+      default: k_bf16x3_split_rows_kt<<<grid, 256, 0, md_stream()>>>(src, rows, K, stride, dst, plane, flag); break;
+    }
   } else if (k_contig) {
     const dim3 grid((unsigned)((K / 8 + 255) / 256), (unsigned)(rows < 65535 ? rows : 65535));
-    k_bf16x3_split_rows<<<grid, 256, 0, md_stream()>>>(src, rows, K, stride, (char *)planes, plane, flag);
+    switch (nplanes) {
+      case 1: k_bf16xp_split_rows<1><<<grid, 256, 0, md_stream()>>>(src, rows, K, stride, dst, plane, flag); break;
+      case 2: k_bf16xp_split_rows<2><<<grid, 256, 0, md_stream()>>>(src, rows, K, stride, dst, plane, flag); break;
+      default: k_bf16x3_split_rows<<<grid, 256, 0, md_stream()>>>(src, rows, K, stride, dst, plane, flag); break;
+    }
   } else {
     const dim3 grid((unsigned)(rows / 64), (unsigned)(K / 32 < 65535 ? K / 32 : 65535));
-    k_bf16x3_split_cols<<<grid, 256, 0, md_stream()>>>(src, rows, K, stride, (char *)planes, plane, md_bf16x3_row_stride(layout, K),
-                                                       md_bf16x3_k_step(layout, rows), flag);
+    const int64_t prs = md_bf16x3_row_stride(layout, K), pks = md_bf16x3_k_step(layout, rows);
+    switch (nplanes) {
+      case 1: k_bf16xp_split_cols<1><<<grid, 256, 0, md_stream()>>>(src, rows, K, stride, dst, plane, prs, pks, flag); break;
+      case 2: k_bf16xp_split_cols<2><<<grid, 256, 0, md_stream()>>>(src, rows, K, stride, dst, plane, prs, pks, flag); break;
+      default: k_bf16x3_split_cols<<<grid, 256, 0, md_stream()>>>(src, rows, K, stride, dst, plane, prs, pks, flag); break;
+    }
   }
   return MD_LAUNCH_CHECK("matmul(bf16x3 split)");
 }
 
 int md_gemm_bf16x3(const void *a_planes, const void *b_planes, float *c, int64_t M, int64_t N, int64_t K, int64_t c_ms, const unsigned *flag, int loop,
-                   int layout, int band) {
+                   int layout, int band, int products) {
   Bx3Args a{};
   a.A = (const char *)a_planes; a.B = (const char *)b_planes; a.C = c;
   a.K = K; a.c_ms = c_ms;
@@ -471,9 +656,9 @@ int md_gemm_bf16x3(const void *a_planes, const void *b_planes, float *c, int64_t
   a.flag = flag;
   md_opt_table()[MD_OPT_GEMM_BF16X3_RUNS] += 1;
   const dim3 grid((unsigned)(a.tiles_m * a.tiles_n));
-  switch (loop) {
-    case 0: MD_LAUNCH(k_gemm_bf16x3<0>, grid, BX_NT, a); break;
-    default: MD_LAUNCH(k_gemm_bf16x3<1>, grid, BX_NT, a); break;
-  }
+  if (products == 1) MD_LAUNCH(k_gemm_bf16xp<1>, grid, BX_NT, a);
+  else if (products == 3) MD_LAUNCH(k_gemm_bf16xp<3>, grid, BX_NT, a);
+  else if (loop == 0) MD_LAUNCH(k_gemm_bf16x3<0>, grid, BX_NT, a);
+  else MD_LAUNCH(k_gemm_bf16x3<1>, grid, BX_NT, a);
   return MD_LAUNCH_CHECK("matmul(f32 as bf16x3)");
 }

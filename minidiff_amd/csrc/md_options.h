@@ -44,6 +44,7 @@
   X(GEMM_BF16X3_LOOP, "gemm_bf16x3_loop", 1, 'x')      /* k loop of the bf16x3 product kernel: 0 staging in front of the reads, fold behind the MFMAs | 1 staging and fold under the MFMAs (same bits; A/B) */ \
   X(GEMM_BF16X3_BAND, "gemm_bf16x3_band", 0, 'x')      /* tile walk of the bf16x3 product kernel, tile rows per band of an XCD's tiles: 0 by the CU count | 1 row-major | n forced (same bits; A/B) */ \
   X(GEMM_BF16X3_PLANES, "gemm_bf16x3_planes", 1, 'x')  /* image of the bf16x3 planes: 0 [rows][K] | 1 k-tile-major [K / 32][rows][64 B] (same bits; A/B) */ \
+  X(GEMM_PRODUCTS, "gemm_products", 6, 'x')            /* plane products of a float32 product on the bf16 matrix cores: 6 full float32 accuracy | 3 a1b1 + a1b2 + a2b1 of two ROUNDED planes | 1 a1b1 of one (anything else: 6). A permission: what the reduced kernels do not take runs as under 6 (ndarray.set_matmul_precision) */ \
   X(JIT_U, "jit_u", 0, 'x')                            /* vector groups per lane and trip of the generated streaming kernels (0: by form) */ \
   X(JIT_BLOCKS, "jit_blocks", 0, 'x')                  /* blocks per CU of the generated EVAL kernels (0: by form) */                     \
   X(JIT_AXES_WIDE, "jit_axes_wide", 0, 'x')            /* 1: generated three / four-axis EVAL kernels take the 64-bit index form at any size (tests) */ \

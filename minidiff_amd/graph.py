@@ -195,7 +195,9 @@ class SweepCache:
         never) of a captured entry runs eagerly instead and compares keys; on a mismatch the stale graph is destroyed.
     The key is the structural hash PLUS the tape's sweep signature (`tape._signature`: which inputs are the same tensor,
     shared intermediates, leaf shapes / dtypes, scalar constants, keyword arguments) — the structural hash alone maps every
-    leaf and scalar to -1, so sum(sin(a)*sin(a)) and sum(sin(a)*sin(b)) would collide.
+    leaf and scalar to -1, so sum(sin(a)*sin(a)) and sum(sin(a)*sin(b)) would collide — PLUS the matmul precision
+    (`ndarray.set_matmul_precision`): a captured graph holds the kernels of the precision it was recorded under, so a call made
+    under another precision never replays it; it runs eagerly and starts an entry of its own.
     A sweep that cannot be captured (a synchronising call inside it; the CPU test double) stays eager.
     `step` should RETURN the arrays it produces (e.g. the gradient tensors): a replay rewrites those very arrays,
     but it runs no Python, so attributes that the sweep rebinds (`x.grad = ...`) keep pointing at whatever the
@@ -216,7 +218,12 @@ class SweepCache:
     def _key(self):
         # the structural hash alone maps every leaf and scalar to -1 (as the reference's does): two sweeps that differ only in
         # WHICH inputs coincide, in shapes or in constants would share it, and a stale graph would replay silently
-        return (self.md.last_root_hash, getattr(self.md, "last_root_signature", None))
+        return (self.md.last_root_hash, getattr(self.md, "last_root_signature", None), self._precision())
+
+    @staticmethod
+    def _precision():
+        from . import ndarray as _nd
+        return _nd.get_matmul_precision()
 
     def _eager(self, step):
         with self.md.reuse_graph():   # (a fresh traversal table per Python-run sweep: the tape's memo is keyed by the structural hash alone)
@@ -226,6 +233,8 @@ class SweepCache:
     def run(self, step):
         sid = id(step)
         h = self._current.get(sid)
+        if h is not None and h[2] != self._precision():
+            h = None   # the latest Python-run sweep ran under another matmul precision: its graph is not this call's
         entry = self._entries.get((sid, h)) if h is not None else None
         if entry is not None and entry["sweep"] is not None:
             n = self._calls[sid] = self._calls.get(sid, 0) + 1

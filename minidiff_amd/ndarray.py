@@ -97,6 +97,47 @@ def lazy_float16_enabled() -> bool:
     return _LAZY_F16
 
 
+# Precision of float32 matmul (library option gemm_products, csrc/md_options.h): how many bfloat16 plane products a float32 product
+# may be formed from on the bf16 matrix cores. "highest" (6, the default) is float32 accuracy; "high" (3 products of two rounded
+# planes per operand, ~2^-16 per term) and "medium" (1 product of one, ~2^-8) are permissions, not promises: a product the reduced
+# kernels do not take (batches, ragged or misaligned shapes, anything under the size floors, non-finite operands) runs as under
+# "highest". The option lives in the library, so every route into it (ctypes and _fastpath) sees it. A matmul recorded in lazy
+# mode runs under the precision in force when it is evaluated.
+_MATMUL_PRODUCTS = {"highest": 6, "high": 3, "medium": 1}
+_MATMUL_PRECISION = os.environ.get("MDHIP_MATMUL_PRECISION", "highest")
+if _MATMUL_PRECISION not in _MATMUL_PRODUCTS:
+    raise ValueError(f"MDHIP_MATMUL_PRECISION={_MATMUL_PRECISION!r}: expected one of {sorted(_MATMUL_PRODUCTS)}")
+
+
+def _push_matmul_precision(lib) -> None:
+    lib.debug_set_option(b"gemm_products", _MATMUL_PRODUCTS[_MATMUL_PRECISION])
+
+
+def _bind_matmul_precision(lib) -> None:   # a library bound later starts from the setting made here ("highest" is its own default)
+    if _MATMUL_PRECISION != "highest":
+        _push_matmul_precision(lib)
+
+
+_capi._BIND_HOOKS.append(_bind_matmul_precision)
+if _capi._LIB is not None:
+    _bind_matmul_precision(_capi._LIB)
+
+
+def set_matmul_precision(name: str) -> str:
+    """Allow float32 matmul to trade accuracy for speed: "highest" | "high" | "medium"; returns the previous setting."""
+    global _MATMUL_PRECISION
+    if not isinstance(name, str) or name not in _MATMUL_PRODUCTS:
+        raise ValueError(f"matmul precision {name!r}: expected one of {sorted(_MATMUL_PRODUCTS)}")
+    prev, _MATMUL_PRECISION = _MATMUL_PRECISION, name
+    if _capi._LIB is not None:
+        _push_matmul_precision(_capi._LIB)
+    return prev
+
+
+def get_matmul_precision() -> str:
+    return _MATMUL_PRECISION
+
+
 # launches issued for pending expressions (tests assert that fusion really happened)
 FUSION_STATS = {"vm_eval": 0, "vm_reduce": 0, "vm_reduce_rows": 0, "vm_reduce_axis": 0, "vm_eval_multi": 0, "vm_eval_reduce_cols": 0, "deferred_cols": 0, "gemm_deferred": 0, "gemm_epilogue": 0}
 
