@@ -1246,24 +1246,29 @@ struct StampDump {
   unsigned long long *dev = nullptr;
   int bm = 0, bn = 0, bk = 0;
   size_t blocks = 0;
+  int64_t ktiles = 0;   // k-tiles of the stamped loop, where the launcher knows them (0: not reported)
   static StampDump &get() { static StampDump d; return d; }
   unsigned long long *buffer() {
     if (!dev) (void)hipMalloc((void **)&dev, kMax * 16);
     return dev;
   }
-  void note(int m, int n, int k, size_t b) { bm = m; bn = n; bk = k; blocks = b; }
+  void note(int m, int n, int k, size_t b, int64_t kt = 0) { bm = m; bn = n; bk = k; blocks = b; ktiles = kt; }
   ~StampDump() {
     if (!dev || !blocks) return;
     std::vector<unsigned long long> h(blocks * 2);
     if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(h.data(), dev, h.size() * 8, hipMemcpyDeviceToHost) != hipSuccess) return;
-    std::vector<double> ghz, us;
+    std::vector<double> ghz, us, cyc;
     for (size_t b = 0; b < blocks; ++b)
-      if (h[2 * b + 1]) { ghz.push_back((double)h[2 * b] / (double)h[2 * b + 1] * 0.1); us.push_back((double)h[2 * b + 1] * 0.01); }
+      if (h[2 * b + 1]) { ghz.push_back((double)h[2 * b] / (double)h[2 * b + 1] * 0.1); us.push_back((double)h[2 * b + 1] * 0.01); cyc.push_back((double)h[2 * b]); }
     std::sort(ghz.begin(), ghz.end());
     std::sort(us.begin(), us.end());
+    std::sort(cyc.begin(), cyc.end());
     if (!ghz.empty())
       fprintf(stderr, "[mdhip] last gemm %dx%dx%d: in-kernel clock median %.3f GHz (min %.3f, max %.3f) over %zu blocks; block main loop median %.1f us (min %.1f, p10 %.1f, p90 %.1f, max %.1f)\n",
               bm, bn, bk, ghz[ghz.size() / 2], ghz.front(), ghz.back(), ghz.size(), us[us.size() / 2], us.front(), us[us.size() / 10], us[us.size() * 9 / 10], us.back());
+    if (!cyc.empty() && ktiles > 0)
+      fprintf(stderr, "[mdhip] last gemm %dx%dx%d: %lld k-tiles per block, shader cycles per k-tile and CU median %.0f (min %.0f, p10 %.0f, p90 %.0f, max %.0f)\n", bm, bn, bk,
+              (long long)ktiles, cyc[cyc.size() / 2] / ktiles, cyc.front() / ktiles, cyc[cyc.size() / 10] / ktiles, cyc[cyc.size() * 9 / 10] / ktiles, cyc.back() / ktiles);
   }
 };
 
@@ -1887,8 +1892,11 @@ static int run_step(const GemmStep &s, const void *const *tmp, int *skip) {
       if (s.epi) ga.tickets = md_tickets();
       const GemmKernel k = f32_kernel(s);
       if (!k) return md_fail(MDHIP_ERUNTIME, "matmul: no kernel for the planned launch (cfg %d)", s.cfg);
-      if (s.stamp) ga.stamp = StampDump::get().buffer();   // persistent: no sync behind the launch, the LAST launch's stamps are printed at exit
-      if (s.stamp) StampDump::get().note(s.tile.bm, s.tile.bn, s.tile.bk, (size_t)s.grid.x * s.grid.z);
+      // persistent: no sync behind the launch, the LAST launch's stamps are printed at exit (not the stand-in's behind a bf16x3
+      // product, which does not run: the product kernel's own stamps stay)
+      const bool stamped = s.stamp && !ga.run_if_set;
+      if (stamped) ga.stamp = StampDump::get().buffer();
+      if (stamped) StampDump::get().note(s.tile.bm, s.tile.bn, s.tile.bk, (size_t)s.grid.x * s.grid.z);
       if (s.splits > 1) hipLaunchKernelGGL(k, s.grid, dim3(64u * s.tile.wm * s.tile.wn), 0, md_stream(), ga);   // (not the timed launch)
       else md_gemm_launch(k, s.grid, 64 * s.tile.wm * s.tile.wn, ga);
       return MD_LAUNCH_CHECK(s.what);
@@ -1916,9 +1924,14 @@ static int run_step(const GemmStep &s, const void *const *tmp, int *skip) {
     case S_BX_SPLIT_COLS:   // launched plainly, as the repack: attached events wait for the product
       return md_gemm_bf16x3_split((const float *)g.a, s.kind == S_BX_SPLIT_ROWS, g.M, g.K, g.a_ms, g.c, (unsigned *)const_cast<void *>(g.b), s.cfg,
                                   s.splits == 6 ? 3 : s.splits == 3 ? 2 : 1);
-    case S_BX_GEMM:
+    case S_BX_GEMM: {
+      // diagnostic (option gemm_stamp): the six-product kernel's stamped instantiation, into the persistent stamp buffer
+      const int64_t tiles = (g.M / 256) * (g.N / 128);
+      unsigned long long *stamp = s.splits == 6 && md_gemm_stamped(tiles) ? StampDump::get().buffer() : nullptr;
+      if (stamp) StampDump::get().note(256, 128, 32, (size_t)tiles, g.K / 32);
       return md_gemm_bf16x3(g.a, at(s.b_planes), (float *)g.c, g.M, g.N, g.K, g.c_ms, (const unsigned *)g.b, (int)md_opt(MD_OPT_GEMM_BF16X3_LOOP), s.cfg,
-                            (int)md_opt(MD_OPT_GEMM_BF16X3_BAND), s.splits);
+                            (int)md_opt(MD_OPT_GEMM_BF16X3_BAND), s.splits, stamp);
+    }
     case S_NGENERIC: return s.wide ? md_gemm_widen_generic(g, s.dtype) : md_gemm_narrow_generic(g, s.dtype);
     case S_NCONV: {
       mdhip_array sd{}, dd{};

@@ -31,7 +31,7 @@
 // two waves per SIMD. Each plane tile is staged ONCE per k-tile (global_load_lds_dwordx4: scalar base + 32-bit lane offset, a 1-KiB
 // piece = 16 rows per wave instruction, nine pieces per wave and k-tile) and serves all its products: per k16 step a wave reads 12
 // fragments (3 planes x 2 row blocks of A and of B, one ds_read_b128 each) for 24 MFMAs; 64 adds per wave fold a k-tile's sum into the running sum.
-// Two k loops in one build (template argument, option gemm_bf16x3_loop), the same bits from both. Loop 0 is the loop the kernel was
+// Three k loops in one build (template argument, option gemm_bf16x3_loop), the same bits from all. Loop 0 is the loop the kernel was
 // first measured with: all nine DMAs in front of the k-tile's reads, their addresses formed anew per k-tile, the fold behind the last
 // MFMA. Loop 1 (the default; bx_tile) forms the nine piece bases once and writes the k-tile's program order out, every MFMA behind a
 // scheduling fence with what issues in its shadow: one DMA, two fragment reads of step 1, or four of the fold's adds; step 1 runs
@@ -40,8 +40,21 @@
 // 4096^3 product in the trace of bench.py; in one process, split passes included: loop 0 754 - 761 us, loop 1 709 - 726 us. Built, timed and dropped: the DMAs in one clump in front of the reads with the rest of loop
 // 1 (all these on [rows][K] planes; 751 us against 711 in that run), the DMAs under step 1's MFMAs instead (789), one DMA per two or three MFMAs (724 - 732 against
 // 726: no difference), the fold as packed adds (723 against 711), and the last sub-tile's six step-1 MFMAs carried over the barrier
-// to cover the first reads' latency (719 against 709). What is left between loop 1 and the MFMA floor is the time in which both
-// waves of a SIMD stand in the same phase (barrier, first reads, DMA issue): the case for de-phasing them.
+// to cover the first reads' latency (719 against 709). What is left between loop 1 and the MFMA floor, MEASURED (the stamped
+// instantiation, scripts/gemm_clock.py, 4000 back-to-back 4096^3 products on random normal data; profiles/gemm_bf16x3_loop2_before.txt):
+// the chip holds 1.67 GHz in this loop, not the 2.0 GHz assumed until then, and a k-tile takes 3640 shader cycles per CU against
+// the 3072 of the matrix pipe (2 waves per SIMD x 48 MFMAs x 32 cycles): 18.5 % of headroom, the time in which both waves of a
+// SIMD stand in the same phase (barrier, first reads, DMA issue).
+// Loop 2 (the default; bx2_tile) de-phases them: the two halves of the block run one segment apart, so that on every SIMD one wave
+// issues MFMAs while its partner reads fragments, stages and folds; four raw barriers per k-tile, no fence (DMAs stay in flight
+// across them), one step's fragments live at a time. Where the DMAs go decided it (one process, loop 1 / loop 2 interleaved, TFLOP/s
+// at 4096^3 and at 1024 x 4096 x 4096, split passes included; profiles/gemm_bf16x3_loop2_after.txt): four pieces behind the reads of
+// the first L segment and five behind the second's, whose vmcnt(0) then stands directly behind fresh DMAs, LOST (214 against 215.4;
+// 131 against 141; 3890 cycles per k-tile); all nine behind the first L's reads 218 against 216, 146 against 143.5; three there and
+// six between the MFMAs of the first C segment, one per four MFMAs, 225.6 against 216.5 and 158 against 144 (kept); five and four
+// (one per six), one and eight (one per three), none and nine (one per two), the fold in front of the DMAs, and static priority for
+// the second half all within the spread of that. So a C segment of MFMAs alone is not the point; a wait that no fresh DMA stands
+// in front of is.
 // Reduced products (option gemm_products 3 / 1 = ndarray.set_matmul_precision "high" / "medium"; the default 6 is everything above,
 // with unchanged machine code). The product list is ordered so that its prefixes are the cheaper forms: k_gemm_bf16xp<3> forms
 // a1b1 + a1b2 + a2b1 over two planes per operand, k_gemm_bf16xp<1> a1b1 over one. Their planes are ROUNDED (md_bf16x3_split_rn:
@@ -54,7 +67,7 @@
 // (2 NPROD 2^-23 + K / 32 x 2^-24) mass; integer operands whose sums stay below 2^24 give the integer product of the rounded planes
 // exactly (tests/test_matmul_precision.py). A permission, not a promise: what plan_bf16x3 does not take runs as under 6.
 // Measured (profiles/matmul_precision.txt, one process, arms interleaved), 4096^3 NN, us per product with its split passes / the
-// kernel alone / the MFMA floor at an assumed 2.0 GHz: six products 630 / 567 / 394, three 409 / 348 / 197, one 217 / 172 / 66; the
+// kernel alone / the MFMA floor at 2.0 GHz (assumed then; the six-product loop was later measured at 1.67 GHz): six products 630 / 567 / 394, three 409 / 348 / 197, one 217 / 172 / 66; the
 // fp32 fma chain 920. 2048^3: fp32 125, three 94, one 60. The fewer the products, the more the DMAs, reads, fold and barrier of a
 // k-tile weigh (8 MFMAs per wave against 3 pieces and 8 reads under one product): loop 1's order, a deeper k-tile and two blocks per
 // CU are not built.
@@ -262,6 +275,7 @@ struct Bx3Args {
   int64_t rs, a_kstep, b_kstep;   // the plane images (md_bf16x3_layout.h): bytes between rows, and between k-tiles of A / of B
   int tiles_m, tiles_n, gm; // gm: band height of the tile walk (md_bf16x3_tile)
   const unsigned *flag;     // the split passes' verdict: a non-zero word = nothing to do here (the fp32 kernel behind runs instead)
+  unsigned long long *stamp;   // diagnostic instantiation only (option gemm_stamp): per block {shader cycles, 100 MHz ticks} of its k loop
 };
 
 __device__ __forceinline__ const char *bx_uniform(const char *p) {
@@ -452,6 +466,87 @@ __device__ __forceinline__ void bx_tile(const Bx3Bufs &S, Bx3Src &src, const Bx3
   carry = part[1][1];
 }
 
+// ---- loop 2 ----------------------------------------------------------------------------------------------------------------------
+// The two halves of the block (waves 0 .. 3 and 4 .. 7: one wave of each per SIMD) run one segment apart. A k-tile is two k16 steps,
+// a step two segments: L — the step's 12 fragment reads, the wave's share of the next tile's DMAs and, in step 0, the fold of the
+// tile before — and C — its 24 MFMAs and nothing else. Every segment ends in a raw s_barrier (no fence: DMAs are in flight across
+// it); half 1 takes ONE barrier more in front of the loop and half 0 one behind it, so that in every slot each SIMD has one wave in
+// C and its partner in L, and both halves execute 4 nk + 1 barriers behind the prologue's. The arithmetic per output element is
+// bx_mma's: 12 accumulations per k-tile in the same order into a fresh accumulator, one round-to-nearest add into the running sum.
+// By count, with slots numbered so that half 0 runs L(j) in slot 2 j and C(j) in 2 j + 1, half 1 one slot later (j = 2 kt + s):
+//   WAR  the last read of tile kt - 1's buffer is half 1's L(2 kt - 1) in slot 4 kt - 1, retired by the lgkmcnt(0) in front of that
+//        slot's barrier; the DMAs of tile kt + 1 into that buffer issue in L(2 kt) and L(2 kt + 1), from slot 4 kt on;
+//   RAW  every wave takes vmcnt(0) at the end of its L(2 kt + 1) — slot 4 kt + 2 for half 0, 4 kt + 3 for half 1 — in front of the
+//        barrier; tile kt + 1 is first read in half 0's L(2 kt + 2), slot 4 kt + 4, behind the barrier that ends slot 4 kt + 3.
+// The barrier: the instruction between two scheduling fences and two compiler memory fences (no instruction of their own), so
+// that neither a fragment read nor an MFMA changes its segment.
+__device__ __forceinline__ void bx2_barrier() {
+  bx_fence();
+  asm volatile("" ::: "memory");
+  __builtin_amdgcn_s_barrier();
+  asm volatile("" ::: "memory");
+  bx_fence();
+}
+
+// One k-tile of loop 2: L(2 kt) B C(2 kt) B L(2 kt + 1) B C(2 kt + 1) B. part: the sum of the tile before on entry (folded in
+// L(2 kt), before C(2 kt) starts it afresh from a zero C operand), this tile's on return. The nine pieces of the next tile: three
+// behind L(2 kt)'s reads and six between the MFMAs of C(2 kt), one behind every fourth — none in L(2 kt + 1), whose vmcnt(0) then
+// waits for pieces that are a segment old or older (with pieces in both L segments and none in C the loop LOST to loop 1: the
+// header's table).
+template <bool STAGE>
+__device__ __forceinline__ void bx2_tile(const Bx3Bufs &S, Bx3Src &src, const Bx3Dst &dst, int64_t ka, int64_t kb, uint32_t lane_off, const uint32_t (&rd)[4],
+                                         bx_f32x16 (&acc)[2][2], bx_f32x16 (&part)[2][2]) {
+  constexpr int PA[6] = {0, 0, 1, 0, 1, 2}, PB[6] = {0, 1, 0, 2, 1, 0};
+  constexpr int NL = 3, CSTEP = 4;   // pieces in L(2 kt); one piece behind every CSTEP-th MFMA of C(2 kt), from its second
+#pragma unroll
+  for (int s = 0; s < 2; ++s) {
+    // L: one step's fragments live at a time (48 registers), read in the order the products first need them
+    bx_bf16x8 a[3][2], b[3][2];
+    uint32_t ra = rd[s], rb = rd[2 + s];
+    asm volatile("" : "+v"(ra), "+v"(rb));
+    a[0][0] = bx_frag_at(S.a[0], ra, 0); b[0][0] = bx_frag_at(S.b[0], rb, 0); b[0][1] = bx_frag_at(S.b[0], rb, 1); a[0][1] = bx_frag_at(S.a[0], ra, 1);
+    b[1][0] = bx_frag_at(S.b[1], rb, 0); b[1][1] = bx_frag_at(S.b[1], rb, 1);
+    a[1][0] = bx_frag_at(S.a[1], ra, 0); a[1][1] = bx_frag_at(S.a[1], ra, 1);
+    b[2][0] = bx_frag_at(S.b[2], rb, 0); b[2][1] = bx_frag_at(S.b[2], rb, 1);
+    a[2][0] = bx_frag_at(S.a[2], ra, 0); a[2][1] = bx_frag_at(S.a[2], ra, 1);
+    bx_fence();
+    if (s == 0) {
+      if (STAGE) {
+#pragma unroll
+        for (int n = 0; n < NL; ++n) bx_dma_n(src, dst, n, ka, kb, lane_off);
+      }
+      bx_fence();
+#pragma unroll
+      for (int t = 0; t < 4; ++t)
+#pragma unroll
+        for (int e = 0; e < 16; e += 4) bx_fold4(acc[t >> 1][t & 1], part[t >> 1][t & 1], e);
+      bx_fence();
+    }
+    // step 0: the reads are back before the barrier (WAR, and C holds no wait). Step 1: and so are this wave's nine pieces (RAW)
+    if (s == 0) __builtin_amdgcn_s_waitcnt(0xC07F);
+    else __builtin_amdgcn_s_waitcnt(0x0070);
+    bx2_barrier();
+    // C: product-major, consecutive MFMAs write different accumulators; every MFMA behind a fence, as in loop 1
+#pragma unroll
+    for (int q = 0; q < 6; ++q)
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          const int n = q * 4 + i * 2 + j;
+          if (s == 0 && q == 0) {
+            const bx_f32x16 zero = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+            part[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0][i], b[0][j], zero, 0, 0, 0);
+          } else {
+            part[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[PA[q]][i], b[PB[q]][j], part[i][j], 0, 0, 0);
+          }
+          if (STAGE && s == 0 && n % CSTEP == 1 && NL + n / CSTEP < 9) bx_dma_n(src, dst, NL + n / CSTEP, ka, kb, lane_off);
+          bx_fence();
+        }
+    bx2_barrier();
+  }
+}
+
 // The tile walk and the write-out of k_gemm_bf16x3 below, as functions for k_gemm_bf16xp (the six-product kernel keeps them in its
 // body: called from there they changed its register allocation). The block's tile:
 __device__ __forceinline__ void bx_origin(const Bx3Args &g, int64_t *m0, int64_t *n0) {
@@ -475,7 +570,10 @@ __device__ __forceinline__ void bx_write_c(const Bx3Args &g, int64_t m0, int64_t
       }
 }
 
-template <int LOOP>
+// STAMP: the diagnostic instantiation (option gemm_stamp, never launched otherwise) reads s_memtime / s_memrealtime before the first
+// DMA and behind the last fold and writes the differences to g.stamp, a buffer of their own that nothing else reads. The
+// instantiations without it hold no stamp and keep their machine code (profiles/gemm_bf16x3_stamp_isa.txt).
+template <int LOOP, bool STAMP = false>
 __global__ void __launch_bounds__(BX_NT) k_gemm_bf16x3(Bx3Args g) {
   __shared__ __attribute__((aligned(16))) char sA00[BX_BM * BX_ROWB];
   __shared__ __attribute__((aligned(16))) char sA01[BX_BM * BX_ROWB];
@@ -507,6 +605,11 @@ __global__ void __launch_bounds__(BX_NT) k_gemm_bf16x3(Bx3Args g) {
     for (int j = 0; j < 2; ++j)
 #pragma unroll
       for (int e = 0; e < 16; ++e) acc[i][j][e] = 0;
+  unsigned long long st_c = 0, st_r = 0;
+  if constexpr (STAMP) {
+    st_c = __builtin_amdgcn_s_memtime(); st_r = __builtin_amdgcn_s_memrealtime();
+    __builtin_amdgcn_s_waitcnt(0xC07F);   // (lgkmcnt(0) alone: the loop's counted LDS waits stay counted)
+  }
   if constexpr (LOOP == 0) {
     bx_stage<3>(g, m0, n0, 0, S0, lane_off);
     for (int kt = 0; kt < nk; kt += 2) {
@@ -536,27 +639,66 @@ __global__ void __launch_bounds__(BX_NT) k_gemm_bf16x3(Bx3Args g) {
       d1.b[p] = S1.b[p] + uw * 1024;
     }
     const uint32_t rd[4] = {bx_read_off(wm * 64, 0), bx_read_off(wm * 64, 1), bx_read_off(wn * 64, 0), bx_read_off(wn * 64, 1)};
-    // the sum carried into the first tile: +0 into a running sum that starts at +0 and is never -0 changes no bit
-    bx_f32x16 carry = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    if constexpr (LOOP == 1) {
+      // the sum carried into the first tile: +0 into a running sum that starts at +0 and is never -0 changes no bit
+      bx_f32x16 carry = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
-    for (int n = 0; n < 9; ++n) bx_dma_n(src, d0, n, 0, 0, lane_off);
-    int kt = 0;
-    for (; kt + 2 < nk; kt += 2) {   // whole pairs with a tile behind them: every tile of the loop stages the next one
-      __syncthreads();   // tile kt is in buffer 0 (the barrier's vmcnt(0) retires the DMAs); every wave is done with buffer 1
-      bx_tile<true>(S0, src, d1, ka, kb, lane_off, rd, acc, carry);
+      for (int n = 0; n < 9; ++n) bx_dma_n(src, d0, n, 0, 0, lane_off);
+      int kt = 0;
+      for (; kt + 2 < nk; kt += 2) {   // whole pairs with a tile behind them: every tile of the loop stages the next one
+        __syncthreads();   // tile kt is in buffer 0 (the barrier's vmcnt(0) retires the DMAs); every wave is done with buffer 1
+        bx_tile<true>(S0, src, d1, ka, kb, lane_off, rd, acc, carry);
+        __syncthreads();
+        bx_tile<true>(S1, src, d0, ka, kb, lane_off, rd, acc, carry);
+      }
       __syncthreads();
-      bx_tile<true>(S1, src, d0, ka, kb, lane_off, rd, acc, carry);
-    }
-    __syncthreads();
-    if (kt + 1 < nk) {
-      bx_tile<true>(S0, src, d1, ka, kb, lane_off, rd, acc, carry);
-      __syncthreads();
-      bx_tile<false>(S1, src, d0, 0, 0, lane_off, rd, acc, carry);
+      if (kt + 1 < nk) {
+        bx_tile<true>(S0, src, d1, ka, kb, lane_off, rd, acc, carry);
+        __syncthreads();
+        bx_tile<false>(S1, src, d0, 0, 0, lane_off, rd, acc, carry);
+      } else {
+        bx_tile<false>(S0, src, d1, 0, 0, lane_off, rd, acc, carry);
+      }
+#pragma unroll
+      for (int e = 0; e < 16; e += 4) bx_fold4(acc[1][1], carry, e);
     } else {
-      bx_tile<false>(S0, src, d1, 0, 0, lane_off, rd, acc, carry);
-    }
+      // loop 2: the prologue stages tile 0 whole; the only statements that depend on the half are the two barriers marked below
+      const int half = uw >> 2;   // (in an SGPR: a scalar branch)
+      bx_f32x16 part[2][2];   // +0 into a running sum that starts at +0 and is never -0 changes no bit: the first tile folds zeros
 #pragma unroll
-    for (int e = 0; e < 16; e += 4) bx_fold4(acc[1][1], carry, e);
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+          for (int e = 0; e < 16; ++e) part[i][j][e] = 0;
+#pragma unroll
+      for (int n = 0; n < 9; ++n) bx_dma_n(src, d0, n, 0, 0, lane_off);
+      __builtin_amdgcn_s_waitcnt(0x0070);
+      bx2_barrier();
+      if (half) bx2_barrier();   // HALF 1: one segment behind
+      int kt = 0;
+      for (; kt + 2 < nk; kt += 2) {   // whole pairs with a tile behind them, as loop 1: 8 barriers per trip
+        bx2_tile<true>(S0, src, d1, ka, kb, lane_off, rd, acc, part);
+        bx2_tile<true>(S1, src, d0, ka, kb, lane_off, rd, acc, part);
+      }
+      if (kt + 1 < nk) {
+        bx2_tile<true>(S0, src, d1, ka, kb, lane_off, rd, acc, part);
+        bx2_tile<false>(S1, src, d0, 0, 0, lane_off, rd, acc, part);
+      } else {
+        bx2_tile<false>(S0, src, d1, 0, 0, lane_off, rd, acc, part);
+      }
+#pragma unroll
+      for (int t = 0; t < 4; ++t)
+#pragma unroll
+        for (int e = 0; e < 16; e += 4) bx_fold4(acc[t >> 1][t & 1], part[t >> 1][t & 1], e);
+      if (!half) bx2_barrier();   // HALF 0: waits for its partners' last C (both halves: 4 nk + 1 barriers behind the prologue's)
+    }
+  }
+  if constexpr (STAMP) {
+    if (threadIdx.x == 0) {
+      g.stamp[2 * blockIdx.x] = __builtin_amdgcn_s_memtime() - st_c;
+      g.stamp[2 * blockIdx.x + 1] = __builtin_amdgcn_s_memrealtime() - st_r;
+    }
   }
   // accumulator element e of lane l: row (e & 3) + 8 (e >> 2) + 4 (l >> 5), column l & 31 of the 32 x 32 tile; one wave store writes
   // 32 consecutive floats of two rows (whole 128-B lines), as k_gemm_widen_mfma
@@ -645,7 +787,7 @@ int md_gemm_bf16x3_split(const float *src, bool k_contig, int64_t rows, int64_t 
 }
 
 int md_gemm_bf16x3(const void *a_planes, const void *b_planes, float *c, int64_t M, int64_t N, int64_t K, int64_t c_ms, const unsigned *flag, int loop,
-                   int layout, int band, int products) {
+                   int layout, int band, int products, unsigned long long *stamp) {
   Bx3Args a{};
   a.A = (const char *)a_planes; a.B = (const char *)b_planes; a.C = c;
   a.K = K; a.c_ms = c_ms;
@@ -654,11 +796,16 @@ int md_gemm_bf16x3(const void *a_planes, const void *b_planes, float *c, int64_t
   a.tiles_m = (int)(M / BX_BM); a.tiles_n = (int)(N / BX_BN);
   a.gm = md_bf16x3_band(a.tiles_m, MD_NUM_CUS / 8, band);   // (one block per CU: the CUs of an XCD hold that many tiles at a time)
   a.flag = flag;
+  a.stamp = stamp;
   md_opt_table()[MD_OPT_GEMM_BF16X3_RUNS] += 1;
   const dim3 grid((unsigned)(a.tiles_m * a.tiles_n));
   if (products == 1) MD_LAUNCH(k_gemm_bf16xp<1>, grid, BX_NT, a);
   else if (products == 3) MD_LAUNCH(k_gemm_bf16xp<3>, grid, BX_NT, a);
+  else if (stamp && loop == 0) MD_LAUNCH((k_gemm_bf16x3<0, true>), grid, BX_NT, a);
+  else if (stamp && loop == 2) MD_LAUNCH((k_gemm_bf16x3<2, true>), grid, BX_NT, a);
+  else if (stamp) MD_LAUNCH((k_gemm_bf16x3<1, true>), grid, BX_NT, a);
   else if (loop == 0) MD_LAUNCH(k_gemm_bf16x3<0>, grid, BX_NT, a);
+  else if (loop == 2) MD_LAUNCH(k_gemm_bf16x3<2>, grid, BX_NT, a);
   else MD_LAUNCH(k_gemm_bf16x3<1>, grid, BX_NT, a);
   return MD_LAUNCH_CHECK("matmul(f32 as bf16x3)");
 }

@@ -24,10 +24,11 @@ int md_gemm_widen_generic(const MdGemm &g, int dtype);
 // the product: C (M x N, c_ms floats between rows) from the planes, nothing when *flag != 0. layout: the plane image, the same for
 // the split passes and the product of one plan (md_bf16x3_layout.h: 0 [rows][K] | 1 k-tile-major); band: option gemm_bf16x3_band.
 // products: 6 (nplanes 3, the exact split) or the reduced forms 3 (nplanes 2) / 1 (nplanes 1) over rounded planes (option
-// gemm_products), which also raise the flag for a finite element that rounds to inf
+// gemm_products), which also raise the flag for a finite element that rounds to inf. stamp: null, or (option gemm_stamp, six
+// products only) 16 bytes per block for the diagnostic instantiation's clock stamps
 int md_gemm_bf16x3_split(const float *src, bool k_contig, int64_t rows, int64_t K, int64_t stride, void *planes, unsigned *flag, int layout, int nplanes);
 int md_gemm_bf16x3(const void *a_planes, const void *b_planes, float *c, int64_t M, int64_t N, int64_t K, int64_t c_ms, const unsigned *flag, int loop,
-                   int layout, int band, int products);
+                   int layout, int band, int products, unsigned long long *stamp);
 unsigned *md_tickets();                                   // MD_TICKET_WORDS zeroed counters (md_ticket.h)
 bool md_capturing();                                      // a stream capture is recording (mdhip_graph_begin .. _end)
 int *md_sticky();                                         // host-mapped word a CAPTURED gather / scatter sets on an out-of-bounds index

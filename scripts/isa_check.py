@@ -133,7 +133,7 @@ def report(obj=None):
     return res
 
 
-BF16X3_LOOP1 = "k_gemm_bf16x3ILi1EE"   # the loop-1 instantiation of gemm_bf16x3.hip's product kernel
+BF16X3_LOOP1 = "k_gemm_bf16x3ILi1ELb0EE"   # the loop-1 instantiation of gemm_bf16x3.hip's product kernel (<1, false>: without stamps)
 
 
 def vgpr_count(obj, frag):
@@ -157,27 +157,56 @@ def vgpr_count(obj, frag):
         shutil.rmtree(tmp, ignore_errors=True)
 
 
-def report_bf16x3(obj=None):
-    """Facts about loop 1 of k_gemm_bf16x3 (tests/test_isa_bf16x3.py): analyse()'s, and of the main loop the scalar multiplies, the
-    fold's adds by form and the explicit waits; the kernel's VGPR count."""
+BF16X3_LOOP2 = "k_gemm_bf16x3ILi2ELb0EE"   # loop 2: the two waves of a SIMD one segment apart
+
+
+def report_bf16x3(obj=None, frag=BF16X3_LOOP1):
+    """Facts about loop 1 of k_gemm_bf16x3 (tests/test_isa_bf16x3.py; `frag`: another instantiation): analyse()'s, and of the main
+    loop the scalar multiplies, the fold's adds by form and the explicit waits; the kernel's VGPR count."""
     obj = obj or os.path.join(ROOT, "minidiff_amd", "libmdhip.so")
-    ks = raw_kernels(disassemble(obj, (BF16X3_LOOP1,)))
-    names = [n for n in ks if BF16X3_LOOP1 in n]
+    ks = raw_kernels(disassemble(obj, (frag,)))
+    names = [n for n in ks if frag in n]
     if len(names) != 1:
-        raise RuntimeError(f"{len(names)} kernels match {BF16X3_LOOP1}")
+        raise RuntimeError(f"{len(names)} kernels match {frag}")
     res = analyse(names[0], ks[names[0]])
     _, body = main_loop(ks[names[0]])
     res["s_mul_loop"] = sum(1 for s in body if s.startswith("s_mul"))
     res["v_add_f32_loop"] = sum(1 for s in body if s.startswith("v_add_f32"))
     res["v_pk_add_f32_loop"] = sum(1 for s in body if s.startswith("v_pk_add_f32"))
     res["barrier_loop"] = sum(1 for s in body if s.startswith("s_barrier"))
-    res["vgprs"] = vgpr_count(obj, BF16X3_LOOP1)
+    res["vgprs"] = vgpr_count(obj, frag)
+    return res
+
+
+def report_bf16x3_loop2(obj=None):
+    """Facts about loop 2 of k_gemm_bf16x3 (tests/test_gemm_bf16x3_loop2.py): report_bf16x3()'s, and of the main loop, cut at its
+    barriers, what each segment holds — "segments": per segment (from the loop's head or a barrier to the next barrier) the MFMAs,
+    fragment reads, DMAs and adds in it — so that a test can see that every C segment is MFMAs alone. "loop1_present": loop 1's
+    kernel is still in the library."""
+    obj = obj or os.path.join(ROOT, "minidiff_amd", "libmdhip.so")
+    res = report_bf16x3(obj, BF16X3_LOOP2)
+    ks = raw_kernels(disassemble(obj, (BF16X3_LOOP2,)))
+    name = next(n for n in ks if BF16X3_LOOP2 in n)
+    _, body = main_loop(ks[name])
+    segs, cur = [], {"mfma": 0, "ds_read": 0, "dma": 0, "v_add_f32": 0}
+    for s in body:
+        if s.startswith("s_barrier"):
+            segs.append(cur)
+            cur = {"mfma": 0, "ds_read": 0, "dma": 0, "v_add_f32": 0}
+        for key, word in (("mfma", "v_mfma"), ("ds_read", "ds_read"), ("dma", "global_load_lds"), ("v_add_f32", "v_add_f32")):
+            cur[key] += s.startswith(word)
+    res["segments"] = segs
+    res["tail_after_last_barrier"] = cur   # (the loop's counter and branch: nothing of the four kinds)
+    res["loop1_present"] = len([n for n in raw_kernels(disassemble(obj, (BF16X3_LOOP1,))) if BF16X3_LOOP1 in n]) == 1
     return res
 
 
 if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "--bf16x3":
         print(report_bf16x3(sys.argv[2] if len(sys.argv) > 2 else None))
+        sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "--bf16x3-loop2":
+        print(report_bf16x3_loop2(sys.argv[2] if len(sys.argv) > 2 else None))
         sys.exit(0)
     r = report(sys.argv[1] if len(sys.argv) > 1 else None)
     for label, d in r.items():
