@@ -274,7 +274,9 @@ int mdhip_var(const mdhip_array *x, const mdhip_array *out, int32_t axis, int64_
  * Operands holding an inf or a NaN get the fma chain's result. Option gemm_bf16x3 = 0 (mdhip_debug_set_option, or
  * MDHIP_GEMM_BF16X3 under MDHIP_EXPERIMENTS=1) restores the fma chain everywhere. Storage-only triples: float16 @ float16 -> float16
  * (float32 accumulation, one rounding) and int8 @ int8 -> int8, uint8 @ uint8 -> uint8 (the low byte of the exact sum) run
- * on the low-precision MFMA (gemm_narrow.hip). Two triples keep the accumulator instead (np.matmul's dtype=): float16 @ float16 ->
+ * on the low-precision MFMA (gemm_narrow.hip); their thin (<= 8 rows or columns) and few-output long-k products run on the
+ * streaming kernels of skinny.hip, read in the operands' own type and summed in float32 / int32 (option gemm_narrow_skinny = 0:
+ * the conversion / generic routes instead). Two triples keep the accumulator instead (np.matmul's dtype=): float16 @ float16 ->
  * float32 and int8 @ int8 -> int32 (c has the wide dtype; the same kernels, stored without the final conversion). No other
  * storage-only dtype and no other mixed triple is accepted (MDHIP_ETYPE). */
 int mdhip_matmul(const mdhip_array *a, const mdhip_array *b, const mdhip_array *c);

@@ -1363,7 +1363,7 @@ struct GemmStep {   // only the steps in use are initialised (GemmPlan::add)
   int kind, dtype, cfg, staging, nbuf, splits, epi, skip;   // cfg: kTiles row (S_F64: 0 64x64, 1 128x128, 2 TN direct to LDS); skip: hand-off
   int dtype_to;                                             // S_NCONV: the destination's dtype
   bool a_kc, b_kc, edge, ct, stamp, wide;                   // ct: C^T-vector stores (c_vec_rows); stamp: clock stamps (diagnostic);
-                                                            // wide: S_NMFMA / S_NGENERIC store the carrier (float32 / int32 c)
+                                                            // wide: narrow hand-offs / S_NMFMA / S_NGENERIC store the carrier (float32 / int32 c)
   Tile tile;
   dim3 grid;
   GemmArgs ga;
@@ -1781,15 +1781,17 @@ static void plan_widened(GemmPlan &p, const MdGemm &g, int dtype, int wide, bool
   plan_gemm(p, w, wide);
   conv(w.c, wide, g.batch, M, N, M * N, N, 1, g.c, dtype, g.c_bs, g.c_ms, g.c_ns);
 }
-// float16 / int8 / uint8: the MFMA kernels (gemm_narrow.hip) for what they take, unless the product is thin (<= 8 rows or columns: the
-// streaming kernels of skinny.hip after a conversion) or float16 of a few tiles under a long k (split-k in the wide plan); small or odd-stride
-// products on the generic narrow kernel; the rest the widened route.
+// float16 / int8 / uint8: first the long-k and the thin hand-offs on the operands as they are (skinny.hip: few outputs under a long k, <= 8
+// rows or columns; option gemm_narrow_skinny = 0: never). What they decline is planned as before them: the MFMA kernels
+// (gemm_narrow.hip) for what they take, unless the product is thin (the float32 streaming kernels of skinny.hip after a conversion) or
+// float16 of a few tiles under a long k (split-k in the wide plan); small or odd-stride products on the generic narrow kernel; the rest
+// the widened route.
 // `wide_out`: float16 @ float16 -> float32, int8 @ int8 -> int32 (`dtype`: the operands') — the same choices with the carrier kept: the
 // wide-output MFMA / generic kernels of gemm_narrow.hip, or the widened route without its conversion back. The few-tile / long-k
 // cut-over is the narrow output's fit (same k loop; the 4-byte C adds to the epilogue only): profiles/gemm_bench_widen_few_tiles.txt shows
 // no shape slower than the conversion route beyond its run-to-run spread, so it was kept. Option gemm_widen = 0: the route a caller had
 // before — convert both operands, the wide plan — for every wide-output product with a k.
-static void plan_narrow(GemmPlan &p, const MdGemm &g, int dtype, bool wide_out) {
+static void plan_narrow_declined(GemmPlan &p, const MdGemm &g, int dtype, bool wide_out) {
   const int esz = dtype == MDHIP_F16 ? 2 : 1, wide = dtype == MDHIP_F16 ? MDHIP_F32 : MDHIP_I32;
   const NarrowLayout L = md_narrow_layout(g, esz);
   const int64_t blocks = ((g.M + 127) / 128) * ((g.N + 127) / 128) * g.batch;
@@ -1813,6 +1815,17 @@ static void plan_narrow(GemmPlan &p, const MdGemm &g, int dtype, bool wide_out) 
     return;
   }
   plan_widened(p, g, dtype, wide, wide_out);
+}
+static void plan_narrow(GemmPlan &p, const MdGemm &g, int dtype, bool wide_out) {
+  // (gemm_widen = 0 asks for the route a wide-output product had before any native one: no hand-off either)
+  const int handoffs = md_opt(MD_OPT_GEMM_NARROW_SKINNY) != 0 && g.K > 0 && (!wide_out || md_opt(MD_OPT_GEMM_WIDEN) != 0) ? 2 : 0;
+  const int h0 = p.n;
+  for (int h = 0; h < handoffs; ++h) {
+    GemmStep &s = p.add(h ? S_SKINNY : S_LONGK);
+    s.dtype = dtype; s.g = g; s.wide = wide_out;
+  }
+  plan_narrow_declined(p, g, dtype, wide_out);
+  for (int h = h0; h < h0 + handoffs; ++h) p.step[h].skip = p.n - h - 1;
 }
 // ---- run ---------------------------------------------------------------------------------------------------------------------------
 typedef void (*GemmKernel)(GemmArgs);
@@ -1872,7 +1885,7 @@ static int run_step(const GemmStep &s, const void *const *tmp, int *skip) {
   switch (s.kind) {
     case S_LONGK:
     case S_SKINNY: {
-      const int rc = s.kind == S_LONGK ? md_gemm_longk(g, s.dtype) : md_gemm_skinny(g, s.dtype);
+      const int rc = s.kind == S_LONGK ? md_gemm_longk(g, s.dtype, s.wide) : md_gemm_skinny(g, s.dtype, s.wide);
       *skip = rc < 0 ? 0 : s.skip;
       return rc < 0 ? MDHIP_OK : rc;
     }

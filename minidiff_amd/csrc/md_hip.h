@@ -10,8 +10,10 @@
 
 hipStream_t md_stream();
 struct MdGemm;
-int md_gemm_skinny(const MdGemm &g, int dtype);           // skinny.hip: thin products (matrix x vector ..); -1 = not applicable
-int md_gemm_longk(const MdGemm &g, int dtype);            // skinny.hip: both sides thin, k long (a dot product ..); -1 = not applicable
+// skinny.hip: thin products (matrix x vector ..) / both sides thin, k long (a dot product ..); -1 = not applicable. dtype: the
+// operands'; wide_out: float16 / int8 operands with a float32 / int32 c
+int md_gemm_skinny(const MdGemm &g, int dtype, bool wide_out = false);
+int md_gemm_longk(const MdGemm &g, int dtype, bool wide_out = false);
 // gemm_narrow.hip: float16 / int8 / uint8 products planned by gemm.hip (plan_narrow). mfma: a_kc / b_kc = the operand's k axis is
 // unit-stride (else its row axis is), edge = ragged tiles (zero: 16-B aligned zeros for the lanes outside the operands)
 int md_gemm_narrow_mfma(const MdGemm &g, int dtype, bool a_kc, bool b_kc, bool edge, const void *zero);

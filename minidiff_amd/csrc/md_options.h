@@ -39,6 +39,8 @@
   X(GEMM_F64_MFMA, "gemm_f64_mfma", 1, 'x')                                                                                     \
   X(GEMM_SKINNY, "gemm_skinny", 1, 'x')                /* 0: thin products stay on the MFMA / generic kernels */                \
   X(GEMM_WIDEN, "gemm_widen", 1, 'x')                  /* 0: float16 -> float32 / int8 -> int32 products convert their operands first (A/B) */ \
+  X(GEMM_NARROW_SKINNY, "gemm_narrow_skinny", 1, 'x')  /* 0: thin and long-k float16 / int8 / uint8 products keep the conversion / generic routes they had (A/B) */ \
+  X(GEMM_NARROW_THIN_RUNS, "gemm_narrow_thin_runs", 0, 'x') /* a COUNTER, as gemm_bf16x3_runs: the host adds 1 for every launch it ISSUES of a streaming / long-k kernel on float16 / int8 / uint8 operands (a long-k product is two launches) */ \
   X(GEMM_BF16X3, "gemm_bf16x3", 1, 'x')                /* large float32 products as six bf16 products of pre-split planes: 0 never | 1 above the size floors | 2 every shape the kernels take and whose fp32 plan is plain launches (tests) */ \
   X(GEMM_BF16X3_RUNS, "gemm_bf16x3_runs", 0, 'x')      /* a COUNTER kept in this table so that tests can read it (and, like any entry, write it): the host adds 1 when it ISSUES the bf16x3 product kernel — a graph replay does not count */ \
   X(GEMM_BF16X3_LOOP, "gemm_bf16x3_loop", 2, 'x')      /* k loop of the bf16x3 product kernel: 0 staging in front of the reads, fold behind the MFMAs | 1 staging and fold under the MFMAs | 2 (default) the two waves of a SIMD one segment apart, one in MFMAs while the other reads, stages and folds (same bits; A/B) */ \

@@ -17,12 +17,45 @@
 //                     published write-through and the block that arrives LAST at the strip's ticket adds them in band order
 //                     (md_ticket.h): one launch, fixed order, bit-identical run to run.
 // Algorithmic bytes: R * K * sizeof(T) per launch (the thin operand and the result are noise). float32 and float64.
+//
+// float16 / int8 / uint8 (the storage-only dtypes, planned by gemm.hip plan_narrow) run on the same kernels with a STORAGE type beside
+// the compute type: X is read as it lies (16-B loads: 8 float16 or 16 bytes per lane), sums and partials live in the carrier (float32 /
+// int32), results are stored in the operands' type (float16: one rounding to nearest even, overflow to inf; integers: the low byte) or
+// as the carrier itself (float16 -> float32, int8 -> int32). The kernels take such a product as T = MdThin<S, O>. Its multiply-adds are
+// the packed dot instructions (v_dot2c_f32_f16, v_dot4c_i32_i8: one instruction per dword of X and column), with the thin operand kept
+// packed in its own type beside X; at 16 B per lane load a convert + fma per element would be at (float16) or over (int8) the vector
+// issue rate at 8 columns. uint8 @ uint8 -> uint8 runs as int8: the low byte of a sum of products does not depend on how the operands'
+// top bit is read.
+#include <type_traits>
+
 #include "md_hip.h"
 
 extern "C" int mdhip_alloc(size_t, void **);
 extern "C" int mdhip_free(void *);
 
 namespace {
+
+template <class S_, class O_> struct MdThin {};   // in place of a kernel's T: operands stored as S_, results as O_
+template <class T> struct SkT {                   // S storage, C compute / partials, O output; NARROW: the packed-dot forms
+  typedef T S; typedef T C; typedef T O;
+  static constexpr bool NARROW = false;
+};
+template <class S_, class O_> struct SkT<MdThin<S_, O_>> {
+  typedef S_ S; typedef typename std::conditional<std::is_same<S_, _Float16>::value, float, int32_t>::type C; typedef O_ O;
+  static constexpr bool NARROW = true;
+};
+typedef uint32_t sk_u32x4 __attribute__((ext_vector_type(4)));
+typedef _Float16 sk_h2 __attribute__((ext_vector_type(2)));
+// one dword of X against one dword of the thin operand, both in the storage type: two float16 or four int8 products onto acc
+// (float16: every product is exact in float32; int8: the sum wraps modulo 2^32, unclamped)
+template <class S> __device__ __forceinline__ auto sk_dot(uint32_t x, uint32_t y, typename SkT<MdThin<S, S>>::C acc) {
+  if constexpr (std::is_same<S, _Float16>::value) return __builtin_amdgcn_fdot2(__builtin_bit_cast(sk_h2, x), __builtin_bit_cast(sk_h2, y), acc, false);
+  else return __builtin_amdgcn_sdot4((int)x, (int)y, acc, false);
+}
+template <class S> __device__ __forceinline__ uint32_t sk_bits(S v) {   // an element's bits, zero-extended
+  if constexpr (sizeof(S) == 2) return (uint32_t)__builtin_bit_cast(uint16_t, v);
+  else return (uint32_t)(uint8_t)v;
+}
 
 struct SkinnyArgs {
   const void *X, *Y;
@@ -53,20 +86,27 @@ template <class T> __device__ __forceinline__ T md_readlane(T v, int l) {   // l
 // The thin operand goes through LDS in k-chunks of KC elements, [c][k] so that a lane reads its V consecutive k of one column as one
 // 16-B ds_read. Two buffers: the global loads of chunk i + 1 are issued (into registers) before chunk i is multiplied and stored
 // behind it, so their latency hides under the X stream; one barrier per chunk.
-template <class T, int NCT, int RW>
+template <class TS, int NCT, int RW>
 __global__ void __launch_bounds__(256) k_skinny_rowdot(SkinnyArgs a) {
-  constexpr int V = 16 / sizeof(T);
-  constexpr int KC = 4096 / sizeof(T);          // 4 KiB of k per column and buffer
-  constexpr int PER = NCT * KC / 256;           // staged elements per thread and chunk
+  typedef typename SkT<TS>::S S;
+  typedef typename SkT<TS>::C T;
+  typedef typename SkT<TS>::O O;
+  constexpr bool NARROW = SkT<TS>::NARROW;
+  constexpr int V = 16 / sizeof(S);
+  constexpr int E = NARROW ? 4 / sizeof(S) : 1;   // elements per staged unit: the packed forms stage and store whole dwords
+  constexpr int KC = 4096 / sizeof(S);          // 4 KiB of k per column and buffer
+  constexpr int KU = KC / E;
+  constexpr int PER = NCT * KU / 256;           // staged units per thread and chunk
   constexpr int STEPS = KC / (64 * V);          // 16-B steps of a lane per chunk (4)
-  typedef MdVec<T, V> Vec;
-  __shared__ __attribute__((aligned(16))) T Ys[2][NCT][KC + V];   // (+ 16 B per row: the stores of one k for all c fall into different banks)
+  typedef MdVec<S, V> Vec;
+  typedef typename std::conditional<NARROW, uint32_t, S>::type Unit;
+  __shared__ __attribute__((aligned(16))) S Ys[2][NCT][KC + V];   // (+ 16 B per row: the stores of one k for all c fall into different banks)
   const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const T *X = (const T *)a.X + (int64_t)blockIdx.z * a.x_bs;
-  const T *Y = (const T *)a.Y + (int64_t)blockIdx.z * a.y_bs;
-  T *out = (T *)a.out + (int64_t)blockIdx.z * a.o_bs;
+  const S *X = (const S *)a.X + (int64_t)blockIdx.z * a.x_bs;
+  const S *Y = (const S *)a.Y + (int64_t)blockIdx.z * a.y_bs;
+  O *out = (O *)a.out + (int64_t)blockIdx.z * a.o_bs;
   const int64_t r0 = ((int64_t)blockIdx.x * 4 + w) * RW;
-  const T *xp[RW];
+  const S *xp[RW];
 #pragma unroll
   for (int i = 0; i < RW; ++i) {
     const int64_t r = r0 + i < a.R ? r0 + i : a.R - 1;   // rows past the end re-read the last row and store nothing
@@ -78,21 +118,57 @@ __global__ void __launch_bounds__(256) k_skinny_rowdot(SkinnyArgs a) {
 #pragma unroll
     for (int c = 0; c < NCT; ++c) acc[i][c] = (T)0;
   const bool y_along_k = a.yk == 1;   // Y rows contiguous along k (a vector, a few k-contiguous rows): threads run along k; else along c
-  T stage[PER];
+  // (packed forms) columns of Y that lie as whole 16-B pieces along k: staged four dwords at a time instead of element by element
+  const bool y_vec = NARROW && y_along_k && ((uintptr_t)Y & 15) == 0 && (a.nc == 1 || ((a.yc * (int64_t)sizeof(S)) & 15) == 0);
+  Unit stage[PER];
   auto fetch = [&](int64_t k0) {
+    if constexpr (NARROW) {
+      if (y_vec) {
+        static_assert(!NARROW || PER % 4 == 0, "a thread stages whole 16-B pieces");
+#pragma unroll
+        for (int u = 0; u < PER / 4; ++u) {
+          const int idx = threadIdx.x + u * 256;
+          const int c = idx / (KC / V), k = idx % (KC / V) * V;
+          sk_u32x4 v = {0u, 0u, 0u, 0u};
+          if (k0 + k < a.K && c < a.nc) v = *reinterpret_cast<const sk_u32x4 *>(Y + (k0 + k) + c * a.yc);   // (K % V == 0: whole pieces)
+          stage[4 * u] = v.x; stage[4 * u + 1] = v.y; stage[4 * u + 2] = v.z; stage[4 * u + 3] = v.w;
+        }
+        return;
+      }
+    }
 #pragma unroll
     for (int u = 0; u < PER; ++u) {
       const int idx = threadIdx.x + u * 256;
-      const int c = y_along_k ? idx / KC : idx % NCT, k = y_along_k ? idx % KC : idx / NCT;
-      stage[u] = (k0 + k < a.K && c < a.nc) ? Y[(k0 + k) * a.yk + c * a.yc] : (T)0;
+      const int c = y_along_k ? idx / KU : idx % NCT, k = y_along_k ? idx % KU : idx / NCT;
+      if constexpr (NARROW) {
+        uint32_t v = 0;
+#pragma unroll
+        for (int e = 0; e < E; ++e)
+          if (k0 + k * E + e < a.K && c < a.nc) v |= sk_bits(Y[(k0 + k * E + e) * a.yk + c * a.yc]) << (8 * sizeof(S) * e);
+        stage[u] = v;
+      } else {
+        stage[u] = (k0 + k < a.K && c < a.nc) ? Y[(k0 + k) * a.yk + c * a.yc] : (T)0;
+      }
     }
   };
   auto put = [&](int buf) {
+    if constexpr (NARROW) {
+      if (y_vec) {
+#pragma unroll
+        for (int u = 0; u < PER / 4; ++u) {
+          const int idx = threadIdx.x + u * 256;
+          const int c = idx / (KC / V), k = idx % (KC / V) * V;
+          *reinterpret_cast<sk_u32x4 *>(&Ys[buf][c][k]) = sk_u32x4{stage[4 * u], stage[4 * u + 1], stage[4 * u + 2], stage[4 * u + 3]};
+        }
+        return;
+      }
+    }
 #pragma unroll
     for (int u = 0; u < PER; ++u) {
       const int idx = threadIdx.x + u * 256;
-      const int c = y_along_k ? idx / KC : idx % NCT, k = y_along_k ? idx % KC : idx / NCT;
-      Ys[buf][c][k] = stage[u];
+      const int c = y_along_k ? idx / KU : idx % NCT, k = y_along_k ? idx % KU : idx / NCT;
+      if constexpr (NARROW) *reinterpret_cast<uint32_t *>(&Ys[buf][c][k * E]) = stage[u];
+      else Ys[buf][c][k] = stage[u];
     }
   };
   fetch(0);
@@ -114,13 +190,30 @@ __global__ void __launch_bounds__(256) k_skinny_rowdot(SkinnyArgs a) {
 #pragma unroll
     for (int st = 0; st < STEPS; ++st) {
       const int k = st * 64 * V + lane * V;
+      if constexpr (NARROW) {
+        sk_u32x4 xw[RW];
 #pragma unroll
-      for (int c = 0; c < NCT; ++c) {
-        const Vec y = *reinterpret_cast<const Vec *>(&Ys[buf][c][k]);
+        for (int i = 0; i < RW; ++i) {
+          xw[i] = __builtin_bit_cast(sk_u32x4, x[st][i]);
+          if (k >= kn) xw[i] = sk_u32x4{0u, 0u, 0u, 0u};   // (an inf or a NaN read past the end must not meet the staged zeros)
+        }
 #pragma unroll
-        for (int i = 0; i < RW; ++i)
+        for (int c = 0; c < NCT; ++c) {
+          const sk_u32x4 y = *reinterpret_cast<const sk_u32x4 *>(&Ys[buf][c][k]);
 #pragma unroll
-          for (int j = 0; j < V; ++j) acc[i][c] = fma(x[st][i].v[j], y.v[j], acc[i][c]);
+          for (int i = 0; i < RW; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[i][c] = sk_dot<S>(xw[i][j], y[j], acc[i][c]);
+        }
+      } else {
+#pragma unroll
+        for (int c = 0; c < NCT; ++c) {
+          const Vec y = *reinterpret_cast<const Vec *>(&Ys[buf][c][k]);
+#pragma unroll
+          for (int i = 0; i < RW; ++i)
+#pragma unroll
+            for (int j = 0; j < V; ++j) acc[i][c] = fma(x[st][i].v[j], y.v[j], acc[i][c]);
+        }
       }
     }
     if (more) put(buf ^ 1);
@@ -133,7 +226,7 @@ __global__ void __launch_bounds__(256) k_skinny_rowdot(SkinnyArgs a) {
     for (int c = 0; c < NCT; ++c) {
       T v = acc[i][c];
 #pragma unroll
-      for (int d = 32; d > 0; d >>= 1) v += md_shfl_down(v, d);
+      for (int d = 32; d > 0; d >>= 1) v = BAdd::apply(v, md_shfl_down(v, d));
       acc[i][c] = v;
     }
   if (lane == 0) {
@@ -142,23 +235,50 @@ __global__ void __launch_bounds__(256) k_skinny_rowdot(SkinnyArgs a) {
       if (r0 + i < a.R) {
 #pragma unroll
         for (int c = 0; c < NCT; ++c)
-          if (c < a.nc) out[(r0 + i) * a.o_r + c * a.o_c] = acc[i][c];
+          if (c < a.nc) out[(r0 + i) * a.o_r + c * a.o_c] = (O)acc[i][c];
       }
   }
 }
 
 // ------------------------------------------------------------------------------------------------ X r-contiguous
-template <class T, int NCT, int RB>
-__global__ void __launch_bounds__(256) k_skinny_colsum(SkinnyArgs a, int NS, int NB, T *partial, unsigned *tickets) {
-  constexpr int V = 16 / sizeof(T);
+// The packed forms (T = MdThin): a dot instruction multiplies E = 2 / 4 neighbours ALONG K, which lie in different rows of X here. A
+// batch's RB rows are regrouped in registers (v_perm_b32) into one dword per r holding its E rows, against E values of a column of Y packed the
+// same way: lane q * NCT + c loads and packs rows q * E .. q * E + E - 1 of column c, one v_readlane per group and column hands the
+// dword to the whole wave. Rows past a wave's last whole batch run as one more batch with zeros for the missing rows.
+template <class S, int E> __device__ __forceinline__ void sk_regroup(const sk_u32x4 *rows, uint32_t *xg) {   // rows[E] (16 B of r each) -> xg[16 / sizeof(S)]
+#pragma unroll
+  for (int d = 0; d < 4; ++d) {
+    if constexpr (E == 2) {
+      xg[2 * d] = __builtin_amdgcn_perm(rows[1][d], rows[0][d], 0x05040100u);
+      xg[2 * d + 1] = __builtin_amdgcn_perm(rows[1][d], rows[0][d], 0x07060302u);
+    } else {
+      const uint32_t lo01 = __builtin_amdgcn_perm(rows[1][d], rows[0][d], 0x05010400u), hi01 = __builtin_amdgcn_perm(rows[1][d], rows[0][d], 0x07030602u);
+      const uint32_t lo23 = __builtin_amdgcn_perm(rows[3][d], rows[2][d], 0x05010400u), hi23 = __builtin_amdgcn_perm(rows[3][d], rows[2][d], 0x07030602u);
+      xg[4 * d] = __builtin_amdgcn_perm(lo23, lo01, 0x05040100u);
+      xg[4 * d + 1] = __builtin_amdgcn_perm(lo23, lo01, 0x07060302u);
+      xg[4 * d + 2] = __builtin_amdgcn_perm(hi23, hi01, 0x05040100u);
+      xg[4 * d + 3] = __builtin_amdgcn_perm(hi23, hi01, 0x07060302u);
+    }
+  }
+}
+template <class TS, int NCT, int RB>
+__global__ void __launch_bounds__(256) k_skinny_colsum(SkinnyArgs a, int NS, int NB, TS *partial_, unsigned *tickets) {   // (partial_: carriers — TS itself unless TS = MdThin)
+  typedef typename SkT<TS>::S S;
+  typedef typename SkT<TS>::C T;
+  T *const partial = (T *)partial_;
+  typedef typename SkT<TS>::O O;
+  constexpr bool NARROW = SkT<TS>::NARROW;
+  constexpr int V = 16 / sizeof(S);
+  typedef MdVec<S, V> XVec;
   typedef MdVec<T, V> Vec;
-  __shared__ Vec sm[3][NCT][64];
+  typedef MdVec<O, V> OVec;
+  __shared__ Vec sm[NARROW ? 1 : 3][NCT][64];   // (the packed forms hold 32 / 64 B of sums per lane and column: one wave's at a time)
   __shared__ unsigned last_flag;
   const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int s = blockIdx.x % NS, b = blockIdx.x / NS;
-  const T *X = (const T *)a.X + (int64_t)blockIdx.z * a.x_bs;
-  const T *Y = (const T *)a.Y + (int64_t)blockIdx.z * a.y_bs;
-  T *out = (T *)a.out + (int64_t)blockIdx.z * a.o_bs;
+  const S *X = (const S *)a.X + (int64_t)blockIdx.z * a.x_bs;
+  const S *Y = (const S *)a.Y + (int64_t)blockIdx.z * a.y_bs;
+  O *out = (O *)a.out + (int64_t)blockIdx.z * a.o_bs;
   const int64_t col_raw = ((int64_t)s * 64 + lane) * V;
   const bool col_ok = col_raw < a.R;
   const int64_t col = col_ok ? col_raw : a.R - V;   // lanes past the edge load a valid vector and store nothing (R % V == 0, R >= V)
@@ -170,11 +290,66 @@ __global__ void __launch_bounds__(256) k_skinny_colsum(SkinnyArgs a, int NS, int
   for (int c = 0; c < NCT; ++c)
 #pragma unroll
     for (int j = 0; j < V; ++j) acc[c][j] = (T)0;
-  const T *p = X + col + first * a.xk;
+  const S *p = X + col + first * a.xk;
   const int64_t rstep = step * a.xk;
-  const T *yq = Y + first * a.yk;          // wave-uniform: the Y reads below are scalar loads
+  const S *yq = Y + first * a.yk;          // wave-uniform: the Y reads below are scalar loads
   const int64_t ystep = step * a.yk;
-  Vec t[2][RB];
+  if constexpr (NARROW) {
+    constexpr int E = 4 / sizeof(S), Q = RB / E;
+    static_assert(RB % E == 0 && Q * NCT <= 64, "a batch's packed Y values must fit one wave-wide load");
+    sk_u32x4 t[2][RB];
+    uint32_t ty[2];
+    const int yg = lane / NCT, yc_ = lane % NCT;
+    const bool y_lane = lane < Q * NCT && yc_ < a.nc;
+    // rows i0 .. i0 + RB - 1 of this wave; `part`: only rows below nrw exist (the others count as zeros)
+    auto load = [&](int buf, int64_t i0, auto part) {
+#pragma unroll
+      for (int u = 0; u < RB; ++u) {
+        if (!decltype(part)::value || i0 + u < nrw) t[buf][u] = *reinterpret_cast<const sk_u32x4 *>(p + (i0 + u) * rstep);
+        else t[buf][u] = sk_u32x4{0u, 0u, 0u, 0u};
+      }
+      uint32_t v = 0;
+#pragma unroll
+      for (int e = 0; e < E; ++e) {
+        const int64_t i = i0 + yg * E + e;
+        if (y_lane && (!decltype(part)::value || i < nrw)) v |= sk_bits(yq[i * ystep + yc_ * a.yc]) << (8 * sizeof(S) * e);
+      }
+      ty[buf] = v;
+    };
+    auto mac = [&](int buf) {
+#pragma unroll
+      for (int q = 0; q < Q; ++q) {
+        uint32_t xg[V];
+        sk_regroup<S, E>(&t[buf][q * E], xg);
+#pragma unroll
+        for (int c = 0; c < NCT; ++c) {
+          const uint32_t yv = md_readlane(ty[buf], q * NCT + c);
+#pragma unroll
+          for (int j = 0; j < V; ++j) acc[c][j] = sk_dot<S>(xg[j], yv, acc[c][j]);
+        }
+      }
+    };
+    if (nb > 0) {
+      load(0, 0, std::false_type{});
+      int64_t bt = 0;
+      for (; bt + 1 < nb; bt += 2) {
+        load(1, (bt + 1) * RB, std::false_type{});
+        __builtin_amdgcn_sched_barrier(0);
+        mac(0);
+        __builtin_amdgcn_sched_barrier(0);
+        load(0, (bt + 2 < nb ? bt + 2 : nb - 1) * RB, std::false_type{});   // a prefetch past the end re-reads the last batch (discarded)
+        __builtin_amdgcn_sched_barrier(0);
+        mac(1);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      if (bt < nb) mac(0);
+    }
+    if (nb * RB < nrw) {
+      load(0, nb * RB, std::true_type{});
+      mac(0);
+    }
+  } else {
+  XVec t[2][RB];
   T ty[2];   // the batch's RB x NCT values of Y, one per lane (lane = u * NCT + c): ONE vector load per batch, broadcast by v_readlane
   static_assert(RB * NCT <= 64, "a batch's Y values must fit one wave-wide load");
   const int yu = lane / NCT, yc_ = lane % NCT;
@@ -182,7 +357,7 @@ __global__ void __launch_bounds__(256) k_skinny_colsum(SkinnyArgs a, int NS, int
   auto load = [&](int buf, int64_t bt) {
     const int64_t i0 = (bt < nb ? bt : nb - 1) * RB;   // a prefetch past the end re-reads the last batch (discarded)
 #pragma unroll
-    for (int u = 0; u < RB; ++u) t[buf][u] = *reinterpret_cast<const Vec *>(p + (i0 + u) * rstep);
+    for (int u = 0; u < RB; ++u) t[buf][u] = *reinterpret_cast<const XVec *>(p + (i0 + u) * rstep);
     ty[buf] = y_lane ? yq[(i0 + yu) * ystep + yc_ * a.yc] : (T)0;
   };
   auto mac = [&](int buf, int64_t) {
@@ -212,7 +387,7 @@ __global__ void __launch_bounds__(256) k_skinny_colsum(SkinnyArgs a, int NS, int
     if (bt < nb) mac(0, bt);
   }
   for (int64_t i = nb * RB; i < nrw; ++i) {
-    const Vec tt = *reinterpret_cast<const Vec *>(p + i * rstep);
+    const XVec tt = *reinterpret_cast<const XVec *>(p + i * rstep);
     const T *yr = yq + i * ystep;
 #pragma unroll
     for (int c = 0; c < NCT; ++c) {
@@ -221,35 +396,59 @@ __global__ void __launch_bounds__(256) k_skinny_colsum(SkinnyArgs a, int NS, int
       for (int j = 0; j < V; ++j) acc[c][j] = fma(tt.v[j], yv, acc[c][j]);
     }
   }
-  // waves 1..3 -> wave 0, in wave order
-  if (w > 0) {
-#pragma unroll
-    for (int c = 0; c < NCT; ++c)
-#pragma unroll
-      for (int j = 0; j < V; ++j) sm[w - 1][c][lane].v[j] = acc[c][j];
   }
-  __syncthreads();
-  if (w == 0) {
+  // waves 1..3 -> wave 0, in wave order (the packed forms: through one wave's worth of LDS, a wave at a time)
+  auto fold_packed = [&]() {
 #pragma unroll
-    for (int q = 0; q < 3; ++q)
+    for (int q = 1; q < 4; ++q) {
+      if (q > 1) __syncthreads();
+      if (w == q) {
+#pragma unroll
+        for (int c = 0; c < NCT; ++c)
+#pragma unroll
+          for (int j = 0; j < V; ++j) sm[0][c][lane].v[j] = acc[c][j];
+      }
+      __syncthreads();
+      if (w == 0) {
+#pragma unroll
+        for (int c = 0; c < NCT; ++c)
+#pragma unroll
+          for (int j = 0; j < V; ++j) acc[c][j] = BAdd::apply(acc[c][j], sm[0][c][lane].v[j]);
+      }
+    }
+  };
+  if constexpr (NARROW) {
+    fold_packed();
+  } else {
+    if (w > 0) {
 #pragma unroll
       for (int c = 0; c < NCT; ++c)
 #pragma unroll
-        for (int j = 0; j < V; ++j) acc[c][j] += sm[q][c][lane].v[j];
+        for (int j = 0; j < V; ++j) sm[w - 1][c][lane].v[j] = acc[c][j];
+    }
+    __syncthreads();
+    if (w == 0) {
+#pragma unroll
+      for (int q = 0; q < 3; ++q)
+#pragma unroll
+        for (int c = 0; c < NCT; ++c)
+#pragma unroll
+          for (int j = 0; j < V; ++j) acc[c][j] += sm[q][c][lane].v[j];
+    }
   }
   auto store_out = [&]() {   // out[r][c], r = col + j
 #pragma unroll
     for (int c = 0; c < NCT; ++c)
       if (c < a.nc) {
         if (a.o_r == 1) {
-          Vec o;
+          OVec o;
 #pragma unroll
-          for (int j = 0; j < V; ++j) o.v[j] = acc[c][j];
-          T *dst = out + col + c * a.o_c;
-          if (((uintptr_t)dst & 15) == 0) { *reinterpret_cast<Vec *>(dst) = o; continue; }
+          for (int j = 0; j < V; ++j) o.v[j] = (O)acc[c][j];
+          O *dst = out + col + c * a.o_c;
+          if (((uintptr_t)dst & 15) == 0) { *reinterpret_cast<OVec *>(dst) = o; continue; }
         }
 #pragma unroll
-        for (int j = 0; j < V; ++j) out[(col + j) * a.o_r + c * a.o_c] = acc[c][j];
+        for (int j = 0; j < V; ++j) out[(col + j) * a.o_r + c * a.o_c] = (O)acc[c][j];
       }
   };
   if (NB == 1) {
@@ -280,39 +479,50 @@ __global__ void __launch_bounds__(256) k_skinny_colsum(SkinnyArgs a, int NS, int
     for (int c = 0; c < NCT; ++c) {
       const Vec pt = md_ld16_sc1<Vec>(pr, (unsigned)(((int64_t)r * plane + (int64_t)c * a.R + col) * (int64_t)sizeof(T)));
 #pragma unroll
-      for (int j = 0; j < V; ++j) acc[c][j] += pt.v[j];
+      for (int j = 0; j < V; ++j) {
+        if constexpr (md_is_float<T>::value) acc[c][j] += pt.v[j];
+        else acc[c][j] = BAdd::apply(acc[c][j], pt.v[j]);   // (integers wrap)
+      }
     }
   }
   __syncthreads();
-  if (w > 0) {
-#pragma unroll
-    for (int c = 0; c < NCT; ++c)
-#pragma unroll
-      for (int j = 0; j < V; ++j) sm[w - 1][c][lane].v[j] = acc[c][j];
-  }
-  __syncthreads();
-  if (w == 0 && col_ok) {
-#pragma unroll
-    for (int q = 0; q < 3; ++q)
+  if constexpr (NARROW) {
+    fold_packed();
+    if (w == 0 && col_ok) store_out();
+  } else {
+    if (w > 0) {
 #pragma unroll
       for (int c = 0; c < NCT; ++c)
 #pragma unroll
-        for (int j = 0; j < V; ++j) acc[c][j] += sm[q][c][lane].v[j];
-    store_out();
+        for (int j = 0; j < V; ++j) sm[w - 1][c][lane].v[j] = acc[c][j];
+    }
+    __syncthreads();
+    if (w == 0 && col_ok) {
+#pragma unroll
+      for (int q = 0; q < 3; ++q)
+#pragma unroll
+        for (int c = 0; c < NCT; ++c)
+#pragma unroll
+          for (int j = 0; j < V; ++j) acc[c][j] += sm[q][c][lane].v[j];
+      store_out();
+    }
   }
 }
 
 template <class T, int NCT> int launch_rowdot(const SkinnyArgs &a, int64_t batch) {
-  const int rw = a.R >= 8192 ? 4 : a.R >= 4096 ? 2 : 1;
+  constexpr int RWMAX = SkT<T>::NARROW && sizeof(typename SkT<T>::S) == 2 && NCT == 8 ? 2 : 4;   // (float16, 8 columns: four rows per wave spill)
+  const int rw = a.R >= 8192 && RWMAX == 4 ? 4 : a.R >= 4096 ? 2 : 1;
   const dim3 grid((unsigned)((a.R + 4 * rw - 1) / (4 * rw)), 1, (unsigned)batch);
-  if (rw == 4) MD_LAUNCH((k_skinny_rowdot<T, NCT, 4>), grid, 256, a);
+  if (rw == 4) MD_LAUNCH((k_skinny_rowdot<T, NCT, RWMAX>), grid, 256, a);   // (rw == 4 only where RWMAX is)
   else if (rw == 2) MD_LAUNCH((k_skinny_rowdot<T, NCT, 2>), grid, 256, a);
   else MD_LAUNCH((k_skinny_rowdot<T, NCT, 1>), grid, 256, a);
+  if (SkT<T>::NARROW) md_opt_table()[MD_OPT_GEMM_NARROW_THIN_RUNS] += 1;
   return MD_LAUNCH_CHECK("matmul(skinny, row dot)");
 }
 
-template <class T, int NCT> int launch_colsum(const SkinnyArgs &a, int64_t batch) {
-  constexpr int V = 16 / sizeof(T);
+template <class TS, int NCT> int launch_colsum(const SkinnyArgs &a, int64_t batch) {
+  typedef typename SkT<TS>::C T;   // (the partials' type)
+  constexpr int V = 16 / sizeof(typename SkT<TS>::S);
   const int64_t NS = (a.R + 64 * V - 1) / (64 * V);
   int64_t NB = (1024 + NS * batch - 1) / (NS * batch);   // ~1024 blocks
   if (NB > 64) NB = 64;
@@ -323,7 +533,8 @@ template <class T, int NCT> int launch_colsum(const SkinnyArgs &a, int64_t batch
   void *partial = nullptr;
   if (NB > 1) MD_TRY(mdhip_alloc((size_t)(batch * NB * NCT * a.R) * sizeof(T), &partial));
   const dim3 grid((unsigned)(NS * NB), 1, (unsigned)batch);
-  MD_LAUNCH((k_skinny_colsum<T, NCT, 8>), grid, 256, a, (int)NS, (int)NB, (T *)partial, md_tickets());
+  MD_LAUNCH((k_skinny_colsum<TS, NCT, 8>), grid, 256, a, (int)NS, (int)NB, (TS *)partial, md_tickets());
+  if (SkT<TS>::NARROW) md_opt_table()[MD_OPT_GEMM_NARROW_THIN_RUNS] += 1;
   int rc = MD_LAUNCH_CHECK("matmul(skinny, weighted column sum)");
   if (partial) mdhip_free(partial);   // stream-ordered
   return rc;
@@ -358,13 +569,15 @@ template <class T> __device__ __forceinline__ T longk_mac(T acc, T x, T y) {
   if constexpr (md_is_float<T>::value) return x * y + acc;   // (contracted to an fma)
   else return BAdd::apply(acc, BMul::apply(x, y));            // integers wrap, as NumPy's
 }
-template <class T, int TM, int TN>
+template <class TS, int TM, int TN>
 __global__ void __launch_bounds__(MD_BLOCK) k_longk_partial(LongKArgs g) {
+  typedef typename SkT<TS>::S S;   // (float16 / int8 operands are read as they lie and widened in registers)
+  typedef typename SkT<TS>::C T;
   __shared__ T red[MD_BLOCK / 64][TM * TN];
   const int tiles = g.tiles_m * g.tiles_n, bz = blockIdx.y / tiles, tile = blockIdx.y - bz * tiles;
   const int m0 = (tile / g.tiles_n) * TM, n0 = (tile % g.tiles_n) * TN;
-  const T *A = (const T *)g.A + (int64_t)bz * g.a_bs + (int64_t)m0 * g.a_ms;
-  const T *B = (const T *)g.B + (int64_t)bz * g.b_bs + (int64_t)n0 * g.b_ns;
+  const S *A = (const S *)g.A + (int64_t)bz * g.a_bs + (int64_t)m0 * g.a_ms;
+  const S *B = (const S *)g.B + (int64_t)bz * g.b_bs + (int64_t)n0 * g.b_ns;
   const int mm = g.M - m0, nn = g.N - n0;   // live rows / columns of this patch
   const int64_t k0 = (int64_t)blockIdx.x * g.chunk, k1 = k0 + g.chunk < g.K ? k0 + g.chunk : g.K;
   T acc[TM][TN];
@@ -375,9 +588,9 @@ __global__ void __launch_bounds__(MD_BLOCK) k_longk_partial(LongKArgs g) {
   for (int64_t k = k0 + threadIdx.x; k < k1; k += MD_BLOCK) {
     T a[TM], b[TN];
 #pragma unroll
-    for (int m = 0; m < TM; ++m) a[m] = m < mm ? A[m * g.a_ms + k * g.a_ks] : T(0);
+    for (int m = 0; m < TM; ++m) a[m] = m < mm ? (T)A[m * g.a_ms + k * g.a_ks] : T(0);
 #pragma unroll
-    for (int n = 0; n < TN; ++n) b[n] = n < nn ? B[k * g.b_ks + n * g.b_ns] : T(0);
+    for (int n = 0; n < TN; ++n) b[n] = n < nn ? (T)B[k * g.b_ks + n * g.b_ns] : T(0);
 #pragma unroll
     for (int m = 0; m < TM; ++m)
 #pragma unroll
@@ -404,8 +617,10 @@ __global__ void __launch_bounds__(MD_BLOCK) k_longk_partial(LongKArgs g) {
 // one block per patch: the 256 threads split into G = 256 / (TM TN) groups, group q adds the partials of blocks q, q + G, q + 2G, ..
 // for its output (independent loads; one thread walking 2048 dependent ones took 80 us), then the group sums are added in group
 // order — a fixed order, so the result is bit-identical run to run
-template <class T, int TM, int TN>
+template <class TS, int TM, int TN>
 __global__ void __launch_bounds__(MD_BLOCK) k_longk_finish(LongKArgs g) {
+  typedef typename SkT<TS>::C T;
+  typedef typename SkT<TS>::O O;
   constexpr int P = TM * TN, G = MD_BLOCK / P;
   __shared__ T sums[G][P];
   const int tiles = g.tiles_m * g.tiles_n, bz = blockIdx.x / tiles, tile = blockIdx.x - bz * tiles;
@@ -422,11 +637,12 @@ __global__ void __launch_bounds__(MD_BLOCK) k_longk_finish(LongKArgs g) {
     if (m < g.M && n < g.N) {
       T v = sums[0][threadIdx.x];
       for (int qq = 1; qq < G; ++qq) v = BAdd::apply(v, sums[qq][threadIdx.x]);
-      ((T *)g.C)[(int64_t)bz * g.c_bs + (int64_t)m * g.c_ms + (int64_t)n * g.c_ns] = v;
+      ((O *)g.C)[(int64_t)bz * g.c_bs + (int64_t)m * g.c_ms + (int64_t)n * g.c_ns] = (O)v;
     }
   }
 }
-template <class T, int TM, int TN> int longk_run(LongKArgs a, int64_t batch) {
+template <class TS, int TM, int TN> int longk_run(LongKArgs a, int64_t batch) {
+  typedef typename SkT<TS>::C T;
   a.tiles_m = (a.M + TM - 1) / TM;
   a.tiles_n = (a.N + TN - 1) / TN;
   const int64_t patches = batch * a.tiles_m * a.tiles_n;
@@ -441,8 +657,9 @@ template <class T, int TM, int TN> int longk_run(LongKArgs a, int64_t batch) {
   MD_TRY(mdhip_alloc((size_t)patches * a.nb * TM * TN * sizeof(T), &partial));
   a.partial = partial;
   hipStream_t st = md_stream();
-  MD_LAUNCH((k_longk_partial<T, TM, TN>), dim3((unsigned)a.nb, (unsigned)patches), MD_BLOCK, a);
-  k_longk_finish<T, TM, TN><<<(unsigned)patches, MD_BLOCK, 0, st>>>(a);
+  MD_LAUNCH((k_longk_partial<TS, TM, TN>), dim3((unsigned)a.nb, (unsigned)patches), MD_BLOCK, a);
+  k_longk_finish<TS, TM, TN><<<(unsigned)patches, MD_BLOCK, 0, st>>>(a);
+  if (SkT<TS>::NARROW) md_opt_table()[MD_OPT_GEMM_NARROW_THIN_RUNS] += 2;
   const int rc = MD_LAUNCH_CHECK("matmul(few outputs, long k)");
   mdhip_free(partial);
   return rc;
@@ -457,9 +674,21 @@ template <class T> int longk_dispatch(const LongKArgs &a, int64_t batch) {
 }
 }  // namespace
 
-// -1: not such a product; otherwise the launch status. dtype: MDHIP_F32 / F64 / I32 / I64.
-int md_gemm_longk(const MdGemm &g, int dtype) {
+// The element spec of a storage-only product: operands float16 / int8 / uint8, c of the same type or (wide_out) the carrier's.
+// f(spec) for the four that exist; uint8 -> uint8 is int8 -> int8 (the same low byte), uint8 has no wide form.
+template <class F> static int with_thin_spec(int dtype, bool wide_out, F &&f) {
+  if (dtype == MDHIP_F16) return wide_out ? f(MdThin<_Float16, float>{}) : f(MdThin<_Float16, _Float16>{});
+  if (dtype == MDHIP_I8) return wide_out ? f(MdThin<int8_t, int32_t>{}) : f(MdThin<int8_t, int8_t>{});
+  if (dtype == MDHIP_U8 && !wide_out) return f(MdThin<int8_t, int8_t>{});
+  return -1;
+}
+static bool md_thin_dtype(int dtype) { return dtype == MDHIP_F16 || dtype == MDHIP_I8 || dtype == MDHIP_U8; }
+
+// -1: not such a product; otherwise the launch status. dtype: MDHIP_F32 / F64 / I32 / I64, or (plan_narrow) the operands' F16 / I8 /
+// U8 with c of that type or, wide_out, of the carrier's (float32 / int32).
+int md_gemm_longk(const MdGemm &g, int dtype, bool wide_out) {
   if (!md_opt(MD_OPT_GEMM_SKINNY) || g.M < 1 || g.N < 1 || g.M > 128 || g.N > 128 || g.batch < 1) return -1;
+  if (md_thin_dtype(dtype) ? !md_opt(MD_OPT_GEMM_NARROW_SKINNY) : wide_out) return -1;
   const int64_t big = g.M > g.N ? g.M : g.N, small = g.M > g.N ? g.N : g.M;
   if (big <= 8) {
     if (g.K < 512) return -1;
@@ -467,7 +696,7 @@ int md_gemm_longk(const MdGemm &g, int dtype) {
     // larger outputs: only while k dwarfs them (the tile kernels would leave most of the chip idle); float32 from 64 x 64 up has the
     // MFMA split-k path
     if (g.K < 8192 || g.K < 64 * big) return -1;
-    if (dtype == MDHIP_F32 && small >= 64) return -1;
+    if ((dtype == MDHIP_F32 || dtype == MDHIP_F16) && small >= 64) return -1;
   }
   LongKArgs a{};
   a.A = g.a; a.B = g.b; a.C = g.c;
@@ -482,14 +711,16 @@ int md_gemm_longk(const MdGemm &g, int dtype) {
     case MDHIP_I32: return longk_dispatch<int32_t>(a, g.batch);
     case MDHIP_I64: return longk_dispatch<int64_t>(a, g.batch);
   }
-  return -1;
+  return with_thin_spec(dtype, wide_out, [&](auto spec) { return longk_dispatch<decltype(spec)>(a, g.batch); });
 }
 
 // -1: not a product for these kernels (the caller goes on to the MFMA / generic paths); otherwise the launch status.
-// dtype: MDHIP_F32 / MDHIP_F64.
-int md_gemm_skinny(const MdGemm &g, int dtype) {
-  if (!md_opt(MD_OPT_GEMM_SKINNY) || (dtype != MDHIP_F32 && dtype != MDHIP_F64) || g.batch < 1 || g.batch > 65535) return -1;
-  const int64_t esz = dtype == MDHIP_F32 ? 4 : 8, V = 16 / esz;
+// dtype: MDHIP_F32 / MDHIP_F64, or (plan_narrow) the operands' F16 / I8 / U8 with c of that type or, wide_out, of the carrier's.
+int md_gemm_skinny(const MdGemm &g, int dtype, bool wide_out) {
+  const bool thin = md_thin_dtype(dtype);
+  if (!md_opt(MD_OPT_GEMM_SKINNY) || (dtype != MDHIP_F32 && dtype != MDHIP_F64 && !thin) || g.batch < 1 || g.batch > 65535) return -1;
+  if (thin ? !md_opt(MD_OPT_GEMM_NARROW_SKINNY) || (wide_out && dtype == MDHIP_U8) : wide_out) return -1;
+  const int64_t esz = (int64_t)md_dtype_size(dtype), V = 16 / esz;
   SkinnyArgs a{};
   if (g.N <= 8 && g.M > 8) {          // thin N: X = A, Y = B, out = C
     a.X = g.a; a.Y = g.b; a.out = g.c;
@@ -513,5 +744,6 @@ int md_gemm_skinny(const MdGemm &g, int dtype) {
   if (a.xk == 1 && a.xr >= a.K && a.xr % V == 0 && a.K % V == 0) rowdot = true;
   else if (a.xr == 1 && a.xk >= a.R && a.xk % V == 0 && a.R % V == 0) rowdot = false;
   else return -1;
+  if (thin) return with_thin_spec(dtype, wide_out, [&](auto spec) { return skinny_run<decltype(spec)>(a, g.batch, rowdot); });
   return dtype == MDHIP_F32 ? skinny_run<float>(a, g.batch, rowdot) : skinny_run<double>(a, g.batch, rowdot);
 }
