@@ -31,9 +31,11 @@
 // two waves per SIMD. Each plane tile is staged ONCE per k-tile (global_load_lds_dwordx4: scalar base + 32-bit lane offset, a 1-KiB
 // piece = 16 rows per wave instruction, nine pieces per wave and k-tile) and serves all its products: per k16 step a wave reads 12
 // fragments (3 planes x 2 row blocks of A and of B, one ds_read_b128 each) for 24 MFMAs; 64 adds per wave fold a k-tile's sum into the running sum.
-// Three k loops in one build (template argument, option gemm_bf16x3_loop), the same bits from all. Loop 0 is the loop the kernel was
+// Four k loops in one build (template argument, option gemm_bf16x3_loop). Loops 0 - 2 agree bit for bit; loop 3 (the default, on the
+// 16x16x32 MFMA: SIX truncating accumulations of 32 terms per k-tile and element, where the others take twelve of 16) has bits of
+// its own, under the same contract. Loop 0 is the loop the kernel was
 // first measured with: all nine DMAs in front of the k-tile's reads, their addresses formed anew per k-tile, the fold behind the last
-// MFMA. Loop 1 (the default; bx_tile) forms the nine piece bases once and writes the k-tile's program order out, every MFMA behind a
+// MFMA. Loop 1 (bx_tile) forms the nine piece bases once and writes the k-tile's program order out, every MFMA behind a
 // scheduling fence with what issues in its shadow: one DMA, two fragment reads of step 1, or four of the fold's adds; step 1 runs
 // sub-tile by sub-tile so that a finished sub-tile's adds go under the next one's MFMAs, and the last sub-tile's sum is added under
 // the NEXT k-tile's first MFMAs. Measured (profiles/gemm_bf16x3_loop_after.txt): the kernel 604 min / 662 median us -> 573 / 625 us per
@@ -45,7 +47,7 @@
 // the chip holds 1.67 GHz in this loop, not the 2.0 GHz assumed until then, and a k-tile takes 3640 shader cycles per CU against
 // the 3072 of the matrix pipe (2 waves per SIMD x 48 MFMAs x 32 cycles): 18.5 % of headroom, the time in which both waves of a
 // SIMD stand in the same phase (barrier, first reads, DMA issue).
-// Loop 2 (the default; bx2_tile) de-phases them: the two halves of the block run one segment apart, so that on every SIMD one wave
+// Loop 2 (bx2_tile) de-phases them: the two halves of the block run one segment apart, so that on every SIMD one wave
 // issues MFMAs while its partner reads fragments, stages and folds; four raw barriers per k-tile, no fence (DMAs stay in flight
 // across them), one step's fragments live at a time. Where the DMAs go decided it (one process, loop 1 / loop 2 interleaved, TFLOP/s
 // at 4096^3 and at 1024 x 4096 x 4096, split passes included; profiles/gemm_bf16x3_loop2_after.txt): four pieces behind the reads of
@@ -55,6 +57,15 @@
 // (one per six), one and eight (one per three), none and nine (one per two), the fold in front of the DMAs, and static priority for
 // the second half all within the spread of that. So a C segment of MFMAs alone is not the point; a wait that no fresh DMA stands
 // in front of is.
+// Loop 3 (the default; bx3_tile, bx3_run) is loop 2 on v_mfma_f32_16x16x32_bf16: what loop 2 left was the clock, not the schedule
+// (3108 cycles per k-tile against the pipe's 3072, at 1.54 GHz held), and the chip holds a higher clock on the small shape. Same
+// halves, barriers, DMA placement and LDS bytes (24 ds_read_b128 per wave and k-tile); the wave tile as two 32 x 64 halves with
+// fresh accumulators, `part` of 32 registers, 240 VGPRs against 252; an LDS swizzle of its own (the 16-row read is 2-way on the
+// other loops' image). Measured (profiles/gemm_bf16x3_loop3_after.txt; stamped, 4000 back-to-back 4096^3 products on random normal
+// data): 3107 cycles per k-tile under either loop, 1.539 GHz under loop 2 and 1.701 GHz under loop 3, 608 -> 556 us per product
+// with its split passes; one process, the two loops interleaved, medians of 7 rounds in TFLOP/s, NN / NT / TN: 4096^3 226.4 /
+// 225.5 / 226.0 -> 247.1 / 246.9 / 248.5, 8192 x 4096 x 4096 231.1 / 232.8 / 233.3 -> 243.7 / 243.6 / 245.6, 1024 x 4096 x 4096
+// 155.0 / 155.1 / 154.9 -> 158.3 / 159.8 / 158.3, every arm's min - max spread 5.7 at the most.
 // Reduced products (option gemm_products 3 / 1 = ndarray.set_matmul_precision "high" / "medium"; the default 6 is everything above,
 // with unchanged machine code). The product list is ordered so that its prefixes are the cheaper forms: k_gemm_bf16xp<3> forms
 // a1b1 + a1b2 + a2b1 over two planes per operand, k_gemm_bf16xp<1> a1b1 over one. Their planes are ROUNDED (md_bf16x3_split_rn:
@@ -547,6 +558,113 @@ __device__ __forceinline__ void bx2_tile(const Bx3Bufs &S, Bx3Src &src, const Bx
   }
 }
 
+// ---- loop 3 ----------------------------------------------------------------------------------------------------------------------
+// Loop 2's halves and barriers on v_mfma_f32_16x16x32_bf16: one instruction covers the k-tile (K = 32), so an output sub-tile's whole
+// k-tile sum is SIX accumulations (a1b1, a1b2, a2b1, a1b3, a2b2, a3b1) into an accumulator that starts at zero, and the 64 x 64 wave
+// tile is formed as two 32 x 64 halves, one per C segment: C(2 kt) rows 0 .. 31, C(2 kt + 1) rows 32 .. 63, each 8 sub-tiles x 6
+// products = 48 MFMAs of 16 cycles (the 768 cycles of a C segment of loop 2). `part` is one half (32 registers): a half's sum is
+// folded into the running sum in the L segment behind its C segment, before the next C segment starts it afresh.
+// Reads, 24 ds_read_b128 per wave and k-tile as loop 2: L(2 kt) all of B (4 column blocks x 3 planes, live over both C segments)
+// and A rows 0 .. 31 (2 x 3); L(2 kt + 1) A rows 32 .. 63.
+// LDS image: lane l of a 16-row operand reads chunk l >> 4 of row l & 15. Under loop 0 - 2's slot c ^ ((r >> 2) & 3) the first
+// 16-lane group of ds_read_b128 (lanes 0 - 3, 12 - 15, 20 - 27: rows 0 - 3 and 12 - 15 at chunk 0, rows 4 - 11 at chunk 1) puts rows
+// 0 - 3 and 4 - 7 on the same banks, and rows 8 - 11 and 12 - 15: 2-way. Loop 3's slot is c ^ h((r >> 2) & 3) with h = 0, 2, 3, 1
+// (bx3_swz): every group then covers the 16 slots of 256 B once. Only the DMA's per-lane source offset and the read offsets differ.
+// By count, slots as in loop 2 (half 0 runs L(j) in slot 2 j and C(j) in 2 j + 1, half 1 one slot later):
+//   WAR  tile kt's buffer is read in L(2 kt) (18 reads) and L(2 kt + 1) (6 reads) and nowhere else: the last read is half 1's
+//        L(2 kt + 1) in slot 4 kt + 3, retired by the lgkmcnt(0) in front of that slot's barrier; the DMAs of tile kt + 2 into that
+//        buffer issue in L(2 kt + 2) and C(2 kt + 2), from slot 4 kt + 4 on;
+//   RAW  every wave takes vmcnt(0) at the end of its L(2 kt + 1) — slot 4 kt + 2 for half 0, 4 kt + 3 for half 1 — with no fresh
+//        DMA in front of it (the last piece went out in C(2 kt)); tile kt + 1 is first read in half 0's L(2 kt + 2), slot
+//        4 kt + 4, behind the barrier that ends slot 4 kt + 3.
+__device__ __forceinline__ uint32_t bx3_swz(int g) { return (0x78u >> (2 * g)) & 3u; }   // 0, 2, 3, 1
+
+// the lane's offset of row rb + (l & 15), chunk l >> 4; the 16-row block i of the wave's 64 rows lies i KiB further
+__device__ __forceinline__ uint32_t bx3_read_off(int rb) {
+  const int l = threadIdx.x & 63, r = rb + (l & 15), c = l >> 4;
+  return (uint32_t)(r * BX_ROWB + ((c ^ bx3_swz((r >> 2) & 3)) << 4));
+}
+__device__ __forceinline__ bx_bf16x8 bx3_frag_at(const char *S, uint32_t off, int i) {
+  return __builtin_bit_cast(bx_bf16x8, *(const bx_i32x4 *)(S + off + i * 16 * BX_ROWB));
+}
+
+// acc += part as four scalar adds, pinned where they stand (bx_fold4)
+__device__ __forceinline__ void bx3_fold4(bx_f32x4 &acc, const bx_f32x4 &part) {
+  float r0 = acc[0] + part[0], r1 = acc[1] + part[1], r2 = acc[2] + part[2], r3 = acc[3] + part[3];
+  asm volatile("" : "+v"(r0), "+v"(r1), "+v"(r2), "+v"(r3));
+  acc[0] = r0; acc[1] = r1; acc[2] = r2; acc[3] = r3;
+}
+
+// One k-tile of loop 3: L(2 kt) B C(2 kt) B L(2 kt + 1) B C(2 kt + 1) B. part: the sum of rows 32 .. 63 of the tile before on entry
+// (folded in L(2 kt)), of this tile's on return; rows 0 .. 31 are folded in L(2 kt + 1). The nine pieces as in loop 2: three behind
+// L(2 kt)'s reads, six between the MFMAs of C(2 kt), one behind every eighth (128 cycles apart, as there).
+template <bool STAGE>
+__device__ __forceinline__ void bx3_tile(const Bx3Bufs &S, Bx3Src &src, const Bx3Dst &dst, int64_t ka, int64_t kb, uint32_t lane_off, const uint32_t (&rd)[2],
+                                         bx_f32x4 (&acc)[4][4], bx_f32x4 (&part)[2][4]) {
+  constexpr int PA[6] = {0, 0, 1, 0, 1, 2}, PB[6] = {0, 1, 0, 2, 1, 0};
+  constexpr int NL = 3, CSTEP = 8;
+  bx_bf16x8 b[3][4];
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    bx_bf16x8 a[3][2];
+    uint32_t ra = rd[0], rb = rd[1];
+    asm volatile("" : "+v"(ra), "+v"(rb));
+    if (h == 0) {   // in the order the products first need them
+#pragma unroll
+      for (int i = 0; i < 2; ++i) a[0][i] = bx3_frag_at(S.a[0], ra, i);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) b[0][j] = bx3_frag_at(S.b[0], rb, j);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) b[1][j] = bx3_frag_at(S.b[1], rb, j);
+#pragma unroll
+      for (int i = 0; i < 2; ++i) a[1][i] = bx3_frag_at(S.a[1], ra, i);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) b[2][j] = bx3_frag_at(S.b[2], rb, j);
+#pragma unroll
+      for (int i = 0; i < 2; ++i) a[2][i] = bx3_frag_at(S.a[2], ra, i);
+    } else {
+#pragma unroll
+      for (int p = 0; p < 3; ++p)
+#pragma unroll
+        for (int i = 0; i < 2; ++i) a[p][i] = bx3_frag_at(S.a[p], ra, 2 + i);
+    }
+    bx_fence();
+    if (h == 0 && STAGE) {
+#pragma unroll
+      for (int n = 0; n < NL; ++n) bx_dma_n(src, dst, n, ka, kb, lane_off);
+    }
+    bx_fence();
+    // the half formed by the C segment before: rows 32 .. 63 (of the tile before) in L(2 kt), rows 0 .. 31 in L(2 kt + 1)
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) bx3_fold4(acc[2 * (1 - h) + i][j], part[i][j]);
+    bx_fence();
+    // L(2 kt): the reads are back before the barrier (WAR, and C holds no wait). L(2 kt + 1): and so are this wave's nine pieces (RAW)
+    if (h == 0) __builtin_amdgcn_s_waitcnt(0xC07F);
+    else __builtin_amdgcn_s_waitcnt(0x0070);
+    bx2_barrier();
+    // C: product-major over the eight sub-tiles, consecutive MFMAs write different accumulators; every MFMA behind a fence
+#pragma unroll
+    for (int q = 0; q < 6; ++q)
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int n = q * 8 + i * 4 + j;
+          if (q == 0) {
+            const bx_f32x4 zero = {0, 0, 0, 0};
+            part[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0][i], b[0][j], zero, 0, 0, 0);
+          } else {
+            part[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[PA[q]][i], b[PB[q]][j], part[i][j], 0, 0, 0);
+          }
+          if (STAGE && h == 0 && n % CSTEP == 1 && NL + n / CSTEP < 9) bx_dma_n(src, dst, NL + n / CSTEP, ka, kb, lane_off);
+          bx_fence();
+        }
+    bx2_barrier();
+  }
+}
+
 // The tile walk and the write-out of k_gemm_bf16x3 below, as functions for k_gemm_bf16xp (the six-product kernel keeps them in its
 // body: called from there they changed its register allocation). The block's tile:
 __device__ __forceinline__ void bx_origin(const Bx3Args &g, int64_t *m0, int64_t *n0) {
@@ -566,6 +684,86 @@ __device__ __forceinline__ void bx_write_c(const Bx3Args &g, int64_t m0, int64_t
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
         const int64_t m = m0 + wm * 64 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * (l >> 5), n = n0 + wn * 64 + j * 32 + (l & 31);
+        g.C[m * g.c_ms + n] = acc[i][j][e];
+      }
+}
+
+// Loop 3's body of k_gemm_bf16x3 behind the tile walk: its own lane offset (bx3_swz), sixteen 16 x 16 accumulators, loop 2's prologue,
+// pairs and tails over bx3_tile, and the write-out. Accumulator element e of lane l: row 4 (l >> 4) + e, column l & 15 of the
+// 16 x 16 sub-tile, so one wave store writes 16 consecutive floats (a 64-B half line) of four rows; the stores run along j, so that
+// the halves of a line (sub-tiles j, j + 1, same register) are written back to back.
+template <bool STAMP>
+__device__ __forceinline__ void bx3_run(const Bx3Args &g, const Bx3Bufs &S0, const Bx3Bufs &S1, int64_t m0, int64_t n0) {
+  const int wave = threadIdx.x >> 6, wm = wave >> 1, wn = wave & 1, l = threadIdx.x & 63;
+  const int nk = (int)(g.K / BX_BK);
+  const uint32_t lane_off = (uint32_t)((l >> 2) * g.rs + (((l & 3) ^ bx3_swz((l >> 4) & 3)) << 4));
+  bx_f32x4 acc[4][4], part[2][4];   // +0 into a running sum that starts at +0 and is never -0 changes no bit: the first tile folds zeros
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        acc[i][j][e] = 0;
+        if (i < 2) part[i][j][e] = 0;
+      }
+  unsigned long long st_c = 0, st_r = 0;
+  if constexpr (STAMP) {
+    st_c = __builtin_amdgcn_s_memtime(); st_r = __builtin_amdgcn_s_memrealtime();
+    __builtin_amdgcn_s_waitcnt(0xC07F);
+  }
+  const int uw = __builtin_amdgcn_readfirstlane(wave);
+  const int64_t rs = g.rs, ka = g.a_kstep, kb = g.b_kstep;
+  Bx3Src src;
+  Bx3Dst d0, d1;
+#pragma unroll
+  for (int p = 0; p < 3; ++p) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      src.a[p][i] = bx_uniform(g.A + p * g.a_plane + (m0 + 16 * (uw + 8 * i)) * rs);
+      d0.a[p][i] = S0.a[p] + (uw + 8 * i) * 1024;
+      d1.a[p][i] = S1.a[p] + (uw + 8 * i) * 1024;
+    }
+    src.b[p] = bx_uniform(g.B + p * g.b_plane + (n0 + 16 * uw) * rs);
+    d0.b[p] = S0.b[p] + uw * 1024;
+    d1.b[p] = S1.b[p] + uw * 1024;
+  }
+  const uint32_t rd[2] = {bx3_read_off(wm * 64), bx3_read_off(wn * 64)};
+  const int half = uw >> 2;   // (in an SGPR: a scalar branch)
+#pragma unroll
+  for (int n = 0; n < 9; ++n) bx_dma_n(src, d0, n, 0, 0, lane_off);
+  __builtin_amdgcn_s_waitcnt(0x0070);
+  bx2_barrier();
+  if (half) bx2_barrier();   // HALF 1: one segment behind
+  int kt = 0;
+  for (; kt + 2 < nk; kt += 2) {
+    bx3_tile<true>(S0, src, d1, ka, kb, lane_off, rd, acc, part);
+    bx3_tile<true>(S1, src, d0, ka, kb, lane_off, rd, acc, part);
+  }
+  if (kt + 1 < nk) {
+    bx3_tile<true>(S0, src, d1, ka, kb, lane_off, rd, acc, part);
+    bx3_tile<false>(S1, src, d0, 0, 0, lane_off, rd, acc, part);
+  } else {
+    bx3_tile<false>(S0, src, d1, 0, 0, lane_off, rd, acc, part);
+  }
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) bx3_fold4(acc[2 + i][j], part[i][j]);
+  if (!half) bx2_barrier();   // HALF 0: waits for its partners' last C (both halves: 4 nk + 1 barriers behind the prologue's)
+  if constexpr (STAMP) {
+    if (threadIdx.x == 0) {
+      g.stamp[2 * blockIdx.x] = __builtin_amdgcn_s_memtime() - st_c;
+      g.stamp[2 * blockIdx.x + 1] = __builtin_amdgcn_s_memrealtime() - st_r;
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int64_t m = m0 + wm * 64 + i * 16 + 4 * (l >> 4) + e, n = n0 + wn * 64 + j * 16 + (l & 15);
         g.C[m * g.c_ms + n] = acc[i][j][e];
       }
 }
@@ -595,6 +793,10 @@ __global__ void __launch_bounds__(BX_NT) k_gemm_bf16x3(Bx3Args g) {
   int tm, tn;
   md_bf16x3_tile(wg, g.tiles_m, g.tiles_n, g.gm, &tm, &tn);
   const int64_t m0 = (int64_t)tm * BX_BM, n0 = (int64_t)tn * BX_BN;
+  if constexpr (LOOP == 3) {   // (its own accumulators, swizzle and write-out: nothing below belongs to it)
+    bx3_run<STAMP>(g, S0, S1, m0, n0);
+    return;
+  }
   const int wave = threadIdx.x >> 6, wm = wave >> 1, wn = wave & 1, l = threadIdx.x & 63;
   const int nk = (int)(g.K / BX_BK);
   const uint32_t lane_off = (uint32_t)((l >> 2) * g.rs + (((l & 3) ^ ((l >> 4) & 3)) << 4));
@@ -803,9 +1005,11 @@ int md_gemm_bf16x3(const void *a_planes, const void *b_planes, float *c, int64_t
   else if (products == 3) MD_LAUNCH(k_gemm_bf16xp<3>, grid, BX_NT, a);
   else if (stamp && loop == 0) MD_LAUNCH((k_gemm_bf16x3<0, true>), grid, BX_NT, a);
   else if (stamp && loop == 2) MD_LAUNCH((k_gemm_bf16x3<2, true>), grid, BX_NT, a);
+  else if (stamp && loop == 3) MD_LAUNCH((k_gemm_bf16x3<3, true>), grid, BX_NT, a);
   else if (stamp) MD_LAUNCH((k_gemm_bf16x3<1, true>), grid, BX_NT, a);
   else if (loop == 0) MD_LAUNCH(k_gemm_bf16x3<0>, grid, BX_NT, a);
   else if (loop == 2) MD_LAUNCH(k_gemm_bf16x3<2>, grid, BX_NT, a);
+  else if (loop == 3) MD_LAUNCH(k_gemm_bf16x3<3>, grid, BX_NT, a);
   else MD_LAUNCH(k_gemm_bf16x3<1>, grid, BX_NT, a);
   return MD_LAUNCH_CHECK("matmul(f32 as bf16x3)");
 }

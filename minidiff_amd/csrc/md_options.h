@@ -43,7 +43,7 @@
   X(GEMM_NARROW_THIN_RUNS, "gemm_narrow_thin_runs", 0, 'x') /* a COUNTER, as gemm_bf16x3_runs: the host adds 1 for every launch it ISSUES of a streaming / long-k kernel on float16 / int8 / uint8 operands (a long-k product is two launches) */ \
   X(GEMM_BF16X3, "gemm_bf16x3", 1, 'x')                /* large float32 products as six bf16 products of pre-split planes: 0 never | 1 above the size floors | 2 every shape the kernels take and whose fp32 plan is plain launches (tests) */ \
   X(GEMM_BF16X3_RUNS, "gemm_bf16x3_runs", 0, 'x')      /* a COUNTER kept in this table so that tests can read it (and, like any entry, write it): the host adds 1 when it ISSUES the bf16x3 product kernel — a graph replay does not count */ \
-  X(GEMM_BF16X3_LOOP, "gemm_bf16x3_loop", 2, 'x')      /* k loop of the bf16x3 product kernel: 0 staging in front of the reads, fold behind the MFMAs | 1 staging and fold under the MFMAs | 2 (default) the two waves of a SIMD one segment apart, one in MFMAs while the other reads, stages and folds (same bits; A/B) */ \
+  X(GEMM_BF16X3_LOOP, "gemm_bf16x3_loop", 3, 'x')      /* k loop of the bf16x3 product kernel: 0 staging in front of the reads, fold behind the MFMAs | 1 staging and fold under the MFMAs | 2 the two waves of a SIMD one segment apart, one in MFMAs while the other reads, stages and folds | 3 (default) loop 2 on the 16x16x32 MFMA, the wave tile as two halves (loops 0 - 2 agree bit for bit; loop 3 has bits of its own: six truncating accumulations of 32 terms per k-tile, not twelve of 16; A/B) */ \
   X(GEMM_BF16X3_BAND, "gemm_bf16x3_band", 0, 'x')      /* tile walk of the bf16x3 product kernel, tile rows per band of an XCD's tiles: 0 by the CU count | 1 row-major | n forced (same bits; A/B) */ \
   X(GEMM_BF16X3_PLANES, "gemm_bf16x3_planes", 1, 'x')  /* image of the bf16x3 planes: 0 [rows][K] | 1 k-tile-major [K / 32][rows][64 B] (same bits; A/B) */ \
   X(GEMM_PRODUCTS, "gemm_products", 6, 'x')            /* plane products of a float32 product on the bf16 matrix cores: 6 full float32 accuracy | 3 a1b1 + a1b2 + a2b1 of two ROUNDED planes | 1 a1b1 of one (anything else: 6). A permission: what the reduced kernels do not take runs as under 6 (ndarray.set_matmul_precision) */ \

@@ -22,8 +22,9 @@ if os.environ.get("GEMM_GLDS_AB"):   # every config twice: register staging / di
     CFGS = {(99 if k == -1 else k) + 100 * g: v + (" +glds" if g else "") for k, v in CFGS.items() for g in (0, 1)}   # (99 = auto)
 if os.environ.get("GEMM_BF16X3_AB"):   # every config twice: fp32 fma chain / six bf16 products of pre-split planes on every eligible shape (option gemm_bf16x3)
     CFGS = {(99 if k == -1 else k) + 100000 * g: v + (" bf16x3" if g else " fp32") for k, v in CFGS.items() for g in (0, 1)}
-if os.environ.get("GEMM_BF16X3_LOOP_AB"):   # every config twice, on the six bf16 products wherever they are eligible: the product kernel's loop 1 / loop 2 (option gemm_bf16x3_loop, the digit of the encoding; same bits)
-    CFGS = {(99 if k == -1 else k) + 1000000 * g: v + " bf16x3 loop %d" % g for k, v in CFGS.items() for g in (1, 2)}
+if os.environ.get("GEMM_BF16X3_LOOP_AB"):   # every config twice, on the six bf16 products wherever they are eligible: the product kernel's loop 2 / loop 3 (option gemm_bf16x3_loop, the digit of the encoding; loop 3 has bits of its own, within the 5e-6 of round -1). GEMM_BF16X3_LOOP_AB=1,2: those loops instead
+    _loops = tuple(int(g) for g in os.environ["GEMM_BF16X3_LOOP_AB"].split(",")) if "," in os.environ["GEMM_BF16X3_LOOP_AB"] else (2, 3)
+    CFGS = {(99 if k == -1 else k) + 1000000 * g: v + " bf16x3 loop %d" % g for k, v in CFGS.items() for g in _loops}
 if os.environ.get("GEMM_BF16X3_LAYOUT_AB"):   # every config four times, on the six bf16 products wherever they are eligible: plane image [rows][K] / k-tile-major x tile walk row-major / banded (options gemm_bf16x3_planes, gemm_bf16x3_band; same bits)
     CFGS = {(99 if k == -1 else k) + 10000000 * g: v + " bf16x3 planes %d band %s" % (g >> 1, "auto" if g & 1 else "1") for k, v in CFGS.items() for g in (0, 1, 2, 3)}
 
@@ -104,7 +105,7 @@ def main():
             if os.environ.get("GEMM_BF16X3_LAYOUT_AB"):   # every round, in order: a cold first round shows as such
                 print("   %-22s rounds " % name + "  ".join("%s %s" % (t, " ".join("%.1f" % v for v in res[(cfg, t)])) for t in ("NN", "NT", "TN")))
             print("   %-22s " % name + "  ".join("%s med %6.1f min %6.1f max %6.1f TF" % (t, sorted(res[(cfg, t)])[len(res[(cfg, t)]) // 2], min(res[(cfg, t)]), max(res[(cfg, t)])) for t in (("NN", "NT", "TN", "TT") if os.environ.get("GEMM_TT") else ("NN", "NT", "TN"))))
-    opt("gemm_cfg", -1); opt("gemm_glds", 1); opt("gemm_nbuf", 0); opt("gemm_peel", 1); opt("gemm_bf16x3", 1); opt("gemm_bf16x3_loop", 2)
+    opt("gemm_cfg", -1); opt("gemm_glds", 1); opt("gemm_nbuf", 0); opt("gemm_peel", 1); opt("gemm_bf16x3", 1); opt("gemm_bf16x3_loop", 3)
     for name, v in layout_defaults.items():
         opt(name, v)
 

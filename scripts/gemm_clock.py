@@ -6,7 +6,8 @@ into a persistent buffer of their own (no sync behind the launches); the last la
   usage: gemm_clock.py N LAYOUT [launches [ROUTE]]
   ROUTE  auto (default: the library's choice) | fp32 (the fma chain: gemm_bf16x3 = 0) | bf16x3[:LOOP] (the six bf16 products on
          every shape the kernel takes, k loop LOOP: option gemm_bf16x3_loop; for these the exit line also gives the shader cycles
-         per k-tile and CU, to set against the 3072 the matrix pipe needs: 2 waves per SIMD x 48 MFMAs x 32 cycles)
+         per k-tile and CU, to set against the 3072 the matrix pipe needs: 2 waves per SIMD x 48 MFMAs x 32 cycles, or under
+         bf16x3:3 x 96 MFMAs x 16 cycles)
 Take >= 2 s of launches (a 4096^3 bf16x3 product is ~0.6 ms: 4000) so that the clock has settled where the chip holds it."""
 import os, sys
 os.environ["MDHIP_EXPERIMENTS"] = "1"   # the library reads experiment variables only behind this gate

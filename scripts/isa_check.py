@@ -178,15 +178,16 @@ def report_bf16x3(obj=None, frag=BF16X3_LOOP1):
     return res
 
 
-def report_bf16x3_loop2(obj=None):
-    """Facts about loop 2 of k_gemm_bf16x3 (tests/test_gemm_bf16x3_loop2.py): report_bf16x3()'s, and of the main loop, cut at its
+def report_bf16x3_loop2(obj=None, frag=BF16X3_LOOP2):
+    """Facts about loop 2 of k_gemm_bf16x3 (tests/test_gemm_bf16x3_loop2.py; `frag`: another instantiation with its barriers):
+    report_bf16x3()'s, and of the main loop, cut at its
     barriers, what each segment holds — "segments": per segment (from the loop's head or a barrier to the next barrier) the MFMAs,
     fragment reads, DMAs and adds in it — so that a test can see that every C segment is MFMAs alone. "loop1_present": loop 1's
     kernel is still in the library."""
     obj = obj or os.path.join(ROOT, "minidiff_amd", "libmdhip.so")
-    res = report_bf16x3(obj, BF16X3_LOOP2)
-    ks = raw_kernels(disassemble(obj, (BF16X3_LOOP2,)))
-    name = next(n for n in ks if BF16X3_LOOP2 in n)
+    res = report_bf16x3(obj, frag)
+    ks = raw_kernels(disassemble(obj, (frag,)))
+    name = next(n for n in ks if frag in n)
     _, body = main_loop(ks[name])
     segs, cur = [], {"mfma": 0, "ds_read": 0, "dma": 0, "v_add_f32": 0}
     for s in body:
@@ -201,7 +202,25 @@ def report_bf16x3_loop2(obj=None):
     return res
 
 
+BF16X3_LOOP3 = "k_gemm_bf16x3ILi3ELb0EE"   # loop 3: loop 2's halves on the 16x16x32 MFMA
+
+
+def report_bf16x3_loop3(obj=None):
+    """Facts about loop 3 of k_gemm_bf16x3 (tests/test_gemm_bf16x3_loop3.py): report_bf16x3_loop2()'s for that instantiation, and the
+    main loop's MFMAs by shape ("mfma_16x16x32_loop", "mfma_32x32x16_loop")."""
+    obj = obj or os.path.join(ROOT, "minidiff_amd", "libmdhip.so")
+    res = report_bf16x3_loop2(obj, BF16X3_LOOP3)
+    ks = raw_kernels(disassemble(obj, (BF16X3_LOOP3,)))
+    _, body = main_loop(ks[next(n for n in ks if BF16X3_LOOP3 in n)])
+    res["mfma_16x16x32_loop"] = sum(1 for s in body if s.startswith("v_mfma_f32_16x16x32_bf16"))
+    res["mfma_32x32x16_loop"] = sum(1 for s in body if s.startswith("v_mfma_f32_32x32x16_bf16"))
+    return res
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "--bf16x3-loop3":
+        print(report_bf16x3_loop3(sys.argv[2] if len(sys.argv) > 2 else None))
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "--bf16x3":
         print(report_bf16x3(sys.argv[2] if len(sys.argv) > 2 else None))
         sys.exit(0)
