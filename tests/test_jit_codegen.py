@@ -1,7 +1,10 @@
 """Run-time specialisation of fused programs: the generated HIP source must
 compile for gfx950 (hiprtc, no device needed) for every operator and epilogue the
-interpreter accepts. Numerical parity of the compiled kernels is covered on the
-GPU by running the lazy suites with MDHIP_JIT_MIN=1 (tests/test_lazy_fusion.py)."""
+interpreter accepts. Numerical parity of the compiled base forms (eval, full /
+column reduce, strips, multi-output) is covered on the GPU by
+tests/test_fused_paths.py, which runs every entry through the generated kernels
+(jit_min = 1) and through the interpreter; the later forms by test_fused_rows.py,
+test_fused_axis.py and test_jit_axes.py."""
 import ctypes as C
 import os
 
