@@ -29,10 +29,8 @@
 #include <vector>
 
 #include "md_hip.h"
+#include "md_strips.h"
 #include "md_vm.h"
-
-extern "C" int mdhip_alloc(size_t, void **);
-extern "C" int mdhip_free(void *);
 
 namespace {
 
@@ -712,10 +710,8 @@ static bool sweep_geometry(int64_t n_out, int64_t n_red, int ru, int64_t *NS, in
   if ((n_out & 3) || n_out < 4 || n_red < 512) return false;
   const int nb_force = (int)md_opt(MD_OPT_SWEEP_NB);
   const int64_t ns = (n_out + 255) / 256, nse = ns * outer;
-  int64_t nb = nb_force > 0 ? nb_force : (nse >= MD_NUM_CUS ? 1 : MD_NUM_CUS / nse);
-  if (nb > 64) nb = 64;
-  if (nb > n_red / (4 * ru)) nb = n_red / (4 * ru);
-  if (nb < 1) nb = 1;
+  // one block per CU, as the column sums of reduce.hip; option sweep_nb forces the count (still clamped)
+  int64_t nb = nb_force > 0 ? md_strips_bands(1, nb_force, MD_FLOOR, n_red, 4 * ru) : md_strips_bands(nse, MD_NUM_CUS, MD_FLOOR, n_red, 4 * ru);
   if (outer > 1 && nb > 1 && (nse * MD_TICKET_PAD > MD_TICKET_WORDS || nb * n_out * (int64_t)sizeof(double) >= (1ll << 32))) nb = 1;
   if (ns * nb >= (1ll << 31) || (nb > 1 && ns * MD_TICKET_PAD > MD_TICKET_WORDS)) return false;
   *NS = ns;

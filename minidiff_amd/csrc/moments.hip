@@ -6,16 +6,16 @@
 //   rows    (the reduced axis is the contiguous one): a row of up to 16 Ki elements is read ONCE into registers — sum, mean (a true
 //           division, as NumPy), centred squares, all from the registers; longer rows are read twice (the second time from cache);
 //   columns (axis 0 of a row-major matrix): the column sums by mdhip_reduce's strips kernel, then one more strips walk that adds
-//           (x - mean)^2 — two reads, the last block of a strip folds the band partials in band order and finishes the division;
+//           (x - mean)^2 — two reads, the last block of a strip folds the band partials in band order and finishes the division
+//           (the band count is md_strips.h's, as for every strips walk; the scratch blocks live in an MdScratch);
 //   a middle axis ((outer, n, inner) with inner contiguous: the statistics of a normalisation over the sequence axis): `outer`
 //           independent column problems — the batched column sums of mdhip_reduce, then ONE batched launch of the same second walk
 //           (the batch on blockIdx.y, per-batch offsets into x, the sums, the partial rows, the ticket words and out).
 // Same arithmetic as NumPy up to the order of the two sums (no Welford update, no E[x^2] - mean^2 cancellation). HBM-bound:
 // algorithmic bytes = one read of x.
 #include "md_hip.h"
+#include "md_strips.h"
 
-extern "C" int mdhip_alloc(size_t, void **);
-extern "C" int mdhip_free(void *);
 extern "C" int mdhip_reduce(int op, const mdhip_array *x, const mdhip_array *out, uint32_t axis_mask);
 
 namespace {
@@ -266,8 +266,9 @@ template <class T> int var_rows(const T *x, int64_t n_rows, int64_t n, T *out, T
 // `outer` column problems of n_red x n_out, n_red * n_out elements apart (outer == 1: the 2-D form).
 template <class T> int var_cols(const void *xdata, int64_t outer, int64_t n_red, int64_t n_out, T *out, T denom, int take_sqrt, int dtype) {
   constexpr int V = 16 / sizeof(T);
-  void *csum = nullptr;
-  MD_TRY(mdhip_alloc((size_t)(outer * n_out) * sizeof(T), &csum));
+  MdScratch scratch;   // (freed on every way out, stream-ordered behind the launches)
+  void *csum, *partial;
+  MD_TRY(scratch.get((size_t)(outer * n_out) * sizeof(T), &csum));
   mdhip_array xd{}, sd{};
   xd.data = const_cast<void *>(xdata); xd.dtype = dtype;
   sd.data = csum; sd.dtype = dtype;
@@ -281,28 +282,20 @@ template <class T> int var_cols(const void *xdata, int64_t outer, int64_t n_red,
     sd.ndim = 3; sd.shape[0] = outer; sd.shape[1] = 1; sd.shape[2] = n_out; sd.strides[0] = n_out; sd.strides[1] = n_out; sd.strides[2] = 1;
     mask = 1u << 1;
   }
-  int rc = mdhip_reduce(MDHIP_R_SUM, &xd, &sd, mask);
-  if (rc != MDHIP_OK) { mdhip_free(csum); return rc; }
+  MD_TRY(mdhip_reduce(MDHIP_R_SUM, &xd, &sd, mask));
   const int64_t NS = (n_out + 64 * V - 1) / (64 * V);
-  // 2-D: ~1024 blocks; batched: one block per CU, as the batched column sums
-  int64_t NB = outer == 1 ? (1024 + NS - 1) / NS : (NS * outer >= MD_NUM_CUS ? 1 : MD_NUM_CUS / (NS * outer));
-  if (NB > 64) NB = 64;
-  if (NB > n_red / 32) NB = n_red / 32;
-  if (NB < 1) NB = 1;
-  if (NS * outer * MD_TICKET_PAD > MD_TICKET_WORDS) NB = 1;
-  while (NB > 1 && NB * n_out * (int64_t)sizeof(T) >= (1ll << 31)) NB /= 2;   // (32-bit byte offsets into a batch's partial rows)
-  void *partial = nullptr;
-  if (NB > 1) {
-    rc = mdhip_alloc((size_t)(outer * NB * n_out) * sizeof(T), &partial);
-    if (rc != MDHIP_OK) { mdhip_free(csum); return rc; }
-  }
+  // 2-D: ~1024 blocks (rounded up); batched: one block per CU (rounded down), as the batched column sums
+  int64_t NB = outer == 1 ? md_strips_bands(NS, 1024, MD_CEIL, n_red, 32) : md_strips_bands(NS * outer, MD_NUM_CUS, MD_FLOOR, n_red, 32);
+  if (NS * outer * MD_TICKET_PAD > MD_TICKET_WORDS) NB = 1;   // more strips than ticket words: one band (a plain column sum declines instead)
+  while (NB > 1 && NB * n_out * (int64_t)sizeof(T) >= (1ll << 31)) NB /= 2;   // (32-bit byte offsets into a batch's partial rows of T)
+  MD_TRY(scratch.get(NB > 1 ? (size_t)(outer * NB * n_out) * sizeof(T) : 0, &partial));
+  // from one batch to the next: elements in x, in the sums and out, in the partial rows (2-D: one batch, no steps)
+  struct { int64_t x, o, p; } step = {0, 0, 0};
+  if (outer > 1) step = {n_red * n_out, n_out, NB * n_out};
   const dim3 grid((unsigned)(NS * NB), (unsigned)outer);
   MD_LAUNCH((k_var_cols<T, 8>), grid, 256, (const T *)xdata, (const T *)csum, n_out, n_red, (int)NS, (int)NB, (T *)partial, md_tickets(), out, denom, take_sqrt,
-            outer == 1 ? (int64_t)0 : n_red * n_out, outer == 1 ? (int64_t)0 : n_out, outer == 1 ? (int64_t)0 : NB * n_out);
-  rc = MD_LAUNCH_CHECK(outer == 1 ? "var(cols)" : "var(cols,batched)");
-  if (partial) mdhip_free(partial);
-  mdhip_free(csum);   // stream-ordered
-  return rc;
+            step.x, step.o, step.p);
+  return MD_LAUNCH_CHECK(outer == 1 ? "var(cols)" : "var(cols,batched)");
 }
 
 }  // namespace

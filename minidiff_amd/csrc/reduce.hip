@@ -17,11 +17,15 @@
 //          lanes read neighbouring addresses (coalesced); rows are split over
 //          gridDim.y into partials [split][n_out] + a finishing pass.
 //   generic : one lane per output, div/mod walk — small or oddly strided inputs.
+//
+// Host side (the end of the file): plan_reduce / plan_arg choose ONE launch form (enum RedForm) and its numbers, without
+// allocating or launching; run_reduce<R,Tacc,To> / run_arg<IsMax,T> are one switch over the form — scratch (MdScratch), launch,
+// check. The route of a call is the order of the tests in its planner. The band count of the strips walk is md_strips.h's.
+#include <type_traits>
+
 #include "md_hip.h"
 #include "md_narrow.h"
-
-extern "C" int mdhip_alloc(size_t, void **);
-extern "C" int mdhip_free(void *);
+#include "md_strips.h"
 
 namespace {
 
@@ -901,348 +905,443 @@ __global__ void __launch_bounds__(MD_BLOCK) k_anyall_flat(const T *__restrict__ 
   }
 }
 
+// ------------------------------------------------------------------- host: plan, then run ------
+// plan_reduce / plan_arg read the collapsed plan, the dtypes, the alignment of the two base addresses and md_opt, and describe ONE
+// launch form in a RedLaunch; they allocate nothing and launch nothing. run_reduce / run_arg are one switch over the form: allocate
+// what the description names, launch, check, free. The order of the tests in a planner is the route: the first form whose
+// predicate holds is taken, and where one form shadows another the comment at it says why.
 static int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
-template <bool ANY, class T> static int anyall_flat(const mdhip_array *x, int64_t n, const mdhip_array *out) {
-  int64_t blocks = ceil_div(n * (int64_t)sizeof(T), 64 * 1024);   // >= 64 KiB per block
-  if (blocks > 4 * MD_NUM_CUS) blocks = 4 * MD_NUM_CUS;
-  if (blocks < 1) blocks = 1;
-  void *partial = nullptr;
-  if (blocks > 1) MD_TRY(mdhip_alloc((size_t)blocks * sizeof(unsigned), &partial));
-  MD_LAUNCH((k_anyall_flat<ANY, T>), (unsigned)blocks, MD_BLOCK, (const T *)x->data, n, (unsigned *)partial, md_tickets(), (uint8_t *)out->data);
-  const int rc = MD_LAUNCH_CHECK("reduce(any/all, flat)");
-  if (partial) mdhip_free(partial);
-  return rc;
+constexpr int RED_RB = 8;   // rows per batch of k_reduce_cols_strips
+constexpr int ARG_RB = 4;   // .. of k_arg_cols_strips (rocprofv3 at one block per CU: 26.6 us with 4 rows per batch, 28.4 with 8)
+
+enum RedForm {
+  RED_ANYALL_FLAT, RED_ROWS_WAVE, RED_ROWS_WAVE_ANY, RED_COLS_STRIPS, RED_COLS_STRIPS_BATCHED, RED_COLS_VEC, RED_COLS_VEC_SPLIT,
+  RED_COLS, RED_COLS_SPLIT, RED_ROWS, RED_ALL_NARROW, RED_ALL, RED_ROWS_TICKET, RED_ROWS_SPLIT, RED_GENERIC,
+  ARG_COLS_STRIPS, ARG_COLS_STRIPS_BATCHED, ARG_COLS_VEC, ARG_ROWS_VEC, ARG_ROWS_VEC_SPLIT, ARG_ROWS_WAVE, ARG_BLOCK, ARG_THREAD
+};
+// One launch form and the numbers it needs (a form reads only its own).
+struct RedLaunch {
+  RedForm form;
+  const char *label;      // MD_LAUNCH_CHECK's
+  int64_t NS, NB, outer;  // strips: column strips, row bands, batches on blockIdx.y (plain: outer 1)
+  int64_t splits, chunk;  // split forms: blocks (or grid rows) per output, reduced items per block
+  int64_t blocks;         // gridDim.x of the other forms
+  int NV;                 // rows-wave: 16-B vectors per lane
+  bool nt;                // non-temporal loads (operands larger than the Infinity Cache are read once)
+  bool typed;             // arg rows-wave: x has the compare type itself
+  size_t partial_bytes, index_bytes;   // temporaries: the partial values, the partial indices of an arg form (0: none)
+};
+static RedLaunch &red_pick(RedLaunch &L, RedForm f, const char *label) {
+  L.form = f;
+  L.label = label;
+  return L;
+}
+
+// The properties of <R, Tacc, To> the planner asks about.
+struct RedTraits {
+  int acc_size, acc_dtype;   // sizeof(Tacc), md_dtype_of<Tacc>
+  bool same_out;             // Tacc == To
+  bool cheap;                // the strips walk serves it (f64 / integer max and min keep the tiled kernel — their compare chain wants more waves per CU)
+  bool anyall;
+};
+template <class R, class Tacc, class To> constexpr RedTraits red_traits() {
+  return {(int)sizeof(Tacc), md_dtype_of<Tacc>::value, md_same<Tacc, To>::value,
+          md_same<R, RSum>::value || md_same<R, RProd>::value || ((md_same<R, RMax>::value || md_same<R, RMin>::value) && md_same<Tacc, float>::value),
+          md_same<R, RAny>::value || md_same<R, RAll>::value};
+}
+// k_reduce_all over a storage-only dtype: only the accumulator types such an input can meet (md_dispatch.h). Of an integer
+// accumulator `cheap` says sum / prod, its absence max / min.
+static bool red_all_narrow_ok(const RedTraits &t, int xdt) {
+  const bool small = xdt == MDHIP_I8 || xdt == MDHIP_I16 || xdt == MDHIP_U8 || xdt == MDHIP_U16;
+  if (t.acc_dtype == MDHIP_I64) return t.cheap ? (small || xdt == MDHIP_U32 || xdt == MDHIP_U64) : xdt == MDHIP_U32;
+  if (t.acc_dtype == MDHIP_I32) return !t.cheap && small;
+  return t.acc_dtype == MDHIP_F32 && xdt == MDHIP_F16;
+}
+
+// Calls f with `flag` as a compile-time constant: a launch that exists as <.., true> and <.., false> stands once.
+template <class F> static void with_flag(bool flag, F &&f) {
+  if (flag) f(std::true_type());
+  else f(std::false_type());
+}
+
+static RedLaunch plan_reduce(const MdRedPlan &pl, const mdhip_array *x, const mdhip_array *out, RedTraits t) {
+  RedLaunch L{};
+  const int64_t n_out = pl.n_out, n_red = pl.n_red, asz = t.acc_size;
+  const bool x_al = ((uintptr_t)x->data & 15) == 0, out_al = ((uintptr_t)out->data & 15) == 0;
+  const bool row_contig = pl.nr == 1 && pl.rx[0] == 1;   // one reduced axis, unit stride
+  const bool typed = x->dtype == t.acc_dtype;
+  // the whole of a contiguous array: truth values from 16-B vectors of the array's own type
+  if (t.anyall && n_out == 1 && row_contig && n_red >= (1 << 16) && x_al &&
+      (x->dtype == MDHIP_BOOL || x->dtype == MDHIP_I32 || x->dtype == MDHIP_I64 || x->dtype == MDHIP_F32 || x->dtype == MDHIP_F64)) {
+    L.blocks = ceil_div(n_red * (int64_t)md_dtype_size(x->dtype), 64 * 1024);   // >= 64 KiB per block
+    if (L.blocks > 4 * MD_NUM_CUS) L.blocks = 4 * MD_NUM_CUS;
+    if (L.blocks < 1) L.blocks = 1;
+    L.partial_bytes = L.blocks > 1 ? (size_t)L.blocks * sizeof(unsigned) : 0;
+    return red_pick(L, RED_ANYALL_FLAT, "reduce(any/all, flat)");
+  }
+  const bool rows_ok = n_red >= 256 && n_out < (1ll << 30);
+  const bool cols_ok = pl.nk >= 1 && pl.kx[pl.nk - 1] == 1 && n_out >= 64;
+  const int64_t V = asz >= 4 ? 16 / asz : 1;   // (the vector forms need a 4- / 8-byte accumulator)
+  if (asz >= 4) {
+    // many short contiguous rows: a wave per output (every row must start on a 16-B boundary)
+    const bool wave_on = md_opt(MD_OPT_ROWS_WAVE) != 0;   // 0: block per output (A/B)
+    bool aligned = x_al;
+    for (int k = 0; k < pl.nk; ++k) aligned = aligned && (pl.kx[k] % V) == 0;
+    if (wave_on && row_contig && typed && aligned && n_red >= 32 && n_red <= 64 * V * 8 && n_out >= 1024 && n_out < (1ll << 32)) {
+      const int64_t nvec = n_red / V;
+      L.blocks = ceil_div(n_out, 4);
+      L.NV = nvec <= 64 ? 1 : nvec <= 128 ? 2 : nvec <= 256 ? 4 : 8;
+      return red_pick(L, RED_ROWS_WAVE, "reduce(rows,wave)");
+    }
+  }
+  // (rows of the accumulator's own 4- / 8-byte type from 256 elements on keep the block kernel's peeled 16-B loads)
+  const bool typed_vec = asz >= 4 && typed;
+  if (row_contig && n_red >= 16 && n_red <= 4096 && (!typed_vec || n_red < 256) && n_out >= 256 && md_opt(MD_OPT_ROWS_WAVE) != 0) {
+    L.blocks = ceil_div(n_out, MD_BLOCK / 64);
+    if (L.blocks > 8 * MD_NUM_CUS) L.blocks = 8 * MD_NUM_CUS;
+    return red_pick(L, RED_ROWS_WAVE_ANY, "reduce(rows,wave,any type)");
+  }
+  // (kept last axis contiguous, >= 64 outputs: the column kernels, whatever the width — up to round 4 widths under 1024 went to a
+  // block per OUTPUT walking its column with the row stride: the bias gradient of a 300,000 x 1000 batch ran at 550 GB/s)
+  // (under 1024 outputs only when the contiguous kept axis is at least a wave wide: the middle axis of 8 x 62500 x 8 has 64 outputs in
+  // runs of 8 — one block, a quarter of its lanes, 0.24 ms; a block per output walks them in 0.03)
+  const bool wide = pl.nk >= 1 && pl.kshape[pl.nk - 1] >= 64;
+  if (cols_ok && (!rows_ok || n_out >= 1024 || (wide && (asz >= 4 || n_out >= 256)))) {   // (1-byte accumulators — any / all — from 256 columns on)
+    if (asz >= 4 && t.same_out) {
+      const bool vec_ok = pl.nk == 1 && pl.nr == 1 && pl.ko[0] == 1 && typed && (n_out % V) == 0 && (pl.rx[0] % V) == 0 && x_al && out_al && n_red >= 16;
+      if (t.cheap && vec_ok && n_red >= 512) {
+        const int nb_force = (int)md_opt(MD_OPT_COLS_NB);
+        const int64_t NS = ceil_div(n_out, 64 * V);
+        // one block per CU (two per CU ran 15 % slower, half a block per CU 20 %: profiles/r3_reduce_lab.txt); option cols_nb
+        // forces the count (still clamped)
+        const int64_t NB = nb_force > 0 ? md_strips_bands(1, nb_force, MD_FLOOR, n_red, 4 * RED_RB) : md_strips_bands(NS, MD_NUM_CUS, MD_FLOOR, n_red, 4 * RED_RB);
+        // tickets that do not fit: decline — the tiled kernels below take it (the batched forms and var fall to one band instead)
+        if (NS * NB >= MD_NUM_CUS / 4 && NS * NB < (1ll << 31) && (NB == 1 || NS * MD_TICKET_PAD <= MD_TICKET_WORDS)) {
+          L.NS = NS; L.NB = NB; L.outer = 1;
+          L.nt = n_red * n_out * asz > ((int64_t)320 << 20);
+          L.partial_bytes = NB > 1 ? (size_t)(NB * n_out) * asz : 0;
+          return red_pick(L, RED_COLS_STRIPS, "reduce(cols,strips)");
+        }
+      }
+      // a middle axis reduced: (outer, n_red, inner) with the inner axis contiguous — `outer` independent column problems in one launch
+      if (t.cheap && pl.nk == 2 && pl.nr == 1 && pl.kx[1] == 1 && pl.ko[1] == 1 && pl.ko[0] == pl.kshape[1] && typed && (pl.kshape[1] % V) == 0 &&
+          (pl.rx[0] % V) == 0 && (pl.kx[0] % V) == 0 && x_al && out_al && pl.kshape[0] <= 65535 && pl.kshape[1] >= 256 && n_red >= 64) {
+        const int64_t outer = pl.kshape[0], inner = pl.kshape[1];
+        const int64_t NS = ceil_div(inner, 64 * V);
+        const int64_t NB = md_strips_bands(NS * outer, MD_NUM_CUS, MD_FLOOR, n_red, 4 * RED_RB);   // one block per CU over all the batches
+        // tickets that do not fit: decline, as the plain form
+        if (NB == 1 || NS * outer * MD_TICKET_PAD <= MD_TICKET_WORDS) {
+          L.NS = NS; L.NB = NB; L.outer = outer;
+          L.partial_bytes = NB > 1 ? (size_t)(outer * NB * inner) * asz : 0;
+          return red_pick(L, RED_COLS_STRIPS_BATCHED, "reduce(cols,strips,batched)");
+        }
+      }
+      // (the tiled kernels from here on serve what the strips forms do not cover: narrow / ragged / short problems)
+      if (vec_ok) {
+        L.blocks = ceil_div(n_out, 64 * V);
+        int64_t splits = 1024 / L.blocks;
+        if (splits > n_red / 64) splits = n_red / 64;
+        if (splits > 65535) splits = 65535;
+        if (splits < 1) splits = 1;
+        L.chunk = ceil_div(ceil_div(n_red, splits), 16) * 16;
+        L.splits = ceil_div(n_red, L.chunk);
+        if (L.splits == 1) return red_pick(L, RED_COLS_VEC, "reduce(cols,vec)");
+        L.partial_bytes = (size_t)(L.splits * n_out) * asz;
+        return red_pick(L, RED_COLS_VEC_SPLIT, "reduce(cols,vec,split)");
+      }
+    }
+    L.blocks = ceil_div(n_out, MD_BLOCK);
+    int64_t splits = 1024 / L.blocks;
+    if (splits > n_red / 32) splits = n_red / 32;
+    if (splits > 65535) splits = 65535;
+    if (splits < 1) splits = 1;
+    L.chunk = ceil_div(n_red > 0 ? n_red : 1, splits);
+    L.splits = ceil_div(n_red > 0 ? n_red : 1, L.chunk);
+    if (L.splits == 1) return red_pick(L, RED_COLS, "reduce(cols)");
+    L.partial_bytes = (size_t)(L.splits * n_out) * asz;
+    return red_pick(L, RED_COLS_SPLIT, "reduce(cols,split)");
+  }
+  if (rows_ok) {
+    // ~1024 blocks in total (4 per CU; option rows_blocks overrides: experiments); each block should still see >= 4096 items
+    const int64_t total_blocks = md_opt(MD_OPT_ROWS_BLOCKS) > 0 ? md_opt(MD_OPT_ROWS_BLOCKS) : 1024;
+    int64_t splits = total_blocks / n_out;
+    const int64_t max_splits = ceil_div(n_red, 4096);
+    if (splits > max_splits) splits = max_splits;
+    if (splits < 1) splits = 1;
+    L.splits = splits;
+    if (splits == 1) return red_pick(L, RED_ROWS, "reduce(rows)");
+    L.partial_bytes = (size_t)(splits * n_out) * asz;
+    L.nt = n_red * n_out * asz > ((int64_t)320 << 20);
+    if (asz >= 4) {
+      const bool whole = n_out == 1 && row_contig && x_al;
+      // the whole of a contiguous array of a STORAGE-ONLY dtype (sum(int8), max(float16) ..): the same kernel, 16-B loads of the narrow type
+      if (whole && md_is_narrow(x->dtype) && red_all_narrow_ok(t, x->dtype)) return red_pick(L, RED_ALL_NARROW, "reduce(all, storage-only dtype)");
+      if (whole && typed) return red_pick(L, RED_ALL, "reduce(all)");
+      if (n_out * (splits >= 64 ? MD_TICKET2_WORDS : MD_TICKET_PAD) <= MD_TICKET_WORDS) return red_pick(L, RED_ROWS_TICKET, "reduce(rows,ticket)");
+    }
+    // (the two-launch form: more outputs x splits than ticket words, 1-byte accumulators)
+    return red_pick(L, RED_ROWS_SPLIT, "reduce(rows,split)");
+  }
+  L.blocks = md_grid_for(n_out);
+  return red_pick(L, RED_GENERIC, "reduce(generic)");
+}
+
+// A form the runner's instantiation was not compiled for: the planner and the `if constexpr` gates below disagree.
+static int red_unplanned(const RedLaunch &L) { return md_fail(MDHIP_ERUNTIME, "%s: planned for a type this instantiation does not hold", L.label); }
+
+template <class R, class Tacc, class To>
+static int run_reduce(const RedLaunch &L, const MdRedPlan &pl, const mdhip_array *x, const mdhip_array *out) {
+  constexpr RedTraits t = red_traits<R, Tacc, To>();
+  constexpr bool WIDE = t.acc_size >= 4, VEC = WIDE && t.same_out, STRIPS = VEC && t.cheap;   // what the planner asks before it picks the gated forms
+  hipStream_t st = md_stream();
+  const int64_t n_out = pl.n_out, n_red = pl.n_red;
+  To *const o = (To *)out->data;
+  MdScratch scratch;   // freed on return — stream-ordered: the next user of a block runs after the kernels launched here
+  void *pv;
+  MD_TRY(scratch.get(L.partial_bytes, &pv));
+  Tacc *const partial = (Tacc *)pv;
+  switch (L.form) {
+    case RED_ANYALL_FLAT:
+      if constexpr (t.anyall) {
+#define MD_FLAT(DT, T)                                                                                                                                          \
+  if (x->dtype == DT) {                                                                                                                                         \
+    MD_LAUNCH((k_anyall_flat<md_same<R, RAny>::value, T>), (unsigned)L.blocks, MD_BLOCK, (const T *)x->data, n_red, (unsigned *)pv, md_tickets(), (uint8_t *)out->data); \
+    break;                                                                                                                                                      \
+  }
+        MD_FLAT(MDHIP_BOOL, uint8_t) MD_FLAT(MDHIP_I32, int32_t) MD_FLAT(MDHIP_I64, int64_t) MD_FLAT(MDHIP_F32, float) MD_FLAT(MDHIP_F64, double)
+#undef MD_FLAT
+      }
+      return red_unplanned(L);
+    case RED_ROWS_WAVE:
+      if constexpr (!WIDE) return red_unplanned(L);
+      else {
+        const unsigned grid = (unsigned)L.blocks;
+        const Tacc *xp = (const Tacc *)x->data;
+        if (L.NV == 1) MD_LAUNCH((k_reduce_rows_wave<R, Tacc, To, 1>), grid, MD_BLOCK, pl, xp, o);
+        else if (L.NV == 2) MD_LAUNCH((k_reduce_rows_wave<R, Tacc, To, 2>), grid, MD_BLOCK, pl, xp, o);
+        else if (L.NV == 4) MD_LAUNCH((k_reduce_rows_wave<R, Tacc, To, 4>), grid, MD_BLOCK, pl, xp, o);
+        else MD_LAUNCH((k_reduce_rows_wave<R, Tacc, To, 8>), grid, MD_BLOCK, pl, xp, o);
+      }
+      break;
+    case RED_ROWS_WAVE_ANY:
+      MD_LAUNCH((k_reduce_rows_wave_any<R, Tacc, To>), (unsigned)L.blocks, MD_BLOCK, pl, x->data, x->dtype, o);
+      break;
+    case RED_COLS_STRIPS:
+    case RED_COLS_STRIPS_BATCHED:
+      if constexpr (!STRIPS) return red_unplanned(L);
+      else {
+        const bool batched = L.form == RED_COLS_STRIPS_BATCHED;
+        const dim3 grid((unsigned)(L.NS * L.NB), (unsigned)L.outer);
+        // plain: n_out columns, no batch steps; batched: `outer` problems of kshape[1] columns, kx[0] apart in x, a row of out each
+        const int64_t cols = batched ? pl.kshape[1] : n_out, x_step = batched ? pl.kx[0] : 0, o_step = batched ? pl.kshape[1] : 0;
+        with_flag(L.nt, [&](auto NT) {
+          MD_LAUNCH((k_reduce_cols_strips<R, Tacc, RED_RB, decltype(NT)::value>), grid, MD_BLOCK, (const Tacc *)x->data, cols, n_red, pl.rx[0], (int)L.NS, (int)L.NB,
+                    partial, md_tickets(), (Tacc *)out->data, x_step, o_step);
+        });
+      }
+      break;
+    case RED_COLS_VEC:
+      if constexpr (!VEC) return red_unplanned(L);
+      else k_reduce_cols_vec<R, Tacc, To, true><<<dim3((unsigned)L.blocks, 1), MD_BLOCK, 0, st>>>((const Tacc *)x->data, n_out, n_red, pl.rx[0], L.chunk, o);
+      break;
+    case RED_COLS_VEC_SPLIT:
+      if constexpr (!VEC) return red_unplanned(L);
+      else {
+        k_reduce_cols_vec<R, Tacc, Tacc, false><<<dim3((unsigned)L.blocks, (unsigned)L.splits), MD_BLOCK, 0, st>>>((const Tacc *)x->data, n_out, n_red, pl.rx[0], L.chunk, partial);
+        const int64_t chunk2 = ceil_div(L.splits, 16) * 16;
+        k_reduce_cols_vec<R, Tacc, To, true><<<dim3((unsigned)L.blocks, 1), MD_BLOCK, 0, st>>>((const Tacc *)partial, n_out, L.splits, n_out, chunk2, o);
+      }
+      break;
+    case RED_COLS:
+      k_reduce_cols<R, Tacc, To, true><<<dim3((unsigned)L.blocks, 1), MD_BLOCK, 0, st>>>(pl, x->data, x->dtype, L.chunk, o);
+      break;
+    case RED_COLS_SPLIT:
+      k_reduce_cols<R, Tacc, Tacc, false><<<dim3((unsigned)L.blocks, (unsigned)L.splits), MD_BLOCK, 0, st>>>(pl, x->data, x->dtype, L.chunk, partial);
+      k_finish_cols<R, Tacc, To><<<(unsigned)L.blocks, MD_BLOCK, 0, st>>>(pl, (const Tacc *)partial, L.splits, o);
+      break;
+    case RED_ROWS:
+      k_reduce_rows<R, Tacc, To, 0><<<(unsigned)n_out, MD_BLOCK, 0, st>>>(pl, x->data, x->dtype, 1, o, nullptr, nullptr);
+      break;
+    case RED_ALL_NARROW:
+      if constexpr (WIDE) {
+#define MD_RED_ALL_AS(DT, S)                                                                                                                             \
+  if (x->dtype == DT) {                                                                                                                                  \
+    with_flag(L.nt, [&](auto NT) {                                                                                                                       \
+      MD_LAUNCH((k_reduce_all<R, Tacc, To, decltype(NT)::value, S>), (unsigned)L.splits, MD_BLOCK, (const S *)x->data, n_red, partial, md_tickets(), o); \
+    });                                                                                                                                                  \
+    break;                                                                                                                                               \
+  }
+        // (the instances red_all_narrow_ok admits)
+        if constexpr (md_same<Tacc, int64_t>::value && t.cheap) {
+          MD_RED_ALL_AS(MDHIP_I8, int8_t) MD_RED_ALL_AS(MDHIP_I16, int16_t) MD_RED_ALL_AS(MDHIP_U8, uint8_t) MD_RED_ALL_AS(MDHIP_U16, uint16_t)
+          MD_RED_ALL_AS(MDHIP_U32, uint32_t) MD_RED_ALL_AS(MDHIP_U64, uint64_t)
+        }
+        if constexpr (md_same<Tacc, int32_t>::value && !t.cheap) {
+          MD_RED_ALL_AS(MDHIP_I8, int8_t) MD_RED_ALL_AS(MDHIP_I16, int16_t) MD_RED_ALL_AS(MDHIP_U8, uint8_t) MD_RED_ALL_AS(MDHIP_U16, uint16_t)
+        }
+        if constexpr (md_same<Tacc, int64_t>::value && !t.cheap) { MD_RED_ALL_AS(MDHIP_U32, uint32_t) }
+        if constexpr (md_same<Tacc, float>::value) { MD_RED_ALL_AS(MDHIP_F16, f16) }
+#undef MD_RED_ALL_AS
+      }
+      return red_unplanned(L);
+    case RED_ALL:
+      if constexpr (!WIDE) return red_unplanned(L);
+      else with_flag(L.nt, [&](auto NT) {
+        MD_LAUNCH((k_reduce_all<R, Tacc, To, decltype(NT)::value>), (unsigned)L.splits, MD_BLOCK, (const Tacc *)x->data, n_red, partial, md_tickets(), o);
+      });
+      break;
+    case RED_ROWS_TICKET:
+      if constexpr (!WIDE) return red_unplanned(L);
+      else with_flag(L.nt, [&](auto NT) {
+        MD_LAUNCH((k_reduce_rows<R, Tacc, To, 2, decltype(NT)::value>), (unsigned)(n_out * L.splits), MD_BLOCK, pl, x->data, x->dtype, L.splits, o, partial, md_tickets());
+      });
+      break;
+    case RED_ROWS_SPLIT:
+      with_flag(L.nt, [&](auto NT) {
+        k_reduce_rows<R, Tacc, Tacc, 1, decltype(NT)::value><<<(unsigned)(n_out * L.splits), MD_BLOCK, 0, st>>>(pl, x->data, x->dtype, L.splits, partial, nullptr, nullptr);
+      });
+      k_finish_rows<R, Tacc, To><<<(unsigned)n_out, MD_BLOCK, 0, st>>>(pl, (const Tacc *)partial, L.splits, o);
+      break;
+    case RED_GENERIC:
+      k_reduce_generic<R, Tacc, To><<<(unsigned)L.blocks, MD_BLOCK, 0, st>>>(pl, x->data, x->dtype, o);
+      break;
+    default: return red_unplanned(L);
+  }
+  return MD_LAUNCH_CHECK(L.label);
+}
+
+// sizeof(T) and md_dtype_of<T> of the compare type are all the planner needs of <IsMax, T>.
+static RedLaunch plan_arg(const MdRedPlan &pl, const mdhip_array *x, int64_t tsz, int tdtype) {
+  RedLaunch L{};
+  const int64_t n_out = pl.n_out, n_red = pl.n_red;
+  const bool typed = x->dtype == tdtype;
+  if (tsz >= 4 && typed) {
+    const int64_t V = 16 / tsz;
+    const bool x_al = ((uintptr_t)x->data & 15) == 0;
+    const int64_t isz = V == 4 ? 4 : 8;   // the strips kernel's partial indices: as wide as the values
+    const int64_t arg_blocks = md_opt(MD_OPT_ARG_BLOCKS) > 0 ? (int)md_opt(MD_OPT_ARG_BLOCKS) : MD_NUM_CUS;   // one block per CU, as the column sums (rocprofv3: 26.6 us against 38.0 with four per CU); the knob is for experiments
+    // kept axis contiguous (argmax over the rows of a row-major matrix)
+    if (pl.nk == 1 && pl.nr == 1 && pl.kx[0] == 1 && pl.ko[0] == 1 && n_out >= 256 && (n_out % V) == 0 && (pl.rx[0] % V) == 0 && x_al && n_red >= 16) {
+      const int64_t bxv = ceil_div(n_out, 64 * V);
+      if (n_red < (1ll << 31) && n_red >= 64 && bxv * MD_TICKET_PAD <= MD_TICKET_WORDS) {
+        L.NS = bxv; L.outer = 1;
+        L.NB = md_strips_bands(L.NS, arg_blocks, MD_CEIL, n_red, 32);
+        while (L.NB > 1 && L.NB * n_out * 8 >= (1ll << 31)) L.NB /= 2;   // (32-bit byte offsets into the partial rows, of 8-byte elements at most)
+        if (L.NB > 1) L.partial_bytes = (size_t)(L.NB * n_out) * tsz, L.index_bytes = (size_t)(L.NB * n_out) * isz;
+        return red_pick(L, ARG_COLS_STRIPS, "argreduce(cols,strips)");
+      }
+      // What the strips kernel leaves: columns of 16 .. 63 rows, or more than 1024 strips (more than the ticket block serves); a
+      // block per strip walks the whole of its columns. Cutting the rows into chunks (partials + a finish pass, as the row form
+      // below does) was unreachable here: its split count min(1024 / strips, n_red / 64) is 0 -> 1 both ways — n_red < 64 gives
+      // n_red / 64 == 0, more than 1024 strips give 1024 / strips == 0 — and the third way past the strips kernel, n_red >= 2^31
+      // rows of >= 256 columns, does not fit in memory.
+      L.blocks = bxv;
+      return red_pick(L, ARG_COLS_VEC, "argreduce(cols,vec)");
+    }
+    // a middle axis reduced: (outer, n_red, inner) with the inner axis contiguous — `outer` column problems in one launch of the strips
+    // kernel (the predicate of the batched column sums above); up to here these went to k_arg_block / k_arg_thread, a block or a
+    // thread per output walking its column with the row stride. (md_build_redplan merges neighbouring kept axes whose strides nest in x
+    // and in out, so (2,3,[64],256) and (2,[64],4,64) arrive here as nk == 2 as well: profiles/middle_axis_4d_kernel_stats.csv)
+    if (md_opt(MD_OPT_ARG_BATCHED) != 0 && pl.nk == 2 && pl.nr == 1 && pl.kx[1] == 1 && pl.ko[1] == 1 && pl.ko[0] == pl.kshape[1] &&
+        (pl.kshape[1] % V) == 0 && (pl.rx[0] % V) == 0 && (pl.kx[0] % V) == 0 && x_al && pl.kshape[1] >= 256 && n_red >= 64 && n_red < (1ll << 31) &&
+        pl.kshape[0] <= 65535) {
+      const int64_t outer = pl.kshape[0], inner = pl.kshape[1];
+      L.NS = ceil_div(inner, 64 * V); L.outer = outer;
+      L.NB = md_strips_bands(L.NS * outer, arg_blocks, MD_CEIL, n_red, 32);   // one block per CU over all the batches
+      if (L.NS * outer * MD_TICKET_PAD > MD_TICKET_WORDS) L.NB = 1;   // more strips than ticket words: one band (the column sums decline instead)
+      while (L.NB > 1 && L.NB * inner * 8 >= (1ll << 31)) L.NB /= 2;   // (32-bit byte offsets into a batch's partial rows, of 8-byte elements at most)
+      if (L.NB > 1) L.partial_bytes = (size_t)(outer * L.NB * inner) * tsz, L.index_bytes = (size_t)(outer * L.NB * inner) * isz;
+      return red_pick(L, ARG_COLS_STRIPS_BATCHED, "argreduce(cols,strips,batched)");
+    }
+    // reduced axis contiguous
+    if (pl.nr == 1 && pl.rx[0] == 1 && n_red >= 1024 && n_out < (1ll << 30)) {
+      // ~2048 blocks in total, each with >= 8192 items of its row
+      int64_t splits = 2048 / n_out;
+      const int64_t max_splits = ceil_div(n_red, 8192);
+      if (splits > max_splits) splits = max_splits;
+      if (splits < 1) splits = 1;
+      L.chunk = ceil_div(ceil_div(n_red, splits), V) * V;
+      L.splits = ceil_div(n_red, L.chunk);
+      if (L.splits == 1) return red_pick(L, ARG_ROWS_VEC, "argreduce(rows,vec)");
+      L.partial_bytes = (size_t)(L.splits * n_out) * tsz;
+      L.index_bytes = (size_t)(L.splits * n_out) * sizeof(int64_t);
+      return red_pick(L, ARG_ROWS_VEC_SPLIT, "argreduce(rows,vec,split)");
+    }
+  }
+  if (pl.nr == 1 && pl.rx[0] == 1 && n_red >= 24 && (n_red < 1024 || !typed) && n_red <= 65536 && n_out >= 64) {
+    L.blocks = ceil_div(n_out, MD_BLOCK / 64);
+    if (L.blocks > 8 * MD_NUM_CUS) L.blocks = 8 * MD_NUM_CUS;
+    L.typed = typed;
+    return red_pick(L, ARG_ROWS_WAVE, "argreduce(rows,wave)");
+  }
+  if (n_red >= 512 && n_out < (1ll << 30)) return red_pick(L, ARG_BLOCK, "argreduce(block)");
+  L.blocks = md_grid_for(n_out);
+  return red_pick(L, ARG_THREAD, "argreduce(thread)");
+}
+
+template <bool IsMax, class T>
+static int run_arg(const RedLaunch &L, const MdRedPlan &pl, const mdhip_array *x, const mdhip_array *out) {
+  constexpr bool WIDE = sizeof(T) >= 4;   // plan_arg picks the strips / vec forms for 4- / 8-byte compare types only
+  hipStream_t st = md_stream();
+  const int64_t n_out = pl.n_out, n_red = pl.n_red;
+  int64_t *const o = (int64_t *)out->data;
+  MdScratch scratch;   // both blocks freed on every way out, stream-ordered behind the launches
+  void *pv, *pi;
+  MD_TRY(scratch.get(L.partial_bytes, &pv));
+  MD_TRY(scratch.get(L.index_bytes, &pi));
+  switch (L.form) {
+    case ARG_COLS_STRIPS:
+    case ARG_COLS_STRIPS_BATCHED:
+      if constexpr (!WIDE) return red_unplanned(L);
+      else {
+        const bool batched = L.form == ARG_COLS_STRIPS_BATCHED;
+        const dim3 grid((unsigned)(L.NS * L.NB), (unsigned)L.outer);
+        // plain: n_out columns, no batch steps; batched: `outer` problems of kshape[1] columns, kx[0] apart in x, a row of out each
+        const int64_t cols = batched ? pl.kshape[1] : n_out, x_step = batched ? pl.kx[0] : 0, o_step = batched ? pl.kshape[1] : 0;
+        MD_LAUNCH((k_arg_cols_strips<IsMax, T, ARG_RB>), grid, MD_BLOCK, (const T *)x->data, cols, n_red, pl.rx[0], (int)L.NS, (int)L.NB, (T *)pv, pi, md_tickets(), o,
+                  x_step, o_step);
+      }
+      break;
+    case ARG_COLS_VEC:
+      if constexpr (!WIDE) return red_unplanned(L);
+      else k_arg_cols_vec<IsMax, T><<<(unsigned)L.blocks, MD_BLOCK, 0, st>>>((const T *)x->data, n_out, n_red, pl.rx[0], o);
+      break;
+    case ARG_ROWS_VEC:
+      if constexpr (!WIDE) return red_unplanned(L);
+      else k_arg_rows_vec<IsMax, T, true><<<(unsigned)n_out, MD_BLOCK, 0, st>>>(pl, (const T *)x->data, 1, L.chunk, nullptr, o);
+      break;
+    case ARG_ROWS_VEC_SPLIT:
+      if constexpr (!WIDE) return red_unplanned(L);
+      else {
+        k_arg_rows_vec<IsMax, T, false><<<(unsigned)(n_out * L.splits), MD_BLOCK, 0, st>>>(pl, (const T *)x->data, L.splits, L.chunk, (T *)pv, (int64_t *)pi);
+        k_arg_rows_finish<IsMax, T><<<(unsigned)ceil_div(n_out, MD_BLOCK), MD_BLOCK, 0, st>>>(pl, (const T *)pv, (const int64_t *)pi, L.splits, o);
+      }
+      break;
+    case ARG_ROWS_WAVE:
+      with_flag(L.typed, [&](auto TYPED) {
+        MD_LAUNCH((k_arg_rows_wave<IsMax, T, decltype(TYPED)::value>), (unsigned)L.blocks, MD_BLOCK, pl, x->data, x->dtype, o);
+      });
+      break;
+    case ARG_BLOCK:
+      k_arg_block<IsMax, T><<<(unsigned)n_out, MD_BLOCK, 0, st>>>(pl, x->data, x->dtype, o);
+      break;
+    case ARG_THREAD:
+      k_arg_thread<IsMax, T><<<(unsigned)L.blocks, MD_BLOCK, 0, st>>>(pl, x->data, x->dtype, o);
+      break;
+    default: return red_unplanned(L);
+  }
+  return MD_LAUNCH_CHECK(L.label);
 }
 
 struct HipExec {
   template <class R, class Tacc, class To>
   static int reduce(const MdRedPlan &pl, const mdhip_array *x, const mdhip_array *out) {
-    hipStream_t st = md_stream();
-    const int64_t n_out = pl.n_out, n_red = pl.n_red;
-    if constexpr (md_same<R, RAny>::value || md_same<R, RAll>::value) {
-      // the whole of a contiguous array: truth values from 16-B vectors of the array's own type
-      if (n_out == 1 && pl.nr == 1 && pl.rx[0] == 1 && n_red >= (1 << 16) && ((uintptr_t)x->data & 15) == 0) {
-        constexpr bool ANY = md_same<R, RAny>::value;
-        switch (x->dtype) {
-          case MDHIP_BOOL: return anyall_flat<ANY, uint8_t>(x, n_red, out);
-          case MDHIP_I32: return anyall_flat<ANY, int32_t>(x, n_red, out);
-          case MDHIP_I64: return anyall_flat<ANY, int64_t>(x, n_red, out);
-          case MDHIP_F32: return anyall_flat<ANY, float>(x, n_red, out);
-          case MDHIP_F64: return anyall_flat<ANY, double>(x, n_red, out);
-          default: break;
-        }
-      }
-    }
-    const bool rows_ok = n_red >= 256 && n_out < (1ll << 30);
-    const bool cols_ok = pl.nk >= 1 && pl.kx[pl.nk - 1] == 1 && n_out >= 64;
-    if constexpr (sizeof(Tacc) >= 4) {
-      // many short contiguous rows: a wave per output (every row must start on a 16-B boundary)
-      constexpr int V = 16 / sizeof(Tacc);
-      const bool wave_on = md_opt(MD_OPT_ROWS_WAVE) != 0;   // 0: block per output (A/B)
-      bool aligned = ((uintptr_t)x->data & 15) == 0;
-      for (int k = 0; k < pl.nk; ++k) aligned = aligned && (pl.kx[k] % V) == 0;
-      if (wave_on && pl.nr == 1 && pl.rx[0] == 1 && x->dtype == md_dtype_of<Tacc>::value && aligned && n_red >= 32 && n_red <= 64 * V * 8 &&
-          n_out >= 1024 && n_out < (1ll << 32)) {
-        const unsigned grid = (unsigned)ceil_div(n_out, 4);
-        const Tacc *xp = (const Tacc *)x->data;
-        const int64_t nvec = n_red / V;
-        if (nvec <= 64) MD_LAUNCH((k_reduce_rows_wave<R, Tacc, To, 1>), grid, MD_BLOCK, pl, xp, (To *)out->data);
-        else if (nvec <= 128) MD_LAUNCH((k_reduce_rows_wave<R, Tacc, To, 2>), grid, MD_BLOCK, pl, xp, (To *)out->data);
-        else if (nvec <= 256) MD_LAUNCH((k_reduce_rows_wave<R, Tacc, To, 4>), grid, MD_BLOCK, pl, xp, (To *)out->data);
-        else MD_LAUNCH((k_reduce_rows_wave<R, Tacc, To, 8>), grid, MD_BLOCK, pl, xp, (To *)out->data);
-        return MD_LAUNCH_CHECK("reduce(rows,wave)");
-      }
-    }
-    // (rows of the accumulator's own 4- / 8-byte type from 256 elements on keep the block kernel's peeled 16-B loads)
-    const bool typed_vec = sizeof(Tacc) >= 4 && x->dtype == md_dtype_of<Tacc>::value;
-    if (pl.nr == 1 && pl.rx[0] == 1 && n_red >= 16 && n_red <= 4096 && (!typed_vec || n_red < 256) && n_out >= 256 && md_opt(MD_OPT_ROWS_WAVE) != 0) {
-      int64_t blocks = ceil_div(n_out, MD_BLOCK / 64);
-      if (blocks > 8 * MD_NUM_CUS) blocks = 8 * MD_NUM_CUS;
-      MD_LAUNCH((k_reduce_rows_wave_any<R, Tacc, To>), (unsigned)blocks, MD_BLOCK, pl, x->data, x->dtype, (To *)out->data);
-      return MD_LAUNCH_CHECK("reduce(rows,wave,any type)");
-    }
-    // (kept last axis contiguous, >= 64 outputs: the column kernels, whatever the width — up to round 4 widths under 1024 went to a
-    // block per OUTPUT walking its column with the row stride: the bias gradient of a 300,000 x 1000 batch ran at 550 GB/s)
-    // (under 1024 outputs only when the contiguous kept axis is at least a wave wide: the middle axis of 8 x 62500 x 8 has 64 outputs in
-    // runs of 8 — one block, a quarter of its lanes, 0.24 ms; a block per output walks them in 0.03)
-    const bool wide = pl.nk >= 1 && pl.kshape[pl.nk - 1] >= 64;
-    if (cols_ok && (!rows_ok || n_out >= 1024 || (wide && (sizeof(Tacc) >= 4 || n_out >= 256)))) {   // (1-byte accumulators — any / all — from 256 columns on)
-      if constexpr (sizeof(Tacc) >= 4 && md_same<Tacc, To>::value) {
-        constexpr int V = 16 / sizeof(Tacc);
-        const bool vec_ok = pl.nk == 1 && pl.nr == 1 && pl.ko[0] == 1 && x->dtype == md_dtype_of<Tacc>::value &&
-                            (n_out % V) == 0 && (pl.rx[0] % V) == 0 && ((uintptr_t)x->data & 15) == 0 &&
-                            ((uintptr_t)out->data & 15) == 0 && n_red >= 16;
-        constexpr int sweep_mode = 1;   // (the tiled kernels below serve what the strips form does not cover: narrow / ragged / short problems)
-        const int nb_force = (int)md_opt(MD_OPT_COLS_NB);
-        // (f64 / integer max and min keep the tiled kernel — their compare chain wants more waves per CU)
-        constexpr bool cheap = md_same<R, RSum>::value || md_same<R, RProd>::value ||
-                               ((md_same<R, RMax>::value || md_same<R, RMin>::value) && md_same<Tacc, float>::value);
-        constexpr int RB = 8;
-        const int64_t NS = ceil_div(n_out, 64 * V);
-        // one block per CU (two per CU ran 15 % slower, half a block per CU 20 %: profiles/r3_reduce_lab.txt); <= 64 bands: the
-        // last block of a strip holds all its partial rows in registers
-        int64_t NB = nb_force > 0 ? nb_force : (NS >= MD_NUM_CUS ? 1 : MD_NUM_CUS / NS);
-        if (NB > 64) NB = 64;
-        if (NB > n_red / (4 * RB)) NB = n_red / (4 * RB);
-        if (NB < 1) NB = 1;
-        if (cheap && vec_ok && sweep_mode && n_red >= 512 && NS * NB >= MD_NUM_CUS / 4 && NS * NB < (1ll << 31) &&
-            (NB == 1 || NS * MD_TICKET_PAD <= MD_TICKET_WORDS)) {
-          void *partial = nullptr;
-          if (NB > 1) MD_TRY(mdhip_alloc((size_t)(NB * n_out) * sizeof(Tacc), &partial));
-          const Tacc *xp = (const Tacc *)x->data;
-          if (n_red * n_out * (int64_t)sizeof(Tacc) > ((int64_t)320 << 20))
-            MD_LAUNCH((k_reduce_cols_strips<R, Tacc, RB, true>), (unsigned)(NS * NB), MD_BLOCK, xp, n_out, n_red, pl.rx[0], (int)NS, (int)NB, (Tacc *)partial, md_tickets(), (Tacc *)out->data, (int64_t)0, (int64_t)0);
-          else
-            MD_LAUNCH((k_reduce_cols_strips<R, Tacc, RB, false>), (unsigned)(NS * NB), MD_BLOCK, xp, n_out, n_red, pl.rx[0], (int)NS, (int)NB, (Tacc *)partial, md_tickets(), (Tacc *)out->data, (int64_t)0, (int64_t)0);
-          int rc = MD_LAUNCH_CHECK("reduce(cols,strips)");
-          if (partial) mdhip_free(partial);  // stream-ordered: the next user of this block runs after the kernel
-          return rc;
-        }
-        // a middle axis reduced: (outer, n_red, inner) with the inner axis contiguous — `outer` independent column problems in one launch
-        if constexpr (cheap) {
-          if (sweep_mode && pl.nk == 2 && pl.nr == 1 && pl.kx[1] == 1 && pl.ko[1] == 1 && pl.ko[0] == pl.kshape[1] && x->dtype == md_dtype_of<Tacc>::value &&
-              (pl.kshape[1] % V) == 0 && (pl.rx[0] % V) == 0 && (pl.kx[0] % V) == 0 && ((uintptr_t)x->data & 15) == 0 && ((uintptr_t)out->data & 15) == 0 &&
-              pl.kshape[0] <= 65535 && pl.kshape[1] >= 256 && n_red >= 64) {
-            const int64_t outer = pl.kshape[0], inner = pl.kshape[1];
-            const int64_t NSb = ceil_div(inner, 64 * V);
-            int64_t NBb = NSb * outer >= MD_NUM_CUS ? 1 : MD_NUM_CUS / (NSb * outer);
-            if (NBb > 64) NBb = 64;
-            if (NBb > n_red / (4 * RB)) NBb = n_red / (4 * RB);
-            if (NBb < 1) NBb = 1;
-            if (NBb == 1 || NSb * outer * MD_TICKET_PAD <= MD_TICKET_WORDS) {
-              void *partial = nullptr;
-              if (NBb > 1) MD_TRY(mdhip_alloc((size_t)(outer * NBb * inner) * sizeof(Tacc), &partial));
-              const dim3 grid((unsigned)(NSb * NBb), (unsigned)outer);
-              MD_LAUNCH((k_reduce_cols_strips<R, Tacc, RB, false>), grid, MD_BLOCK, (const Tacc *)x->data, inner, n_red, pl.rx[0], (int)NSb, (int)NBb, (Tacc *)partial,
-                        md_tickets(), (Tacc *)out->data, (int64_t)pl.kx[0], (int64_t)inner);
-              int rc = MD_LAUNCH_CHECK("reduce(cols,strips,batched)");
-              if (partial) mdhip_free(partial);
-              return rc;
-            }
-          }
-        }
-        if (vec_ok) {
-          const int64_t bxv = ceil_div(n_out, 64 * V);
-          int64_t splits = 1024 / bxv;
-          if (splits > n_red / 64) splits = n_red / 64;
-          if (splits > 65535) splits = 65535;
-          if (splits < 1) splits = 1;
-          const int64_t chunk = ceil_div(ceil_div(n_red, splits), 16) * 16;
-          splits = ceil_div(n_red, chunk);
-          const Tacc *xp = (const Tacc *)x->data;
-          if (splits == 1) {
-            k_reduce_cols_vec<R, Tacc, To, true><<<dim3((unsigned)bxv, 1), MD_BLOCK, 0, st>>>(xp, n_out, n_red, pl.rx[0], chunk, (To *)out->data);
-            return MD_LAUNCH_CHECK("reduce(cols,vec)");
-          }
-          void *partial = nullptr;
-          MD_TRY(mdhip_alloc((size_t)(splits * n_out) * sizeof(Tacc), &partial));
-          k_reduce_cols_vec<R, Tacc, Tacc, false><<<dim3((unsigned)bxv, (unsigned)splits), MD_BLOCK, 0, st>>>(xp, n_out, n_red, pl.rx[0], chunk, (Tacc *)partial);
-          const int64_t chunk2 = ceil_div(splits, 16) * 16;
-          k_reduce_cols_vec<R, Tacc, To, true><<<dim3((unsigned)bxv, 1), MD_BLOCK, 0, st>>>((const Tacc *)partial, n_out, splits, n_out, chunk2, (To *)out->data);
-          int rc = MD_LAUNCH_CHECK("reduce(cols,vec,split)");
-          mdhip_free(partial);
-          return rc;
-        }
-      }
-      const int64_t bx = ceil_div(n_out, MD_BLOCK);
-      int64_t splits = 1024 / bx;
-      if (splits > n_red / 32) splits = n_red / 32;
-      if (splits > 65535) splits = 65535;
-      if (splits < 1) splits = 1;
-      const int64_t chunk = ceil_div(n_red > 0 ? n_red : 1, splits);
-      splits = ceil_div(n_red > 0 ? n_red : 1, chunk);
-      dim3 grid((unsigned)bx, (unsigned)splits);
-      if (splits == 1) {
-        k_reduce_cols<R, Tacc, To, true><<<grid, MD_BLOCK, 0, st>>>(pl, x->data, x->dtype, chunk, (To *)out->data);
-        return MD_LAUNCH_CHECK("reduce(cols)");
-      }
-      void *partial = nullptr;
-      MD_TRY(mdhip_alloc((size_t)(splits * n_out) * sizeof(Tacc), &partial));
-      k_reduce_cols<R, Tacc, Tacc, false><<<grid, MD_BLOCK, 0, st>>>(pl, x->data, x->dtype, chunk, (Tacc *)partial);
-      k_finish_cols<R, Tacc, To><<<(unsigned)bx, MD_BLOCK, 0, st>>>(pl, (const Tacc *)partial, splits, (To *)out->data);
-      int rc = MD_LAUNCH_CHECK("reduce(cols,split)");
-      mdhip_free(partial);  // stream-ordered: the next user of this block runs after the finish pass
-      return rc;
-    }
-    if (rows_ok) {
-      // ~1024 blocks in total (4 per CU; option rows_blocks overrides: experiments); each block should still see >= 4096 items
-      const int64_t total_blocks = md_opt(MD_OPT_ROWS_BLOCKS) > 0 ? md_opt(MD_OPT_ROWS_BLOCKS) : 1024;
-      int64_t splits = total_blocks / n_out;
-      const int64_t max_splits = ceil_div(n_red, 4096);
-      if (splits > max_splits) splits = max_splits;
-      if (splits < 1) splits = 1;
-      if (splits == 1) {
-        k_reduce_rows<R, Tacc, To, 0><<<(unsigned)n_out, MD_BLOCK, 0, st>>>(pl, x->data, x->dtype, 1, (To *)out->data, nullptr, nullptr);
-        return MD_LAUNCH_CHECK("reduce(rows)");
-      }
-      void *partial = nullptr;
-      MD_TRY(mdhip_alloc((size_t)(splits * n_out) * sizeof(Tacc), &partial));
-      const bool nt = n_red * n_out * (int64_t)sizeof(Tacc) > ((int64_t)320 << 20);
-      int rc;
-      if constexpr (sizeof(Tacc) >= 4) {
-        constexpr bool all_on = true;
-        // the whole of a contiguous array of a STORAGE-ONLY dtype (sum(int8), max(float16) ..): the same kernel, 16-B loads of the narrow type
-        if (all_on && n_out == 1 && pl.nr == 1 && pl.rx[0] == 1 && md_is_narrow(x->dtype) && ((uintptr_t)x->data & 15) == 0) {
-#define MD_RED_ALL_AS(DT, S)                                                                                                          \
-          if (x->dtype == DT) {                                                                                                        \
-            if (nt) MD_LAUNCH((k_reduce_all<R, Tacc, To, true, S>), (unsigned)splits, MD_BLOCK, (const S *)x->data, n_red, (Tacc *)partial, md_tickets(), (To *)out->data); \
-            else MD_LAUNCH((k_reduce_all<R, Tacc, To, false, S>), (unsigned)splits, MD_BLOCK, (const S *)x->data, n_red, (Tacc *)partial, md_tickets(), (To *)out->data);   \
-            rc = MD_LAUNCH_CHECK("reduce(all, storage-only dtype)");                                                                   \
-            mdhip_free(partial);                                                                                                       \
-            return rc;                                                                                                                 \
-          }
-          // (only the accumulator types a storage-only input can meet: md_dispatch.h)
-          if constexpr (md_same<Tacc, int64_t>::value && (md_same<R, RSum>::value || md_same<R, RProd>::value)) {
-            MD_RED_ALL_AS(MDHIP_I8, int8_t) MD_RED_ALL_AS(MDHIP_I16, int16_t) MD_RED_ALL_AS(MDHIP_U8, uint8_t) MD_RED_ALL_AS(MDHIP_U16, uint16_t)
-            MD_RED_ALL_AS(MDHIP_U32, uint32_t) MD_RED_ALL_AS(MDHIP_U64, uint64_t)
-          }
-          if constexpr (md_same<Tacc, int32_t>::value && (md_same<R, RMax>::value || md_same<R, RMin>::value)) {
-            MD_RED_ALL_AS(MDHIP_I8, int8_t) MD_RED_ALL_AS(MDHIP_I16, int16_t) MD_RED_ALL_AS(MDHIP_U8, uint8_t) MD_RED_ALL_AS(MDHIP_U16, uint16_t)
-          }
-          if constexpr (md_same<Tacc, int64_t>::value && (md_same<R, RMax>::value || md_same<R, RMin>::value)) { MD_RED_ALL_AS(MDHIP_U32, uint32_t) }
-          if constexpr (md_same<Tacc, float>::value) { MD_RED_ALL_AS(MDHIP_F16, f16) }
-#undef MD_RED_ALL_AS
-        }
-        if (all_on && n_out == 1 && pl.nr == 1 && pl.rx[0] == 1 && x->dtype == md_dtype_of<Tacc>::value && ((uintptr_t)x->data & 15) == 0) {
-          if (nt) MD_LAUNCH((k_reduce_all<R, Tacc, To, true>), (unsigned)splits, MD_BLOCK, (const Tacc *)x->data, n_red, (Tacc *)partial, md_tickets(), (To *)out->data);
-          else MD_LAUNCH((k_reduce_all<R, Tacc, To, false>), (unsigned)splits, MD_BLOCK, (const Tacc *)x->data, n_red, (Tacc *)partial, md_tickets(), (To *)out->data);
-          rc = MD_LAUNCH_CHECK("reduce(all)");
-          mdhip_free(partial);
-          return rc;
-        }
-        constexpr bool ticket_on = true;   // (the two-launch form below: more outputs x splits than ticket words, 1-byte accumulators)
-        if (ticket_on && n_out * (splits >= 64 ? MD_TICKET2_WORDS : MD_TICKET_PAD) <= MD_TICKET_WORDS) {
-          if (nt) MD_LAUNCH((k_reduce_rows<R, Tacc, To, 2, true>), (unsigned)(n_out * splits), MD_BLOCK, pl, x->data, x->dtype, splits, (To *)out->data, (Tacc *)partial, md_tickets());
-          else MD_LAUNCH((k_reduce_rows<R, Tacc, To, 2>), (unsigned)(n_out * splits), MD_BLOCK, pl, x->data, x->dtype, splits, (To *)out->data, (Tacc *)partial, md_tickets());
-          rc = MD_LAUNCH_CHECK("reduce(rows,ticket)");
-          mdhip_free(partial);
-          return rc;
-        }
-      }
-      if (nt) k_reduce_rows<R, Tacc, Tacc, 1, true><<<(unsigned)(n_out * splits), MD_BLOCK, 0, st>>>(pl, x->data, x->dtype, splits, (Tacc *)partial, nullptr, nullptr);
-      else k_reduce_rows<R, Tacc, Tacc, 1><<<(unsigned)(n_out * splits), MD_BLOCK, 0, st>>>(pl, x->data, x->dtype, splits, (Tacc *)partial, nullptr, nullptr);
-      k_finish_rows<R, Tacc, To><<<(unsigned)n_out, MD_BLOCK, 0, st>>>(pl, (const Tacc *)partial, splits, (To *)out->data);
-      rc = MD_LAUNCH_CHECK("reduce(rows,split)");
-      mdhip_free(partial);
-      return rc;
-    }
-    k_reduce_generic<R, Tacc, To><<<md_grid_for(n_out), MD_BLOCK, 0, st>>>(pl, x->data, x->dtype, (To *)out->data);
-    return MD_LAUNCH_CHECK("reduce(generic)");
+    return run_reduce<R, Tacc, To>(plan_reduce(pl, x, out, red_traits<R, Tacc, To>()), pl, x, out);
   }
-
   template <bool IsMax, class T>
   static int argreduce(const MdRedPlan &pl, const mdhip_array *x, const mdhip_array *out) {
-    hipStream_t st = md_stream();
-    if constexpr (sizeof(T) >= 4) {
-      constexpr int V = 16 / sizeof(T);
-      const bool same = x->dtype == md_dtype_of<T>::value;
-      // kept axis contiguous (argmax over the rows of a row-major matrix)
-      if (same && pl.nk == 1 && pl.nr == 1 && pl.kx[0] == 1 && pl.ko[0] == 1 && pl.n_out >= 256 && (pl.n_out % V) == 0 &&
-          (pl.rx[0] % V) == 0 && ((uintptr_t)x->data & 15) == 0 && pl.n_red >= 16) {
-        const int64_t n_out = pl.n_out, n_red = pl.n_red;
-        const int64_t bxv = ceil_div(n_out, 64 * V);
-        constexpr bool strips_on = true;   // (k_arg_cols_vec below: more strips than ticket words, short columns)
-        if (strips_on && n_red < (1ll << 31) && n_red >= 64 && bxv * MD_TICKET_PAD <= MD_TICKET_WORDS) {
-          const int64_t NS = bxv;
-          const int arg_blocks = md_opt(MD_OPT_ARG_BLOCKS) > 0 ? (int)md_opt(MD_OPT_ARG_BLOCKS) : MD_NUM_CUS;   // one block per CU, as the column sums (rocprofv3: 26.6 us against 38.0 with four per CU); the knob is for experiments
-          int64_t NB = ceil_div(arg_blocks, NS);
-          if (NB > 64) NB = 64;
-          if (NB > n_red / 32) NB = n_red / 32;
-          if (NB < 1) NB = 1;
-          while (NB > 1 && NB * n_out * 8 >= (1ll << 31)) NB /= 2;   // (32-bit byte offsets into the partial rows)
-          constexpr int ARG_RB = 4;   // (rocprofv3 at one block per CU: 26.6 us with 4 rows per batch, 28.4 with 8)
-          void *pv = nullptr, *pi = nullptr;
-          if (NB > 1) {
-            MD_TRY(mdhip_alloc((size_t)(NB * n_out) * sizeof(T), &pv));
-            const int rc = mdhip_alloc((size_t)(NB * n_out) * (V == 4 ? 4 : 8), &pi);
-            if (rc != MDHIP_OK) { mdhip_free(pv); return rc; }
-          }
-          MD_LAUNCH((k_arg_cols_strips<IsMax, T, ARG_RB>), (unsigned)(NS * NB), MD_BLOCK, (const T *)x->data, n_out, n_red, pl.rx[0], (int)NS, (int)NB, (T *)pv, pi, md_tickets(),
-                    (int64_t *)out->data, (int64_t)0, (int64_t)0);
-          const int rc = MD_LAUNCH_CHECK("argreduce(cols,strips)");
-          if (pv) mdhip_free(pv);
-          if (pi) mdhip_free(pi);
-          return rc;
-        }
-        // What the strips kernel leaves: columns of 16 .. 63 rows, or more than 1024 strips (more than the ticket block serves); a
-        // block per strip walks the whole of its columns. Cutting the rows into chunks (partials + a finish pass, as the row form
-        // below does) was unreachable here: its split count min(1024 / strips, n_red / 64) is 0 -> 1 both ways — n_red < 64 gives
-        // n_red / 64 == 0, more than 1024 strips give 1024 / strips == 0 — and the third way past the strips kernel, n_red >= 2^31
-        // rows of >= 256 columns, does not fit in memory.
-        k_arg_cols_vec<IsMax, T><<<(unsigned)bxv, MD_BLOCK, 0, st>>>((const T *)x->data, n_out, n_red, pl.rx[0], (int64_t *)out->data);
-        return MD_LAUNCH_CHECK("argreduce(cols,vec)");
-      }
-      // a middle axis reduced: (outer, n_red, inner) with the inner axis contiguous — `outer` column problems in one launch of the strips
-      // kernel (the predicate of the batched column sums above); up to here these went to k_arg_block / k_arg_thread, a block or a
-      // thread per output walking its column with the row stride. (md_build_redplan merges neighbouring kept axes whose strides nest in x
-      // and in out, so (2,3,[64],256) and (2,[64],4,64) arrive here as nk == 2 as well: profiles/middle_axis_4d_kernel_stats.csv)
-      if (same && md_opt(MD_OPT_ARG_BATCHED) != 0 && pl.nk == 2 && pl.nr == 1 && pl.kx[1] == 1 && pl.ko[1] == 1 && pl.ko[0] == pl.kshape[1] &&
-          (pl.kshape[1] % V) == 0 && (pl.rx[0] % V) == 0 && (pl.kx[0] % V) == 0 && ((uintptr_t)x->data & 15) == 0 && pl.kshape[1] >= 256 &&
-          pl.n_red >= 64 && pl.n_red < (1ll << 31) && pl.kshape[0] <= 65535) {
-        const int64_t outer = pl.kshape[0], inner = pl.kshape[1], n_red = pl.n_red;
-        const int64_t NS = ceil_div(inner, 64 * V);
-        const int arg_blocks = md_opt(MD_OPT_ARG_BLOCKS) > 0 ? (int)md_opt(MD_OPT_ARG_BLOCKS) : MD_NUM_CUS;
-        int64_t NB = ceil_div(arg_blocks, NS * outer);   // one block per CU over all the batches
-        if (NB > 64) NB = 64;
-        if (NB > n_red / 32) NB = n_red / 32;
-        if (NB < 1) NB = 1;
-        if (NS * outer * MD_TICKET_PAD > MD_TICKET_WORDS) NB = 1;
-        while (NB > 1 && NB * inner * 8 >= (1ll << 31)) NB /= 2;   // (32-bit byte offsets into a batch's partial rows)
-        constexpr int ARG_RB = 4;
-        void *pv = nullptr, *pi = nullptr;
-        if (NB > 1) {
-          MD_TRY(mdhip_alloc((size_t)(outer * NB * inner) * sizeof(T), &pv));
-          const int rc = mdhip_alloc((size_t)(outer * NB * inner) * (V == 4 ? 4 : 8), &pi);
-          if (rc != MDHIP_OK) { mdhip_free(pv); return rc; }
-        }
-        const dim3 grid((unsigned)(NS * NB), (unsigned)outer);
-        MD_LAUNCH((k_arg_cols_strips<IsMax, T, ARG_RB>), grid, MD_BLOCK, (const T *)x->data, inner, n_red, pl.rx[0], (int)NS, (int)NB, (T *)pv, pi, md_tickets(),
-                  (int64_t *)out->data, (int64_t)pl.kx[0], (int64_t)inner);
-        const int rc = MD_LAUNCH_CHECK("argreduce(cols,strips,batched)");
-        if (pv) mdhip_free(pv);
-        if (pi) mdhip_free(pi);
-        return rc;
-      }
-      // reduced axis contiguous
-      if (same && pl.nr == 1 && pl.rx[0] == 1 && pl.n_red >= 1024 && pl.n_out < (1ll << 30)) {
-        // ~2048 blocks in total, each with >= 8192 items of its row
-        int64_t splits = 2048 / pl.n_out;
-        const int64_t max_splits = ceil_div(pl.n_red, 8192);
-        if (splits > max_splits) splits = max_splits;
-        if (splits < 1) splits = 1;
-        const int64_t chunk = ceil_div(ceil_div(pl.n_red, splits), V) * V;
-        splits = ceil_div(pl.n_red, chunk);
-        if (splits == 1) {
-          k_arg_rows_vec<IsMax, T, true><<<(unsigned)pl.n_out, MD_BLOCK, 0, st>>>(pl, (const T *)x->data, 1, chunk, nullptr, (int64_t *)out->data);
-          return MD_LAUNCH_CHECK("argreduce(rows,vec)");
-        }
-        void *pv = nullptr, *pi = nullptr;
-        MD_TRY(mdhip_alloc((size_t)(splits * pl.n_out) * sizeof(T), &pv));
-        int rc = mdhip_alloc((size_t)(splits * pl.n_out) * sizeof(int64_t), &pi);
-        if (rc != MDHIP_OK) { mdhip_free(pv); return rc; }
-        k_arg_rows_vec<IsMax, T, false><<<(unsigned)(pl.n_out * splits), MD_BLOCK, 0, st>>>(pl, (const T *)x->data, splits, chunk, (T *)pv, (int64_t *)pi);
-        k_arg_rows_finish<IsMax, T><<<(unsigned)ceil_div(pl.n_out, MD_BLOCK), MD_BLOCK, 0, st>>>(pl, (const T *)pv, (const int64_t *)pi, splits, (int64_t *)out->data);
-        rc = MD_LAUNCH_CHECK("argreduce(rows,vec,split)");
-        mdhip_free(pv);
-        mdhip_free(pi);
-        return rc;
-      }
-    }
-    const bool typed = x->dtype == md_dtype_of<T>::value;
-    if (pl.nr == 1 && pl.rx[0] == 1 && pl.n_red >= 24 && (pl.n_red < 1024 || !typed) && pl.n_red <= 65536 && pl.n_out >= 64) {
-      int64_t blocks = ceil_div(pl.n_out, MD_BLOCK / 64);
-      if (blocks > 8 * MD_NUM_CUS) blocks = 8 * MD_NUM_CUS;
-      if (typed) MD_LAUNCH((k_arg_rows_wave<IsMax, T, true>), (unsigned)blocks, MD_BLOCK, pl, x->data, x->dtype, (int64_t *)out->data);
-      else MD_LAUNCH((k_arg_rows_wave<IsMax, T, false>), (unsigned)blocks, MD_BLOCK, pl, x->data, x->dtype, (int64_t *)out->data);
-      return MD_LAUNCH_CHECK("argreduce(rows,wave)");
-    }
-    if (pl.n_red >= 512 && pl.n_out < (1ll << 30)) {
-      k_arg_block<IsMax, T><<<(unsigned)pl.n_out, MD_BLOCK, 0, st>>>(pl, x->data, x->dtype, (int64_t *)out->data);
-      return MD_LAUNCH_CHECK("argreduce(block)");
-    }
-    k_arg_thread<IsMax, T><<<md_grid_for(pl.n_out), MD_BLOCK, 0, st>>>(pl, x->data, x->dtype, (int64_t *)out->data);
-    return MD_LAUNCH_CHECK("argreduce(thread)");
+    return run_arg<IsMax, T>(plan_arg(pl, x, (int64_t)sizeof(T), md_dtype_of<T>::value), pl, x, out);
   }
 };
 

@@ -29,9 +29,7 @@
 #include <type_traits>
 
 #include "md_hip.h"
-
-extern "C" int mdhip_alloc(size_t, void **);
-extern "C" int mdhip_free(void *);
+#include "md_strips.h"
 
 namespace {
 
@@ -524,10 +522,7 @@ template <class TS, int NCT> int launch_colsum(const SkinnyArgs &a, int64_t batc
   typedef typename SkT<TS>::C T;   // (the partials' type)
   constexpr int V = 16 / sizeof(typename SkT<TS>::S);
   const int64_t NS = (a.R + 64 * V - 1) / (64 * V);
-  int64_t NB = (1024 + NS * batch - 1) / (NS * batch);   // ~1024 blocks
-  if (NB > 64) NB = 64;
-  if (NB > a.K / 32) NB = a.K / 32;
-  if (NB < 1) NB = 1;
+  int64_t NB = md_strips_bands(NS * batch, 1024, MD_CEIL, a.K, 32);   // ~1024 blocks
   if (NB > 1 && NS * batch * MD_TICKET_PAD > MD_TICKET_WORDS) NB = 1;
   while (NB > 1 && NB * NCT * a.R * (int64_t)sizeof(T) >= (1ll << 31)) NB /= 2;   // (32-bit byte offsets into a batch's partial planes)
   void *partial = nullptr;

@@ -1,4 +1,4 @@
-"""Every launch form of mdhip_var (csrc/moments.hip: variance / std along one axis) and of HipExec::argreduce (csrc/reduce.hip:
+"""Every launch form of mdhip_var (csrc/moments.hip: variance / std along one axis) and of plan_arg / run_arg (csrc/reduce.hip:
 argmax / argmin along one axis) against exact references — the companion of tests/test_reduce_paths.py for the two reduction
 families that module leaves out.
 

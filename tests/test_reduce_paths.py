@@ -1,8 +1,9 @@
-"""Every launch form of the plain reductions (csrc/reduce.hip, HipExec::reduce: sum, prod, max, min, any / all over an axis)
-against exact references.
+"""Every launch form of the plain reductions (csrc/reduce.hip, plan_reduce / run_reduce: sum, prod, max, min, any / all over an
+axis) against exact references.
 
 The centre is TABLE: what an entry reaches, the array it is cut from, the view taken, the reduced axes, the dtypes. There is no
-hook that reports which kernel ran: every shape is derived from the launcher's predicates (MD_NUM_CUS 256, MD_BLOCK 256,
+hook that reports which kernel ran: every shape is derived from the planner's predicates (plan_reduce, whose tests stand in the
+order of the route; MD_NUM_CUS 256, MD_BLOCK 256,
 MD_TICKET_WORDS 16384, MD_TICKET_PAD 16; V = 16 bytes / element size); the `reaches` column is to be confirmed by a kernel trace of
 the gpu half (profiles/README.md: reduce_paths_kernel_stats.csv). The calls go through the C-ABI as ndarray._reduce does at its end
 (DeviceArray.empty + lib.reduce), so that neither _staged_reduce nor lazy fusion re-expresses them; test_public_functions runs
