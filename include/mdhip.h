@@ -60,7 +60,9 @@ enum {
    * Arrays of these types live in device memory, are moved by mdhip_h2d / mdhip_d2h and converted by mdhip_convert, and are
    * computed on DIRECTLY by mdhip_unary / mdhip_binary / mdhip_where / mdhip_reduce (each operand read in its own type, the
    * arithmetic in the loop dtype's carrier: int32 / int64 / uint64 / float32) and by mdhip_matmul for the float16, int8 and
-   * uint8 triples. What no entry point takes (products of mixed or other narrow dtypes, mean / std) the host composes as
+   * uint8 triples, and by mdhip_var (x read in its own type: float32 arithmetic for float16, float64 for the integers). The
+   * sum behind `mean` is mdhip_reduce with the narrow x and out in NumPy's accumulator (float32 / float64). What no entry point
+   * takes (products of mixed or other narrow dtypes, the shapes mdhip_var refuses) the host composes as
    * promote -> compute in a wide type -> demote (what NumPy's own float16 loops do; integer wrap-around falls out of the
    * truncating conversion). */
   MDHIP_I8 = 5,
@@ -251,11 +253,18 @@ int mdhip_reduce(int op, const mdhip_array *x, const mdhip_array *out, uint32_t 
 /* Variance / standard deviation along ONE axis in a single entry point. NumPy's np.std (numpy.py:57, called by definitions.py:209-221
  * in the forward pass and again in the vjp) is mean -> x - mean -> square -> sum -> divide -> sqrt: four reads and two writes of the
  * array when composed from the entry points above; this is one read (rows) or two (columns), same arithmetic up to the order of the
- * two sums. x: float32 / float64, C-contiguous, 16-B aligned, viewed as (outer, n, inner) around the reduced axis (leading axes
- * collapse into outer, trailing ones into inner). Accepted: rows, inner == 1 (row length a multiple of 16 B); columns, outer == 1
- * (inner >= 256 and a multiple of 16 B, n >= 64); and the batched column form, outer > 1 and inner > 1 — a MIDDLE axis reduced, `outer`
- * column problems in one launch — under the column form's conditions and outer <= 65535 (option var_batched 0 switches it off).
- * out: C-contiguous, x's dtype, one element
+ * two sums. x: float32 / float64 or one of the seven storage-only dtypes, C-contiguous, 16-B aligned, viewed as (outer, n, inner)
+ * around the reduced axis (leading axes collapse into outer, trailing ones into inner). With V = 16 / the element size of x (the
+ * elements of one 16-B load: 2 .. 16) accepted are: rows, inner == 1 (n % V == 0; a row longer than 4096 vectors — float64: 16384
+ * elements — only with outer >= 256: a few long rows are refused); columns, outer == 1 (inner % V == 0, inner >= 256 — which covers
+ * inner >= V — and n >= 64); and the batched column form, outer > 1 and inner > 1 — a MIDDLE axis reduced, `outer` column problems in
+ * one launch — under the column form's conditions and outer <= 65535 (option var_batched 0 switches it off).
+ * Storage-only x is loaded in its own type, 16 B per lane, and converted in registers (option var_narrow 0 refuses it):
+ *   float16 x: float32 arithmetic, out is float16 — the final float32 value rounded once (not NumPy's float16 intermediates);
+ *   int8/16, uint8/16/32/64 x: every element converted to float64 straight from its own type (uint64: its whole range), float64
+ *   arithmetic, out is float64;
+ * float32 / float64 x: out has x's dtype. Any other x / out pairing is MDHIP_ETYPE (bool / int32 / int64 x: MDHIP_EVALUE).
+ * out: C-contiguous, 16-B aligned, one element
  * per kept position; result = sum((x - mean)^2) / (n - ddof), square-rooted when take_sqrt != 0. Requires n - ddof > 0.
  * Any other form returns MDHIP_EVALUE and the caller composes the result from the other entry points (as NumPy does). */
 int mdhip_var(const mdhip_array *x, const mdhip_array *out, int32_t axis, int64_t ddof, int take_sqrt);

@@ -59,7 +59,8 @@
   X(ARG_BLOCKS, "arg_blocks", 0, 'x')                  /* blocks of the strips arg-reduction (0: one per CU) */                 \
   X(ARG_BATCHED, "arg_batched", 1, 'x')                /* 0: argmax / argmin over a middle axis keep the block / thread kernels (A/B) */ \
   X(VAR_BATCHED, "var_batched", 1, 'x')                /* 0: mdhip_var refuses a middle axis, the caller composes (A/B) */      \
-  X(GATHER_RUNS, "gather_runs", 1, 'x')                                                                                         \
+  X(VAR_NARROW, "var_narrow", 1, 'x')                  /* 0: mdhip_var refuses float16 / small-integer x, the caller promotes and composes (A/B) */ \
+  X(GATHER_RUNS, "gather_runs", 1, 'x')                                                                                    \
   X(SCATTER_CENSUS, "scatter_census", 1, 'x')                                                                                   \
   X(SCATTER_SORTED, "scatter_sorted", 1, 'x')          /* 0: element-granular duplicates by bid / apply rounds (A/B) */
 

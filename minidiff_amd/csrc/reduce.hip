@@ -367,12 +367,16 @@ __global__ void __launch_bounds__(MD_BLOCK) k_reduce_cols_vec(const Tacc *__rest
 // combined through LDS in wave order, bands through write-through partial rows and a ticket per strip (md_ticket.h):
 // the block that arrives last at its strip's counter adds the strip's NB partial rows in band order. No atomics on
 // data, fixed order: bit-identical from run to run.
-template <class R, class Tacc, int RB, bool NT>
-__global__ void __launch_bounds__(MD_BLOCK) k_reduce_cols_strips(const Tacc *__restrict__ x, int64_t n_out, int64_t n_red, int64_t rs, int NS,
+// S: the matrix's storage type — the accumulator's own, or a storage-only dtype (the column sums of mean / std: float16 into float,
+// the small integers into double). A lane then owns V = 16 / sizeof(S) columns (16 of int8), still one 16-B load per row, each
+// element converted in registers; the accumulators, LDS rows, partial rows and `out` are Tacc's, V per lane (several 16-B words).
+template <class R, class Tacc, int RB, bool NT, class S = Tacc>
+__global__ void __launch_bounds__(MD_BLOCK) k_reduce_cols_strips(const S *__restrict__ x, int64_t n_out, int64_t n_red, int64_t rs, int NS,
                                                                 int NB, Tacc *partial, unsigned *tickets, Tacc *__restrict__ out,
                                                                 int64_t x_bs, int64_t o_bs) {
-  constexpr int V = 16 / sizeof(Tacc);
-  typedef MdVec<Tacc, V> Vec;
+  constexpr int V = 16 / sizeof(S);
+  typedef MdVec<S, V> XVec;     // one 16-B load of x
+  typedef MdVec<Tacc, V> Vec;   // the same columns as accumulators
   __shared__ Vec sm[3][64];
   __shared__ unsigned last_flag;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -392,19 +396,19 @@ __global__ void __launch_bounds__(MD_BLOCK) k_reduce_cols_strips(const Tacc *__r
   Tacc acc[V];
 #pragma unroll
   for (int j = 0; j < V; ++j) acc[j] = R::template identity<Tacc>();
-  const Tacc *p = x + col + first * rs;
+  const S *p = x + col + first * rs;
   const int64_t rstep = step * rs;
-  Vec t[2][RB];
+  XVec t[2][RB];
   auto load = [&](int buf, int64_t bt) {
     const int64_t i0 = (bt < nb ? bt : nb - 1) * RB;  // a prefetch past the end re-reads the last batch (discarded): no branch
 #pragma unroll
-    for (int u = 0; u < RB; ++u) t[buf][u] = md_ld_once<NT>(reinterpret_cast<const Vec *>(p + (i0 + u) * rstep));
+    for (int u = 0; u < RB; ++u) t[buf][u] = md_ld_once<NT>(reinterpret_cast<const XVec *>(p + (i0 + u) * rstep));
   };
   auto add = [&](int buf) {
 #pragma unroll
     for (int u = 0; u < RB; ++u)
 #pragma unroll
-      for (int j = 0; j < V; ++j) acc[j] = R::combine(acc[j], t[buf][u].v[j]);
+      for (int j = 0; j < V; ++j) acc[j] = R::combine(acc[j], md_cast<Tacc>(t[buf][u].v[j]));
   };
   if (nb > 0) {
     load(0, 0);
@@ -424,9 +428,9 @@ __global__ void __launch_bounds__(MD_BLOCK) k_reduce_cols_strips(const Tacc *__r
     if (bt < nb) add(0);  // odd batch count: the last batch sits in buffer 0
   }
   for (int64_t i = nb * RB; i < nrw; ++i) {
-    const Vec tt = *reinterpret_cast<const Vec *>(p + i * rstep);
+    const XVec tt = *reinterpret_cast<const XVec *>(p + i * rstep);
 #pragma unroll
-    for (int j = 0; j < V; ++j) acc[j] = R::combine(acc[j], tt.v[j]);
+    for (int j = 0; j < V; ++j) acc[j] = R::combine(acc[j], md_cast<Tacc>(tt.v[j]));
   }
   // waves 1..3 -> wave 0, in wave order
   if (w > 0) {
@@ -457,20 +461,30 @@ __global__ void __launch_bounds__(MD_BLOCK) k_reduce_cols_strips(const Tacc *__r
     md_st16_sc1(pr, (unsigned)(((int64_t)b * n_out + col) * (int64_t)sizeof(Tacc)), o);
   }
   if (!md_ticket_last(tickets + s * MD_TICKET_PAD, (unsigned)NB, &last_flag)) return;
-  // the strip's NB (<= 64) partial rows: wave w takes rows w, w + 4, ..; every load ahead of the first add
-  Vec pt[16];
+  // the strip's NB (<= 64) partial rows: wave w takes rows w, w + 4, ..
+  if constexpr (sizeof(Vec) == 16) {   // every load ahead of the first add
+    Vec pt[16];
 #pragma unroll
-  for (int k = 0; k < 16; ++k) {
-    const int r = w + 4 * k;
-    if (r < NB) pt[k] = md_ld16_sc1<Vec>(pr, (unsigned)(((int64_t)r * n_out + col) * (int64_t)sizeof(Tacc)));
-  }
+    for (int k = 0; k < 16; ++k) {
+      const int r = w + 4 * k;
+      if (r < NB) pt[k] = md_ld16_sc1<Vec>(pr, (unsigned)(((int64_t)r * n_out + col) * (int64_t)sizeof(Tacc)));
+    }
 #pragma unroll
-  for (int j = 0; j < V; ++j) acc[j] = R::template identity<Tacc>();
+    for (int j = 0; j < V; ++j) acc[j] = R::template identity<Tacc>();
 #pragma unroll
-  for (int k = 0; k < 16; ++k) {
-    if (w + 4 * k < NB) {
+    for (int k = 0; k < 16; ++k) {
+      if (w + 4 * k < NB) {
 #pragma unroll
-      for (int j = 0; j < V; ++j) acc[j] = R::combine(acc[j], pt[k].v[j]);
+        for (int j = 0; j < V; ++j) acc[j] = R::combine(acc[j], pt[k].v[j]);
+      }
+    }
+  } else {   // a storage-only x: a partial row is 2 .. 8 words per lane, sixteen of them do not fit the registers — row by row, same order
+#pragma unroll
+    for (int j = 0; j < V; ++j) acc[j] = R::template identity<Tacc>();
+    for (int r = w; r < NB; r += 4) {
+      const Vec pt = md_ld16_sc1<Vec>(pr, (unsigned)(((int64_t)r * n_out + col) * (int64_t)sizeof(Tacc)));
+#pragma unroll
+      for (int j = 0; j < V; ++j) acc[j] = R::combine(acc[j], pt.v[j]);
     }
   }
   if (w > 0) {
@@ -930,6 +944,7 @@ struct RedLaunch {
   int NV;                 // rows-wave: 16-B vectors per lane
   bool nt;                // non-temporal loads (operands larger than the Infinity Cache are read once)
   bool typed;             // arg rows-wave: x has the compare type itself
+  bool narrow;            // strips: x is read in its own storage-only type (red_stats_pair)
   size_t partial_bytes, index_bytes;   // temporaries: the partial values, the partial indices of an arg form (0: none)
 };
 static RedLaunch &red_pick(RedLaunch &L, RedForm f, const char *label) {
@@ -944,11 +959,19 @@ struct RedTraits {
   bool same_out;             // Tacc == To
   bool cheap;                // the strips walk serves it (f64 / integer max and min keep the tiled kernel — their compare chain wants more waves per CU)
   bool anyall;
+  bool sum;                  // R is RSum
 };
 template <class R, class Tacc, class To> constexpr RedTraits red_traits() {
   return {(int)sizeof(Tacc), md_dtype_of<Tacc>::value, md_same<Tacc, To>::value,
           md_same<R, RSum>::value || md_same<R, RProd>::value || ((md_same<R, RMax>::value || md_same<R, RMin>::value) && md_same<Tacc, float>::value),
-          md_same<R, RAny>::value || md_same<R, RAll>::value};
+          md_same<R, RAny>::value || md_same<R, RAll>::value, md_same<R, RSum>::value};
+}
+// The sums of the statistics (mean, and the first pass of mdhip_var's column forms) over a storage-only dtype, in NumPy's accumulator:
+// float16 -> float32, the integers -> float64 (each element converted straight from its own type: uint64 its whole range). These
+// pairs alone take the strips forms with a storage type of their own; int8 -> int64 and the other plain sums keep their routes.
+static bool red_stats_pair(const RedTraits &t, int xdt) {
+  if (!t.sum || !md_is_narrow(xdt)) return false;
+  return xdt == MDHIP_F16 ? t.acc_dtype == MDHIP_F32 : t.acc_dtype == MDHIP_F64;
 }
 // k_reduce_all over a storage-only dtype: only the accumulator types such an input can meet (md_dispatch.h). Of an integer
 // accumulator `cheap` says sum / prod, its absence max / min.
@@ -956,6 +979,8 @@ static bool red_all_narrow_ok(const RedTraits &t, int xdt) {
   const bool small = xdt == MDHIP_I8 || xdt == MDHIP_I16 || xdt == MDHIP_U8 || xdt == MDHIP_U16;
   if (t.acc_dtype == MDHIP_I64) return t.cheap ? (small || xdt == MDHIP_U32 || xdt == MDHIP_U64) : xdt == MDHIP_U32;
   if (t.acc_dtype == MDHIP_I32) return !t.cheap && small;
+  // (the whole-array mean of the small integers: sums below 2^53 are exact in any order — not uint32 / uint64, whose are not)
+  if (t.acc_dtype == MDHIP_F64) return t.sum && small;
   return t.acc_dtype == MDHIP_F32 && xdt == MDHIP_F16;
 }
 
@@ -1009,32 +1034,36 @@ static RedLaunch plan_reduce(const MdRedPlan &pl, const mdhip_array *x, const md
   const bool wide = pl.nk >= 1 && pl.kshape[pl.nk - 1] >= 64;
   if (cols_ok && (!rows_ok || n_out >= 1024 || (wide && (asz >= 4 || n_out >= 256)))) {   // (1-byte accumulators — any / all — from 256 columns on)
     if (asz >= 4 && t.same_out) {
+      // the strips forms read x in the accumulator's type or, for the statistics' pairs, in its own: SV columns per lane and 16-B load
+      const bool stats = red_stats_pair(t, x->dtype);
+      const int64_t SV = stats ? 16 / (int64_t)md_dtype_size(x->dtype) : V;
       const bool vec_ok = pl.nk == 1 && pl.nr == 1 && pl.ko[0] == 1 && typed && (n_out % V) == 0 && (pl.rx[0] % V) == 0 && x_al && out_al && n_red >= 16;
-      if (t.cheap && vec_ok && n_red >= 512) {
+      const bool strips_ok = stats ? pl.nk == 1 && pl.nr == 1 && pl.ko[0] == 1 && pl.kx[0] == 1 && (n_out % SV) == 0 && (pl.rx[0] % SV) == 0 && x_al && out_al : vec_ok;
+      if (t.cheap && strips_ok && n_red >= 512) {
         const int nb_force = (int)md_opt(MD_OPT_COLS_NB);
-        const int64_t NS = ceil_div(n_out, 64 * V);
+        const int64_t NS = ceil_div(n_out, 64 * SV);
         // one block per CU (two per CU ran 15 % slower, half a block per CU 20 %: profiles/r3_reduce_lab.txt); option cols_nb
         // forces the count (still clamped)
         const int64_t NB = nb_force > 0 ? md_strips_bands(1, nb_force, MD_FLOOR, n_red, 4 * RED_RB) : md_strips_bands(NS, MD_NUM_CUS, MD_FLOOR, n_red, 4 * RED_RB);
         // tickets that do not fit: decline — the tiled kernels below take it (the batched forms and var fall to one band instead)
         if (NS * NB >= MD_NUM_CUS / 4 && NS * NB < (1ll << 31) && (NB == 1 || NS * MD_TICKET_PAD <= MD_TICKET_WORDS)) {
-          L.NS = NS; L.NB = NB; L.outer = 1;
-          L.nt = n_red * n_out * asz > ((int64_t)320 << 20);
+          L.NS = NS; L.NB = NB; L.outer = 1; L.narrow = stats;
+          L.nt = n_red * n_out * (int64_t)md_dtype_size(x->dtype) > ((int64_t)320 << 20);
           L.partial_bytes = NB > 1 ? (size_t)(NB * n_out) * asz : 0;
-          return red_pick(L, RED_COLS_STRIPS, "reduce(cols,strips)");
+          return red_pick(L, RED_COLS_STRIPS, stats ? "reduce(cols,strips, storage-only dtype)" : "reduce(cols,strips)");
         }
       }
       // a middle axis reduced: (outer, n_red, inner) with the inner axis contiguous — `outer` independent column problems in one launch
-      if (t.cheap && pl.nk == 2 && pl.nr == 1 && pl.kx[1] == 1 && pl.ko[1] == 1 && pl.ko[0] == pl.kshape[1] && typed && (pl.kshape[1] % V) == 0 &&
-          (pl.rx[0] % V) == 0 && (pl.kx[0] % V) == 0 && x_al && out_al && pl.kshape[0] <= 65535 && pl.kshape[1] >= 256 && n_red >= 64) {
+      if (t.cheap && pl.nk == 2 && pl.nr == 1 && pl.kx[1] == 1 && pl.ko[1] == 1 && pl.ko[0] == pl.kshape[1] && (typed || stats) && (pl.kshape[1] % SV) == 0 &&
+          (pl.rx[0] % SV) == 0 && (pl.kx[0] % SV) == 0 && x_al && out_al && pl.kshape[0] <= 65535 && pl.kshape[1] >= 256 && n_red >= 64) {
         const int64_t outer = pl.kshape[0], inner = pl.kshape[1];
-        const int64_t NS = ceil_div(inner, 64 * V);
+        const int64_t NS = ceil_div(inner, 64 * SV);
         const int64_t NB = md_strips_bands(NS * outer, MD_NUM_CUS, MD_FLOOR, n_red, 4 * RED_RB);   // one block per CU over all the batches
         // tickets that do not fit: decline, as the plain form
         if (NB == 1 || NS * outer * MD_TICKET_PAD <= MD_TICKET_WORDS) {
-          L.NS = NS; L.NB = NB; L.outer = outer;
+          L.NS = NS; L.NB = NB; L.outer = outer; L.narrow = stats;
           L.partial_bytes = NB > 1 ? (size_t)(outer * NB * inner) * asz : 0;
-          return red_pick(L, RED_COLS_STRIPS_BATCHED, "reduce(cols,strips,batched)");
+          return red_pick(L, RED_COLS_STRIPS_BATCHED, stats ? "reduce(cols,strips,batched, storage-only dtype)" : "reduce(cols,strips,batched)");
         }
       }
       // (the tiled kernels from here on serve what the strips forms do not cover: narrow / ragged / short problems)
@@ -1135,6 +1164,24 @@ static int run_reduce(const RedLaunch &L, const MdRedPlan &pl, const mdhip_array
         const dim3 grid((unsigned)(L.NS * L.NB), (unsigned)L.outer);
         // plain: n_out columns, no batch steps; batched: `outer` problems of kshape[1] columns, kx[0] apart in x, a row of out each
         const int64_t cols = batched ? pl.kshape[1] : n_out, x_step = batched ? pl.kx[0] : 0, o_step = batched ? pl.kshape[1] : 0;
+        if (L.narrow) {
+#define MD_RED_STRIPS_AS(DT, S)                                                                                                                         \
+  if (x->dtype == DT) {                                                                                                                                 \
+    with_flag(L.nt, [&](auto NT) {                                                                                                                      \
+      MD_LAUNCH((k_reduce_cols_strips<R, Tacc, RED_RB, decltype(NT)::value, S>), grid, MD_BLOCK, (const S *)x->data, cols, n_red, pl.rx[0], (int)L.NS, \
+                (int)L.NB, partial, md_tickets(), (Tacc *)out->data, x_step, o_step);                                                                   \
+    });                                                                                                                                                 \
+    break;                                                                                                                                              \
+  }
+          // (the instances red_stats_pair admits)
+          if constexpr (t.sum && md_same<Tacc, float>::value) { MD_RED_STRIPS_AS(MDHIP_F16, f16) }
+          if constexpr (t.sum && md_same<Tacc, double>::value) {
+            MD_RED_STRIPS_AS(MDHIP_I8, int8_t) MD_RED_STRIPS_AS(MDHIP_I16, int16_t) MD_RED_STRIPS_AS(MDHIP_U8, uint8_t) MD_RED_STRIPS_AS(MDHIP_U16, uint16_t)
+            MD_RED_STRIPS_AS(MDHIP_U32, uint32_t) MD_RED_STRIPS_AS(MDHIP_U64, uint64_t)
+          }
+#undef MD_RED_STRIPS_AS
+          return red_unplanned(L);
+        }
         with_flag(L.nt, [&](auto NT) {
           MD_LAUNCH((k_reduce_cols_strips<R, Tacc, RED_RB, decltype(NT)::value>), grid, MD_BLOCK, (const Tacc *)x->data, cols, n_red, pl.rx[0], (int)L.NS, (int)L.NB,
                     partial, md_tickets(), (Tacc *)out->data, x_step, o_step);
@@ -1182,6 +1229,9 @@ static int run_reduce(const RedLaunch &L, const MdRedPlan &pl, const mdhip_array
         }
         if constexpr (md_same<Tacc, int64_t>::value && !t.cheap) { MD_RED_ALL_AS(MDHIP_U32, uint32_t) }
         if constexpr (md_same<Tacc, float>::value) { MD_RED_ALL_AS(MDHIP_F16, f16) }
+        if constexpr (md_same<Tacc, double>::value && t.sum) {
+          MD_RED_ALL_AS(MDHIP_I8, int8_t) MD_RED_ALL_AS(MDHIP_I16, int16_t) MD_RED_ALL_AS(MDHIP_U8, uint8_t) MD_RED_ALL_AS(MDHIP_U16, uint16_t)
+        }
 #undef MD_RED_ALL_AS
       }
       return red_unplanned(L);

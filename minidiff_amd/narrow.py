@@ -9,7 +9,11 @@ by index arrays (csrc/index.hip: elements move by size; np.add.at wraps the inte
 contribution, in index order, as NumPy's unbuffered loop does), and the products of the three pairs whose NumPy loop is the
 pair's own — float16 @ float16, int8 @ int8, uint8 @ uint8 (matmul / dot / tensordot: csrc/gemm_narrow.hip, the low-precision
 matrix cores); `matmul(a, b, dtype=)` is let through untouched — matmul casts the operands itself, and float16 operands with
-dtype=float32 / int8 operands with dtype=int32 are one native call that keeps the accumulators. The functions listed in COMPUTE below, and the products of every other combination, still go
+dtype=float32 / int8 operands with dtype=int32 are one native call that keeps the accumulators. `mean` and `std` of one concrete
+array with dtype=None read it in its own type too (ndarray._narrow_stat: the sum of `mean` in NumPy's accumulator — float32 for
+float16, float64 for the integers, every element converted in registers; `std` through mdhip_var, csrc/moments.hip, for the shapes
+it takes). The other functions listed in COMPUTE below, the statistics with a dtype= / out= / a pending operand / a shape mdhip_var
+refuses, and the products of every other combination, still go
 
     promote to a wide device type  ->  the ordinary kernel  ->  demote to NumPy's result dtype
 
@@ -44,6 +48,8 @@ _MOVERS = {"concatenate", "stack", "tile", "repeat", "split"}
 # the statistics: NumPy's own first step is float64 (the sum runs in float64, each element converted first), so uint64 widens
 # straight to float64 there — the whole range, no detour through int64
 _STATS = {"mean", "std"}
+# False: mean / std always take the promote route (the A/B switch of scripts/bench_narrow_moments.py; std alone: option var_narrow)
+NATIVE_STATS = True
 # products that run natively (mdhip_matmul takes float16 / int8 / uint8 triples) when both operands have one of these dtypes
 _PRODUCTS = {"matmul", "dot", "tensordot"}
 _NATIVE_PRODUCT = {np.dtype(np.float16), np.dtype(np.int8), np.dtype(np.uint8)}
@@ -54,7 +60,10 @@ _BITS = {"matmul", "dot", "tensordot", "nonzero", "flatnonzero", "argwhere"}
 # Functions whose C entry points take the storage-only dtypes DIRECTLY (one launch, each operand read in its own type, the result
 # written in its own: csrc/narrow.hip, the 12-dtype loads of the reduction kernels) — every elementwise ufunc, where / clip and the
 # reductions — are NOT wrapped. What is wrapped below (promote -> wide kernel -> demote) are the functions that have no kernel for
-# these types yet: products, the composed statistics, the array builders. (Gathers and scatters by index arrays — getitem, setitem,
+# these types yet: products, the array builders — and the statistics, which are wrapped for their LEFTOVERS only: mean / std of one
+# concrete array with dtype=None are handed to ndarray._narrow_stat first (no promoted copy: the narrow array is read once by the sum,
+# once or twice by mdhip_var); a dtype= / out=, a pending lazy operand, a shape mdhip_var refuses or a C-ABI build without its
+# storage-only forms fall through to the promote route below. (Gathers and scatters by index arrays — getitem, setitem,
 # index_add, take_/put_along_axis — move or add in the array's own type: csrc/index.hip.)
 COMPUTE = [
     "mean", "std", "matmul", "dot", "tensordot",
@@ -181,6 +190,10 @@ def install(ns: dict):
                     return fn(*args, **kw)
             if name in _PRODUCTS and native_product(args, kw):
                 return fn(*args, **kw)
+            if name in _STATS and NATIVE_STATS:
+                res = ns["_narrow_stat"](name, args, kw)   # None: not a form read natively
+                if res is not None:
+                    return res
             if name == "matmul" and kw.get("dtype") is not None:
                 return fn(*args, **kw)   # matmul itself casts the operands to the loop's dtype (float16 -> float32, int8 -> int32: natively)
             # NumPy's own verdict on dtypes (and its exceptions) from one-element dummies

@@ -2211,12 +2211,15 @@ def mean(a, axis=None, dtype=None, out=None, keepdims=False, **kw):
     return _finish_out(_binary(np.true_divide, _capi.B_TRUE_DIV, s, n, out=s), out, "mean")
 
 
-def _std_fused(a, axis, dtype, ddof, keepdims, n):
+def _std_fused(a, axis, dtype, ddof, keepdims, n, res_dtype=None):
     """One-pass (rows) / two-pass (columns) kernel for the forms mdhip_var covers: a concrete float32 / float64 C-contiguous array
     reduced over any single axis. The library alone judges the form — rows, columns, or a middle axis as a batch of column problems —
     and refuses what it does not cover (short / narrow / unaligned shapes); that, and anything else -> None and `std` composes
-    NumPy's five steps."""
-    if a._code not in _FLOAT_CODES or a._expr is not None or (dtype is not None and np.dtype(dtype) != a.dtype) or a.ndim == 0:
+    NumPy's five steps. `res_dtype` (from _narrow_stat): `a` has a storage-only dtype, which mdhip_var reads as it is, and the result
+    has this one — NumPy's: float16 for float16, float64 for the integers."""
+    if res_dtype is None and a._code not in _FLOAT_CODES:
+        return None
+    if a._expr is not None or (dtype is not None and np.dtype(dtype) != a.dtype) or a.ndim == 0:
         return None
     if isinstance(axis, (tuple, list)):
         if len(axis) != 1:
@@ -2235,12 +2238,50 @@ def _std_fused(a, axis, dtype, ddof, keepdims, n):
     if n - int(ddof) <= 0 or n < 2 or not a.is_c_contiguous or a.size == 0:
         return None
     kshape = a.shape[:ax] + (1,) + a.shape[ax + 1:]
-    res = DeviceArray._new(kshape, a.dtype)
+    res = DeviceArray._new(kshape, a.dtype if res_dtype is None else res_dtype)
     try:
         _lib().var(a.desc(), res.desc(), ax, int(ddof), 1)
     except ValueError:       # a form the kernel leaves to the composition (alignment, short / narrow shapes, most middle axes)
         return None
+    except TypeError:        # a build of the C-ABI whose mdhip_var knows float32 / float64 alone (the CPU test double)
+        if res_dtype is None:
+            raise
+        return None
     return res if keepdims else reshape(res, a.shape[:ax] + a.shape[ax + 1:])
+
+
+_STAT_ARGS = {"mean": ("axis", "dtype", "out", "keepdims"), "std": ("axis", "dtype", "out", "ddof", "keepdims")}
+
+
+def _narrow_stat(name, args, kw):
+    """mean / std of ONE concrete array of a storage-only dtype with dtype=None and no out=: read in its own type, no promoted copy.
+    mean — the sum in NumPy's accumulator (float32 for float16, float64 for the integers: every element converted in registers,
+    uint64 its whole range), divided by the count; float16 rounds the small result once. std — mdhip_var with the result in NumPy's
+    dtype; what it refuses -> None. None: narrow.py takes the promote -> wide kernel -> demote route."""
+    names = _STAT_ARGS[name]
+    if not args or len(args) > 1 + len(names) or type(args[0]) is not DeviceArray:
+        return None
+    p = dict(zip(names, args[1:]))
+    for k, v in kw.items():
+        if k not in names or k in p:
+            return None
+        p[k] = v
+    a = args[0]
+    if p.get("dtype") is not None or p.get("out") is not None or a._expr is not None or a.size == 0 or a._code < _narrow.NARROW_CODE_MIN:
+        return None
+    axis, keepdims = p.get("axis"), p.get("keepdims", False)
+    if not isinstance(keepdims, (py_bool, np.bool_)):
+        return None
+    f16 = a.dtype == np.float16
+    try:
+        n = _count(a, axis)
+    except Exception:        # (an axis NumPy rejects: the wrapped route raises NumPy's own exception)
+        return None
+    if name == "std":
+        return _std_fused(a, axis, None, p.get("ddof", 0), py_bool(keepdims), n, a.dtype if f16 else np.dtype(np.float64))
+    s = sum(a, axis=axis, dtype=np.dtype(np.float32 if f16 else np.float64), keepdims=py_bool(keepdims))
+    s = _binary(np.true_divide, _capi.B_TRUE_DIV, s, n, out=s)
+    return _convert(s, a.dtype) if f16 else s
 
 
 def std(a, axis=None, dtype=None, out=None, ddof=0, keepdims=False, **kw):
