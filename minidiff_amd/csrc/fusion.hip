@@ -26,6 +26,12 @@
 //                      stride the row's vector groups — fused per-row statistics
 //                      (softmax denominators, row-wise dots, the gradient of a (R,1) scale)
 // Reductions are deterministic (no atomics).
+//
+// Host side (behind the kernels): plan_eval / plan_reduce / plan_eval_reduce_cols choose ONE launch form (enum VmForm) and its
+// numbers into a VmLaunch — generated kernel or interpreter, geometry, grid, scratch bytes — without allocating or launching;
+// reduce_axis, reduce_cols_2d and sweep_cols are rungs of plan_reduce's ladder, and the order of the tests is the route.
+// run_eval<T, To> / run_reduce<R, T> are one switch over the form with the interpreter launches; run_generated (no template)
+// launches every generated kernel.
 #include <vector>
 
 #include "md_hip.h"
@@ -457,6 +463,8 @@ __global__ void __launch_bounds__(MD_BLOCK) k_vm_reduce_rows(MdVmDev P, int64_t 
 namespace {
 
 // ------------------------------------------------------------------------ host ----
+// plan_eval / plan_reduce choose ONE launch form (enum VmForm) and its numbers, without allocating or launching; run_eval /
+// run_reduce are one switch over that form: the interpreter kernels there, every generated kernel through run_generated.
 static void to_dev(const mdhip_vm_program *pr, MdVmDev *D) {
   memset(D, 0, sizeof *D);
   D->n_instr = pr->n_instr;
@@ -470,6 +478,12 @@ static void to_dev(const mdhip_vm_program *pr, MdVmDev *D) {
 static bool al_for(const void *p, int dtype) {
   const uintptr_t al = md_dtype_size(dtype) * 4 > 16 ? 16 : md_dtype_size(dtype) * 4;
   return ((uintptr_t)p % al) == 0;
+}
+static bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
+static int64_t elems_of(const mdhip_array *a) {
+  int64_t n = 1;
+  for (int d = 0; d < a->ndim; ++d) n *= a->shape[d];
+  return n;
 }
 // (rows, inner) geometry usable by the vector kernels? fills leaf os/is.
 static bool fast_geometry(const MdVmIter &it, int n_leaves, const mdhip_vm_program *pr, bool out_contig_required, MdVmDev *D,
@@ -528,62 +542,41 @@ static bool axes_geometry(const MdVmIter &it, const mdhip_vm_program *pr, const 
   return true;
 }
 
-// To: the compute type, b8 (truth values) or f16 (the chain's value rounded ONCE to binary16 in the same pass: astype(chain, float16))
-template <class T, class To> static int eval_typed(const mdhip_vm_program *pr, const mdhip_array *out) {
-  MdVmIter it;
-  MD_TRY(md_vm_build_iter(&it, pr, out, out));
-  if (it.total == 0) return MDHIP_OK;
+// ---- one launch, planned ----
+enum VmForm {
+  VM_NONE,          // nothing to launch: an empty evaluation, or programs that mdhip_vm_eval_multi evaluates one by one
+  VM_EVAL_FAST,     // k_vm_eval_fast | generated EVAL on the (rows, inner) geometry
+  VM_EVAL_AXES,     // k_vm_eval_axes | generated EVAL over three / four collapsed axes
+  VM_EVAL_GENERIC,  // k_vm_eval_generic
+  VM_RED_ALL,       // k_vm_reduce_all | generated RED_ALL: `grid` block partials, the last block finishes
+  VM_COLS_STRIPS,   // generated SWEEP only: NS strips x NB row bands (x outer batches), with or without the evaluated value stored
+  VM_COLS_TILED,    // k_vm_reduce_cols | generated RED_COLS: one pass (splits == 1), or `splits` partial rows and a second pass
+  VM_COLS_BATCHED,  // .. with the batch on the grid: `outer` problems in one launch, unsplit
+  VM_ROWS,          // k_vm_reduce_rows | generated RED_ROWS
+};
+// plan_begin sets the scalars (0; outer = splits = 1); the four tables are NOT zeroed per call and hold something only where a
+// planner filled them: D in every form but VM_NONE, `it` where md_vm_build_iter ran (not on reduce_axis's path), G and B as noted.
+struct VmLaunch {
+  VmForm form;
+  hipFunction_t fn;          // the generated kernel; nullptr: the interpreter kernel of the form
   MdVmDev D;
-  to_dev(pr, &D);
-  hipStream_t st = md_stream();
-  int64_t rows, inner;
-  constexpr bool to_bool = md_same<To, b8>::value, to_f16 = md_same<To, f16>::value;
-  if (fast_geometry(it, pr->n_leaves, pr, true, &D, &rows, &inner) && al_for(out->data, out->dtype)) {
-    if (jit::enabled() && it.total >= jit::min_elems()) {
-      // the streamed bytes of this launch: output + distinct vector leaves
-      int64_t bytes = it.total * (int64_t)md_dtype_size(out->dtype);
-      for (int l = 0; l < pr->n_leaves; ++l)
-        if (D.leaf[l].is) bytes += it.total * (int64_t)md_dtype_size(pr->leaves[l].dtype);
-      jit::Spec S;
-      S.kind = jit::EVAL;
-      jit::spec_single(&S, pr);
-      jit::spec_modes(&S, D, rows);
-      S.out_bool = to_bool;
-      S.out_f16 = to_f16;
-      S.nt = bytes > ((int64_t)320 << 20);
-      jit::eval_shape(&S);
-      if (hipFunction_t fn = jit::get(S)) {
-        jit::JArgs A;
-        jit::fill_args(&A, pr, D);
-        A.outs[0] = out->data;
-        const int grid = jit::stream_grid(&A, rows, inner, jit::eval_blocks(S));
-        return jit::launch(fn, A, dim3((unsigned)grid));
-      }
-    }
-    const int64_t work = (rows * (inner >> 2) + VG - 1) / VG + (rows == 1 ? 4 : 0);
-    k_vm_eval_fast<T, To><<<md_grid_for(work), MD_BLOCK, 0, st>>>(D, (To *)out->data, rows, inner);
-    return MD_LAUNCH_CHECK("vm_eval(fast)");
-  }
-  VmAxes A;
-  if (axes_geometry(it, pr, out, &D, &A)) {
-    if (jit::enabled() && it.total >= jit::min_elems()) {
-      jit::Spec S;
-      S.kind = jit::EVAL;
-      jit::spec_single(&S, pr);
-      S.out_bool = to_bool;
-      S.out_f16 = to_f16;
-      jit::spec_axes(&S, D, A, (int64_t)md_dtype_size(out->dtype));
-      if (hipFunction_t fn = jit::get(S)) {
-        void *outs[1] = {out->data};
-        return jit::launch_axes(fn, S, D, A, pr->imm, outs);
-      }
-    }
-    k_vm_eval_axes<T, To><<<md_grid_for(it.total >> 2), MD_BLOCK, 0, st>>>(D, A, (To *)out->data);
-    return MD_LAUNCH_CHECK("vm_eval(axes)");
-  }
-  k_vm_eval_generic<T, To><<<md_grid_for(it.total), MD_BLOCK, 0, st>>>(D, it, (To *)out->data);
-  return MD_LAUNCH_CHECK("vm_eval(generic)");
-}
+  MdVmIter it;               // (VM_EVAL_GENERIC reads it in the kernel)
+  VmAxes G;                  // VM_EVAL_AXES
+  VmBatch B;                 // VM_COLS_BATCHED, VM_COLS_STRIPS with `batch`
+  const double *imm;         // the immediates a generated kernel takes as arguments: n_imm of them
+  int n_imm;
+  int n;                     // outputs of an evaluation
+  bool batch;
+  int64_t rows, inner;       // the (rows, inner) geometry of D
+  int64_t n_out, n_red, outer, chunk, splits, NS, NB;
+  int64_t grid;              // blocks on x (the strips: NS * NB)
+  size_t partial_bytes;      // scratch the launch needs (block partials, partial rows), in the compute type; 0: none
+};
+
+static int vm_unplanned(const VmLaunch &L) { return md_fail(MDHIP_ERUNTIME, "vm: launch form %d has no launcher here", (int)L.form); }
+
+// blocks of the interpreter's streaming kernels (k_vm_eval_fast, k_vm_reduce_all)
+static int interp_grid(int64_t rows, int64_t inner) { return md_grid_for((rows * (inner >> 2) + VG - 1) / VG + (rows == 1 ? 4 : 0)); }
 
 // merge the leaf tables of n programs (identical descriptors share a slot) and give every
 // immediate its slot in the shared array; false if the bounds of one launch are exceeded
@@ -635,55 +628,86 @@ static bool merge_programs(const mdhip_vm_program *progs, int n, jit::Spec *M, m
   return M->n_leaves > 0;
 }
 
-static int eval_multi(const mdhip_vm_program *progs, const mdhip_array *outs, int n, bool *done) {
-  *done = false;
-  if (!jit::enabled()) return MDHIP_OK;
-  jit::Spec M;
-  mdhip_vm_program merged;
-  if (!merge_programs(progs, n, &M, &merged)) return MDHIP_OK;
-  for (int k = 0; k < n; ++k) {  // outputs: the compute dtype, contiguous, one shape
-    if (outs[k].dtype != merged.compute_dtype || outs[k].ndim != outs[0].ndim) return MDHIP_OK;
-    for (int d = 0; d < outs[0].ndim; ++d)
-      if (outs[k].shape[d] != outs[0].shape[d] || outs[k].strides[d] != outs[0].strides[d]) return MDHIP_OK;
-    if (((uintptr_t)outs[k].data & 15) != 0) return MDHIP_OK;
-  }
-  MdVmIter it;
-  if (md_vm_build_iter(&it, &merged, &outs[0], &outs[0]) != MDHIP_OK) return MDHIP_OK;
-  if (it.total < jit::min_elems()) return MDHIP_OK;
-  MdVmDev D;
-  to_dev(&merged, &D);
-  int64_t rows, inner;
-  if (!fast_geometry(it, merged.n_leaves, &merged, true, &D, &rows, &inner)) {
-    // three / four collapsed axes: the axes form of the same kernel, still one launch
-    VmAxes G;
-    if (!axes_geometry(it, &merged, &outs[0], &D, &G)) return MDHIP_OK;
-    jit::spec_axes(&M, D, G, (int64_t)n * (int64_t)md_dtype_size(merged.compute_dtype));
-    hipFunction_t fn = jit::get(M);
-    if (!fn) return MDHIP_OK;
-    void *po[4] = {};
-    for (int k = 0; k < n; ++k) po[k] = outs[k].data;
-    *done = true;
-    return jit::launch_axes(fn, M, D, G, merged.imm, po);
-  }
-  int64_t bytes = (int64_t)n * it.total * (int64_t)md_dtype_size(merged.compute_dtype);
-  for (int l = 0; l < merged.n_leaves; ++l)
-    if (D.leaf[l].is) bytes += it.total * (int64_t)md_dtype_size(merged.leaves[l].dtype);
-  jit::spec_modes(&M, D, rows);
-  M.nt = bytes > ((int64_t)320 << 20);
-  jit::eval_shape(&M);
-  hipFunction_t fn = jit::get(M);
-  if (!fn) return MDHIP_OK;
-  jit::JArgs A;
-  memset(&A, 0, sizeof A);
-  for (int l = 0; l < merged.n_leaves; ++l) { A.leaf[l].p = D.leaf[l].p; A.leaf[l].os = D.leaf[l].os; A.leaf[l].is = D.leaf[l].is; }
-  for (int i = 0; i < M.n_imm; ++i) A.imm[i] = merged.imm[i];
-  for (int k = 0; k < n; ++k) A.outs[k] = outs[k].data;
-  const int grid = jit::stream_grid(&A, rows, inner, jit::eval_blocks(M));
-  *done = true;
-  return jit::launch(fn, A, dim3((unsigned)grid));
+// what every plan starts from: nothing to launch, the program's own immediates
+static void plan_begin(VmLaunch *L, const mdhip_vm_program *pr) {
+  L->form = VM_NONE;
+  L->fn = nullptr;
+  L->imm = pr->imm;
+  L->n_imm = pr->n_instr;
+  L->n = 1;
+  L->batch = false;
+  L->outer = L->splits = 1;
+  L->rows = L->inner = L->n_out = L->n_red = L->chunk = L->NS = L->NB = L->grid = 0;
+  L->partial_bytes = 0;
 }
 
-static int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+// Plan an evaluation into outs[0 .. n). n == 1 is mdhip_vm_eval: the fast, the axes or the generic form, each (but the generic one)
+// generated from jit_min elements on and interpreted below. The output's dtype says what is stored — the compute type, b8 (truth
+// values) or f16 (the chain's value rounded ONCE to binary16 in the same pass: astype(chain, float16)).
+// n > 1 is mdhip_vm_eval_multi: the programs share ONE generated launch on the fast or the axes geometry (`merged`, the caller's,
+// holds their common leaf table and immediates and lives as long as the plan), or the plan stays VM_NONE — declined, never an
+// error: the caller evaluates them one by one.
+static int plan_eval(const mdhip_vm_program *progs, const mdhip_array *outs, int n, mdhip_vm_program *merged, VmLaunch *L) {
+  const bool multi = n > 1;
+  const mdhip_vm_program *pr = progs;   // whose leaves give the geometry: the one program, or the merged table
+  plan_begin(L, pr);
+  jit::Spec S;
+  if (multi) {
+    if (!jit::enabled() || !merge_programs(progs, n, &S, merged)) return MDHIP_OK;
+    for (int k = 0; k < n; ++k) {  // outputs: the compute dtype, contiguous, one shape
+      if (outs[k].dtype != merged->compute_dtype || outs[k].ndim != outs[0].ndim) return MDHIP_OK;
+      for (int d = 0; d < outs[0].ndim; ++d)
+        if (outs[k].shape[d] != outs[0].shape[d] || outs[k].strides[d] != outs[0].strides[d]) return MDHIP_OK;
+      if (!aligned16(outs[k].data)) return MDHIP_OK;
+    }
+    pr = merged;
+    L->imm = merged->imm;   // (the merged program has n_instr == 1, but S.n_imm immediates)
+    L->n_imm = S.n_imm;
+    L->n = n;
+  }
+  const int rc = md_vm_build_iter(&L->it, pr, &outs[0], &outs[0]);
+  if (rc != MDHIP_OK) return multi ? MDHIP_OK : rc;
+  const int64_t total = L->it.total;
+  if (multi ? total < jit::min_elems() : total == 0) return MDHIP_OK;
+  to_dev(pr, &L->D);
+  const int out_dtype = outs[0].dtype;
+  const int64_t out_bytes = (int64_t)n * (int64_t)md_dtype_size(out_dtype);   // per element, all outputs together
+  // the common part of the Spec; false: the interpreter runs. (Several programs: merge_programs began it, and only a generated kernel will do.)
+  auto want_generated = [&](int64_t rows) {
+    if (multi) jit::spec_modes(&S, L->D, rows);
+    else if (!jit::spec_for(&S, jit::EVAL, pr, L->D, rows, total)) return false;
+    S.out_bool = out_dtype == MDHIP_BOOL;
+    S.out_f16 = out_dtype == MDHIP_F16;
+    return true;
+  };
+  if (fast_geometry(L->it, pr->n_leaves, pr, true, &L->D, &L->rows, &L->inner) && (multi || al_for(outs[0].data, out_dtype))) {
+    if (want_generated(L->rows)) {
+      // the streamed bytes of this launch: outputs + vector leaves
+      S.nt = total * out_bytes + jit::streamed_bytes(L->D, total, false) > jit::NT_BYTES;
+      jit::eval_shape(&S);
+      L->fn = jit::get(S);
+      if (L->fn) L->grid = jit::stream_grid(L->rows, L->inner, jit::eval_blocks(S));
+    }
+    if (!L->fn) L->grid = interp_grid(L->rows, L->inner);
+    if (L->fn || !multi) L->form = VM_EVAL_FAST;
+    return MDHIP_OK;
+  }
+  // three / four collapsed axes: the axes form of the same kernels, still one launch
+  if (axes_geometry(L->it, pr, &outs[0], &L->D, &L->G)) {
+    if (want_generated(L->G.rows)) {
+      jit::spec_axes(&S, L->D, L->G, out_bytes);
+      L->fn = jit::get(S);
+      if (L->fn) L->grid = jit::axes_grid(S, L->G);
+    }
+    if (!L->fn) L->grid = md_grid_for(total >> 2);
+    if (L->fn || !multi) L->form = VM_EVAL_AXES;
+    return MDHIP_OK;
+  }
+  if (multi) return MDHIP_OK;
+  L->grid = md_grid_for(total);
+  L->form = VM_EVAL_GENERIC;
+  return MDHIP_OK;
+}
 
 // Trailing-axis reductions (mdhip_vm_reduce's third form): rows up to 64 lanes x 8 groups x 4 elements go a wave per row in the
 // generated kernels, longer ones a block per row; long rows need at least a row per CU (no cross-block split yet)
@@ -719,24 +743,15 @@ static bool sweep_geometry(int64_t n_out, int64_t n_red, int ru, int64_t *NS, in
   return true;
 }
 
-// reduce over axis 0 of a 2-D program with the generated sweep kernel; `eval_out` != nullptr: the evaluated value
-// is written as well (one pass for an elementwise product and its reduce-to-shape). false: not applicable.
-// `B` != nullptr: `outer` problems of that shape in one launch, leaf l of batch z read from B->bs[l] * z on, row z of `out` written.
-template <class R, class T>
-static bool sweep_cols(const mdhip_vm_program *pr, int rop, const MdVmDev &D, int64_t rows, int64_t inner, void *eval_out,
-                       const mdhip_array *out, int *status, int64_t outer = 1, const VmBatch *B = nullptr) {
-  if (!jit::enabled() || outer * rows * inner < jit::min_elems()) return false;
+// Plan the reduction over axis 0 of the (n_red, n_out) program in L->D with the generated sweep kernel; `store`: the evaluated value
+// is written as well (one pass for an elementwise product and its reduce-to-shape). false: not applicable, L is no further.
+// `batch`: `outer` problems of that shape in one launch, leaf l of batch z read from L->B.bs[l] * z on, row z of the output written.
+static bool sweep_cols(const mdhip_vm_program *pr, int rop, VmLaunch *L, int64_t n_red, int64_t n_out, bool store, int64_t outer = 1,
+                       bool batch = false) {
+  const int64_t elems = outer * n_red * n_out, tsize = (int64_t)md_dtype_size(pr->compute_dtype);
   jit::Spec S;
-  S.kind = jit::SWEEP;
-  S.batch = B != nullptr;
-  jit::spec_single(&S, pr);
-  jit::spec_modes(&S, D, rows);
-  S.rop = rop;
-  S.store = eval_out != nullptr;
-  int64_t bytes = eval_out ? rows * inner * (int64_t)sizeof(T) : 0;
-  for (int l = 0; l < pr->n_leaves; ++l)
-    if (S.leaf_mode[l] == jit::LM_VEC) bytes += rows * inner * (int64_t)md_dtype_size(pr->leaves[l].dtype);
-  bytes *= outer;
+  if (!jit::spec_for(&S, jit::SWEEP, pr, L->D, n_red, elems, rop, batch)) return false;
+  S.store = store;
   // rows per trip: ~128 B of loads in flight per lane (a bool leaf brings 4 B per row, a float leaf 16)
   int64_t row_bytes = 0;
   for (int l = 0; l < pr->n_leaves; ++l)
@@ -745,89 +760,40 @@ static bool sweep_cols(const mdhip_vm_program *pr, int rop, const MdVmDev &D, in
   S.RU = ru_env > 0 ? ru_env : (row_bytes > 0 ? (int)((128 + row_bytes - 1) / row_bytes) : 1);
   if (S.RU > 8) S.RU = 8;
   if (S.RU < 1) S.RU = 1;
-  int64_t NS, NB;
-  if (!sweep_geometry(inner, rows, S.RU, &NS, &NB, outer)) return false;
-  S.nt = bytes > ((int64_t)320 << 20);
+  if (!sweep_geometry(n_out, n_red, S.RU, &L->NS, &L->NB, outer)) return false;
+  // streamed: the stored value and the leaves that advance from row to row (n_red >= 512 here: exactly the LM_VEC ones)
+  S.nt = (store ? elems * tsize : 0) + jit::streamed_bytes(L->D, elems, true) > jit::NT_BYTES;
   // the evaluated value of a one-pass eval + column reduce is a large write next to (often much smaller) reads, and its
   // reader is whatever needed it in memory (cfg4: the weight-gradient GEMM, which is not bandwidth-bound): written around
   // the caches the pass ran 32.9 -> 26.3 us on the cfg4 shape (128 MiB out, 32 MiB mask in), the GEMM behind it unchanged (option sweep_nt_store = 0 disables)
   const int nt_store = (int)md_opt(MD_OPT_SWEEP_NT_STORE);
-  S.nt_store = nt_store && eval_out != nullptr && rows * inner * (int64_t)sizeof(T) >= ((int64_t)64 << 20);
-  hipFunction_t fn = jit::get(S);
-  if (!fn) return false;
-  void *partial = nullptr;
-  if (NB > 1) {
-    *status = mdhip_alloc((size_t)(outer * NB * inner) * sizeof(T), &partial);
-    if (*status != MDHIP_OK) return true;
-  }
-  jit::JArgs A;
-  jit::fill_args(&A, pr, D);
-  A.rows = rows; A.inner = inner; A.n_out = inner; A.n_red = rows; A.chunk = NB;
-  A.out = out->data;
-  A.outs[0] = eval_out;
-  A.partial = partial;
-  A.tickets = md_tickets();
-  if (B)
-    for (int l = 0; l < pr->n_leaves; ++l) A.bo[l] = B->bs[l];
-  *status = jit::launch(fn, A, dim3((unsigned)(NS * NB), (unsigned)outer));
-  if (partial) mdhip_free(partial);  // stream-ordered
+  S.nt_store = nt_store && store && n_red * n_out * tsize >= ((int64_t)64 << 20);
+  L->fn = jit::get(S);
+  if (!L->fn) return false;
+  L->form = VM_COLS_STRIPS;
+  L->n_red = n_red; L->n_out = n_out; L->outer = outer; L->batch = batch;
+  L->grid = L->NS * L->NB;
+  L->partial_bytes = L->NB > 1 ? (size_t)(outer * L->NB * n_out) * (size_t)tsize : 0;
   return true;
 }
 
-// (rows, inner) program reduced over its rows: the generated strips kernel, else the tiled kernels (generated or interpreted)
+// (n_red, n_out) program reduced over its rows: the generated strips kernel, else the tiled kernels (generated or interpreted)
 // with the rows split over gridDim.y and a second pass over the partial rows
-template <class R, class T>
-static int reduce_cols_2d(const mdhip_vm_program *pr, int rop, MdVmDev &D, int64_t rows, int64_t inner, const mdhip_array *out) {
-  hipStream_t st = md_stream();
-  int status = MDHIP_OK;
-  if (sweep_cols<R, T>(pr, rop, D, rows, inner, nullptr, out, &status)) return status;
-  const int64_t n_out = inner, n_red = rows;
-  const int64_t bx = ceil_div(n_out, 256);
+static void reduce_cols_2d(const mdhip_vm_program *pr, int rop, VmLaunch *L, int64_t n_red, int64_t n_out) {
+  if (sweep_cols(pr, rop, L, n_red, n_out, false)) return;
+  const int64_t bx = md_ceil_div(n_out, 256);
   int64_t splits = 1024 / bx;
   if (splits > n_red / 32) splits = n_red / 32;
   if (splits > 65535) splits = 65535;
   if (splits < 1) splits = 1;
-  const int64_t chunk = ceil_div(ceil_div(n_red, splits), 16) * 16;
-  splits = ceil_div(n_red, chunk);
-  hipFunction_t fn = nullptr;
-  if (jit::enabled() && rows * inner >= jit::min_elems()) {
-    jit::Spec S;
-    S.kind = jit::RED_COLS;
-    jit::spec_single(&S, pr);
-    jit::spec_modes(&S, D, rows);
-    S.rop = rop;
-    fn = jit::get(S);
-  }
-  jit::JArgs A;
-  if (fn) {
-    jit::fill_args(&A, pr, D);
-    A.rows = rows; A.inner = inner; A.n_out = n_out; A.n_red = n_red; A.chunk = chunk;
-  }
-  if (splits == 1) {
-    if (fn) { A.out = out->data; return jit::launch(fn, A, dim3((unsigned)bx, 1)); }
-    k_vm_reduce_cols<R, T, true><<<dim3((unsigned)bx, 1), MD_BLOCK, 0, st>>>(D, n_out, n_red, chunk, (T *)out->data, VmBatch{});
-    return MD_LAUNCH_CHECK("vm_reduce(cols)");
-  }
-  void *partial = nullptr;
-  MD_TRY(mdhip_alloc((size_t)(splits * n_out) * sizeof(T), &partial));
-  if (fn) {
-    A.out = partial;
-    int rc = jit::launch(fn, A, dim3((unsigned)bx, (unsigned)splits));
-    if (rc != MDHIP_OK) { mdhip_free(partial); return rc; }
-  } else {
-    k_vm_reduce_cols<R, T, false><<<dim3((unsigned)bx, (unsigned)splits), MD_BLOCK, 0, st>>>(D, n_out, n_red, chunk, (T *)partial, VmBatch{});
-  }
-  // second pass: a one-instruction program over the partial buffer
-  MdVmDev F;
-  memset(&F, 0, sizeof F);
-  F.n_instr = 1; F.n_leaves = 1;
-  F.code[0].ctrl = MDHIP_VM_CTRL(MDHIP_VM_PUSH, 0, 0, 0, MDHIP_VM_SRC_LEAF, 0);
-  F.leaf[0].p = partial; F.leaf[0].os = n_out; F.leaf[0].is = 1; F.leaf[0].dtype = md_dtype_of<T>::value;
-  const int64_t chunk2 = ceil_div(splits, 16) * 16;
-  k_vm_reduce_cols<R, T, true><<<dim3((unsigned)bx, 1), MD_BLOCK, 0, st>>>(F, n_out, splits, chunk2, (T *)out->data, VmBatch{});
-  int rc = MD_LAUNCH_CHECK("vm_reduce(cols,split)");
-  mdhip_free(partial);
-  return rc;
+  L->form = VM_COLS_TILED;
+  L->n_red = n_red; L->n_out = n_out;
+  L->grid = bx;
+  L->chunk = md_ceil_div(md_ceil_div(n_red, splits), 16) * 16;
+  L->splits = md_ceil_div(n_red, L->chunk);
+  jit::Spec S;
+  if (jit::spec_for(&S, jit::RED_COLS, pr, L->D, n_red, n_red * n_out, rop)) L->fn = jit::get(S);
+  L->partial_bytes = L->splits > 1 ? (size_t)(L->splits * n_out) * md_dtype_size(pr->compute_dtype) : 0;
 }
 
 // The fourth form of mdhip_vm_reduce — ONE run of adjacent reduced axes with kept axes behind it: the program seen as
@@ -869,48 +835,19 @@ static bool group_stride(const mdhip_array &a, int d0, int d1, int64_t *stride) 
   return true;
 }
 
-// The batched column kernels, by size: generated strips (n_red >= 512), generated tiled, interpreter — always ONE launch, unsplit
-// over n_red except for the strips' row bands. D holds the 2-D geometry of one batch (os = the stride over n_red), B the batch strides.
-template <class R, class T>
-static int reduce_axis_batched(const mdhip_vm_program *pr, int rop, MdVmDev &D, const VmBatch &B, int64_t outer, int64_t n_red, int64_t inner,
-                               const mdhip_array *out) {
-  int status = MDHIP_OK;
-  if (sweep_cols<R, T>(pr, rop, D, n_red, inner, nullptr, out, &status, outer, &B)) return status;
-  const int64_t bx = ceil_div(inner, 256);
-  if (jit::enabled() && outer * n_red * inner >= jit::min_elems()) {
-    jit::Spec S;
-    S.kind = jit::RED_COLS;
-    S.batch = true;
-    jit::spec_single(&S, pr);
-    jit::spec_modes(&S, D, n_red);
-    S.rop = rop;
-    if (hipFunction_t fn = jit::get(S)) {
-      jit::JArgs A;
-      jit::fill_args(&A, pr, D);
-      A.rows = n_red; A.inner = inner; A.n_out = inner; A.n_red = n_red; A.chunk = n_red;
-      A.out = out->data;
-      for (int l = 0; l < pr->n_leaves; ++l) A.bo[l] = B.bs[l];
-      return jit::launch(fn, A, dim3((unsigned)bx, (unsigned)outer));
-    }
-  }
-  k_vm_reduce_cols<R, T, true, true><<<dim3((unsigned)bx, 1, (unsigned)outer), MD_BLOCK, 0, md_stream()>>>(D, inner, n_red, n_red, (T *)out->data, B);
-  return MD_LAUNCH_CHECK("vm_reduce(cols,batched)");
-}
-
-template <class R, class T>
-static int reduce_axis(const mdhip_vm_program *pr, int rop, const mdhip_array *shape_like, const mdhip_array *out, const VmAxisForm &F) {
+// plan the (outer, n_red, inner) form F: the 2-D column problem, or the batched column kernels
+static int reduce_axis(const mdhip_vm_program *pr, int rop, const mdhip_array *shape_like, const mdhip_array *out, const VmAxisForm &F, VmLaunch *L) {
   if (F.outer * F.n_red * F.inner == 0) return md_fail(MDHIP_EVALUE, "vm_reduce: empty operand");
   if (F.inner & 3) return md_fail(MDHIP_EVALUE, "vm_reduce: %lld kept elements behind the reduced axes are not whole 16-byte groups", (long long)F.inner);
   if (F.outer > 65535) return md_fail(MDHIP_EVALUE, "vm_reduce: %lld batches in front of the reduced axes exceed the grid (65535)", (long long)F.outer);
   if (F.inner >= (1ll << 31) || F.n_red >= (1ll << 31)) return md_fail(MDHIP_EVALUE, "vm_reduce: extents of 2^31 and more are not fused over a middle axis");
-  if (((uintptr_t)out->data & 15) != 0) return md_fail(MDHIP_EVALUE, "vm_reduce: unaligned output");
-  int64_t out_elems = 1;
-  for (int d = 0; d < out->ndim; ++d) out_elems *= out->shape[d];
+  if (!aligned16(out->data)) return md_fail(MDHIP_EVALUE, "vm_reduce: unaligned output");
+  const int64_t out_elems = elems_of(out);
   if (out_elems != F.outer * F.inner)
     return md_fail(MDHIP_EVALUE, "vm_reduce: out holds %lld elements for %lld x %lld kept ones", (long long)out_elems, (long long)F.outer, (long long)F.inner);
-  MdVmDev D;
+  MdVmDev &D = L->D;
   to_dev(pr, &D);
-  VmBatch B;
+  VmBatch &B = L->B;
   memset(&B, 0, sizeof B);
   // per leaf (s_o, s_r, s_i) from its OWN descriptor (broadcast to the program's shape already): the jointly collapsed iteration
   // merges axes across the reduced / kept boundaries when every leaf is dense
@@ -931,65 +868,54 @@ static int reduce_axis(const mdhip_vm_program *pr, int rop, const mdhip_array *s
     B.bs[l] = so;
   }
   // leading axes reduced: the 2-D column problem (n_red, inner) itself
-  if (F.outer == 1) return reduce_cols_2d<R, T>(pr, rop, D, F.n_red, F.inner, out);
-  return reduce_axis_batched<R, T>(pr, rop, D, B, F.outer, F.n_red, F.inner, out);
+  if (F.outer == 1) {
+    reduce_cols_2d(pr, rop, L, F.n_red, F.inner);
+    return MDHIP_OK;
+  }
+  // The batched column kernels, by size: generated strips (n_red >= 512), generated tiled, interpreter — always ONE launch, unsplit
+  // over n_red except for the strips' row bands. D holds the 2-D geometry of one batch (os = the stride over n_red), B the batch strides.
+  if (sweep_cols(pr, rop, L, F.n_red, F.inner, false, F.outer, true)) return MDHIP_OK;
+  L->form = VM_COLS_BATCHED;
+  L->n_red = F.n_red; L->n_out = F.inner; L->outer = F.outer;
+  L->chunk = F.n_red;
+  L->grid = md_ceil_div(F.inner, 256);
+  jit::Spec S;
+  if (jit::spec_for(&S, jit::RED_COLS, pr, D, F.n_red, F.outer * F.n_red * F.inner, rop, true)) L->fn = jit::get(S);
+  return MDHIP_OK;
 }
 
-template <class R, class T>
-static int reduce_typed(const mdhip_vm_program *pr, int rop, const mdhip_array *shape_like, const mdhip_array *out, uint32_t mask) {
+// Plan mdhip_vm_reduce: the program's value over `shape_like`, reduced with `rop` over the axes of `mask`
+static int plan_reduce(const mdhip_vm_program *pr, int rop, const mdhip_array *shape_like, const mdhip_array *out, uint32_t mask, VmLaunch *L) {
+  plan_begin(L, pr);
   const int nd = shape_like->ndim;
   const uint32_t all = nd ? ((1u << nd) - 1u) : 0u;
   VmAxisForm F;
-  if (!(nd == 2 && mask == 1u) && axis_form(shape_like, mask, &F)) return reduce_axis<R, T>(pr, rop, shape_like, out, F);
-  MdVmIter it;
+  if (!(nd == 2 && mask == 1u) && axis_form(shape_like, mask, &F)) return reduce_axis(pr, rop, shape_like, out, F, L);
+  MdVmIter &it = L->it;
   MD_TRY(md_vm_build_iter(&it, pr, shape_like, nullptr));
   if (it.total == 0) return md_fail(MDHIP_EVALUE, "vm_reduce: empty operand");
-  MdVmDev D;
+  MdVmDev &D = L->D;
   to_dev(pr, &D);
-  hipStream_t st = md_stream();
-  int64_t rows, inner;
+  int64_t &rows = L->rows, &inner = L->inner;
   if (!fast_geometry(it, pr->n_leaves, pr, false, &D, &rows, &inner)) return md_fail(MDHIP_EVALUE, "vm_reduce: geometry not supported");
-  if (((uintptr_t)out->data & 15) != 0) return md_fail(MDHIP_EVALUE, "vm_reduce: unaligned output");
+  if (!aligned16(out->data)) return md_fail(MDHIP_EVALUE, "vm_reduce: unaligned output");
   if (mask == all) {
-    int64_t rbytes = 0;
-    for (int l = 0; l < pr->n_leaves; ++l)
-      if (D.leaf[l].is) rbytes += it.total * (int64_t)md_dtype_size(pr->leaves[l].dtype);
-    hipFunction_t fn = nullptr;
-    if (jit::enabled() && it.total >= jit::min_elems()) {
-      jit::Spec S;
-      S.kind = jit::RED_ALL;
-      jit::spec_single(&S, pr);
-      jit::spec_modes(&S, D, rows);
-      S.rop = rop;
-      S.nt = rbytes > ((int64_t)320 << 20);
-      fn = jit::get(S);
+    jit::Spec S;
+    if (jit::spec_for(&S, jit::RED_ALL, pr, D, rows, it.total, rop)) {
+      S.nt = jit::streamed_bytes(D, it.total, false) > jit::NT_BYTES;
+      L->fn = jit::get(S);
     }
-    jit::JArgs A;
-    int grid;
-    if (fn) {
-      jit::fill_args(&A, pr, D);
-      grid = jit::stream_grid(&A, rows, inner, 4);   // read-only streams: 4 blocks per CU (cfg3 loss pass 137-143 -> 126 us)
-    } else {
-      grid = md_grid_for((rows * (inner >> 2) + VG - 1) / VG + (rows == 1 ? 4 : 0));
-    }
-    void *partial = nullptr;
-    MD_TRY(mdhip_alloc((size_t)grid * sizeof(T), &partial));
-    int rc;
-    if (fn) {
-      A.out = out->data;
-      A.partial = partial;
-      A.tickets = md_tickets();
-      rc = jit::launch(fn, A, dim3((unsigned)grid));
-    } else {
-      k_vm_reduce_all<R, T><<<grid, MD_BLOCK, 0, st>>>(D, rows, inner, (T *)partial, md_tickets(), (T *)out->data);
-      rc = MD_LAUNCH_CHECK("vm_reduce(all)");
-    }
-    mdhip_free(partial);
-    return rc;
+    // read-only streams: 4 blocks per CU (cfg3 loss pass 137-143 -> 126 us)
+    L->grid = L->fn ? jit::stream_grid(rows, inner, 4) : interp_grid(rows, inner);
+    L->form = VM_RED_ALL;
+    L->partial_bytes = (size_t)L->grid * md_dtype_size(pr->compute_dtype);
+    return MDHIP_OK;
   }
   // reduce over axis 0 of a 2-D program that did NOT collapse to 1-D
-  if (nd == 2 && mask == 1u && uncollapse_2d(it, pr->n_leaves, &D, shape_like->shape[0], shape_like->shape[1], &rows, &inner))
-    return reduce_cols_2d<R, T>(pr, rop, D, rows, inner, out);
+  if (nd == 2 && mask == 1u && uncollapse_2d(it, pr->n_leaves, &D, shape_like->shape[0], shape_like->shape[1], &rows, &inner)) {
+    reduce_cols_2d(pr, rop, L, rows, inner);
+    return MDHIP_OK;
+  }
   // reduce over the TRAILING axes: every axis behind the first reduced one is reduced or has extent 1, some kept axis is longer
   // than 1. The iteration is (n_out, n_red) as it stands, or one axis (all leaves dense or fully broadcast) taken apart again.
   int first = 0;
@@ -1004,57 +930,175 @@ static int reduce_typed(const mdhip_vm_program *pr, int rop, const mdhip_array *
     const int64_t n_out = it.total / n_red;
     if (!uncollapse_2d(it, pr->n_leaves, &D, n_out, n_red, &rows, &inner))
       return md_fail(MDHIP_EVALUE, "vm_reduce: a trailing-axis reduction needs (rows, reduced) geometry with rows of whole 16-byte groups");
-    int64_t out_elems = 1;
-    for (int d = 0; d < out->ndim; ++d) out_elems *= out->shape[d];
+    const int64_t out_elems = elems_of(out);
     if (out_elems != n_out) return md_fail(MDHIP_EVALUE, "vm_reduce: out holds %lld elements for %lld rows", (long long)out_elems, (long long)n_out);
     if (n_out >= (1ll << 31)) return md_fail(MDHIP_EVALUE, "vm_reduce: %lld rows exceed the grid of the row kernels", (long long)n_out);
     // long rows are walked by ONE block (generated) or wave (interpreter) each: fewer rows than CUs would leave the chip idle
     // where the eager route splits rows over blocks
     if (n_red > VM_ROWS_WAVE_MAX && n_out < VM_ROWS_MIN_OUT)
       return md_fail(MDHIP_EVALUE, "vm_reduce: %lld rows of %lld elements are too few to fill the device without splitting rows", (long long)n_out, (long long)n_red);
-    if (jit::enabled() && it.total >= jit::min_elems()) {
-      int64_t rbytes = 0;
-      for (int l = 0; l < pr->n_leaves; ++l)
-        if (D.leaf[l].is && D.leaf[l].os) rbytes += it.total * (int64_t)md_dtype_size(pr->leaves[l].dtype);
-      jit::Spec S;
-      S.kind = jit::RED_ROWS;
-      jit::spec_single(&S, pr);
-      jit::spec_modes(&S, D, rows);
-      S.rop = rop;
-      S.nt = rbytes > ((int64_t)320 << 20);
+    L->form = VM_ROWS;
+    L->n_out = n_out; L->n_red = n_red;
+    L->chunk = 0;
+    L->grid = md_ceil_div(n_out, MD_BLOCK / 64);
+    jit::Spec S;
+    if (jit::spec_for(&S, jit::RED_ROWS, pr, D, rows, it.total, rop)) {
+      // streamed: the leaves that advance from row to row (a row-invariant vector is re-read from the caches)
+      S.nt = jit::streamed_bytes(D, it.total, true) > jit::NT_BYTES;
       const int64_t nvec = n_red >> 2;   // wave per row: 1 / 2 / 4 / 8 vector groups per lane; block per row (NV 0) above
       S.NV = n_red > VM_ROWS_WAVE_MAX ? 0 : nvec <= 64 ? 1 : nvec <= 128 ? 2 : nvec <= 256 ? 4 : 8;
-      if (hipFunction_t fn = jit::get(S)) {
-        jit::JArgs A;
-        jit::fill_args(&A, pr, D);
-        A.rows = rows; A.inner = inner; A.n_out = n_out; A.n_red = n_red;
-        A.out = out->data;
-        return jit::launch(fn, A, dim3((unsigned)(S.NV ? ceil_div(n_out, 4) : n_out)));
-      }
+      L->fn = jit::get(S);
+      if (L->fn) L->grid = S.NV ? md_ceil_div(n_out, 4) : n_out;
     }
-    k_vm_reduce_rows<R, T><<<(unsigned)ceil_div(n_out, MD_BLOCK / 64), MD_BLOCK, 0, st>>>(D, n_out, n_red, (T *)out->data);
-    return MD_LAUNCH_CHECK("vm_reduce(rows)");
+    return MDHIP_OK;
   }
   return md_fail(MDHIP_EVALUE, "vm_reduce: only full reductions and reductions over one run of adjacent axes are fused");
 }
 
-// out_eval[r][c] = program(r, c) and out_red[c] = reduce over r, ONE pass (generated sweep kernel only)
-template <class R, class T>
-static int eval_reduce_cols_typed(const mdhip_vm_program *pr, int rop, const mdhip_array *out_eval, const mdhip_array *out_red) {
-  MdVmIter it;
-  MD_TRY(md_vm_build_iter(&it, pr, out_eval, out_eval));
-  if (it.total == 0 || out_eval->ndim != 2) return md_fail(MDHIP_EVALUE, "vm_eval_reduce_cols: a non-empty 2-D program is required");
-  MdVmDev D;
-  to_dev(pr, &D);
-  int64_t rows, inner;
-  if (!fast_geometry(it, pr->n_leaves, pr, true, &D, &rows, &inner) ||
-      !uncollapse_2d(it, pr->n_leaves, &D, out_eval->shape[0], out_eval->shape[1], &rows, &inner))
+// Plan mdhip_vm_eval_reduce_cols: out_eval[r][c] = program(r, c) and out_red[c] = reduce over r, ONE pass (generated sweep kernel only)
+static int plan_eval_reduce_cols(const mdhip_vm_program *pr, int rop, const mdhip_array *out_eval, const mdhip_array *out_red, VmLaunch *L) {
+  plan_begin(L, pr);
+  MD_TRY(md_vm_build_iter(&L->it, pr, out_eval, out_eval));
+  if (L->it.total == 0 || out_eval->ndim != 2) return md_fail(MDHIP_EVALUE, "vm_eval_reduce_cols: a non-empty 2-D program is required");
+  to_dev(pr, &L->D);
+  if (!fast_geometry(L->it, pr->n_leaves, pr, true, &L->D, &L->rows, &L->inner) ||
+      !uncollapse_2d(L->it, pr->n_leaves, &L->D, out_eval->shape[0], out_eval->shape[1], &L->rows, &L->inner))
     return md_fail(MDHIP_EVALUE, "vm_eval_reduce_cols: geometry not supported");
-  if (((uintptr_t)out_eval->data & 15) || ((uintptr_t)out_red->data & 15)) return md_fail(MDHIP_EVALUE, "vm_eval_reduce_cols: unaligned output");
-  int status = MDHIP_OK;
-  if (sweep_cols<R, T>(pr, rop, D, rows, inner, out_eval->data, out_red, &status)) return status;
+  if (!aligned16(out_eval->data) || !aligned16(out_red->data)) return md_fail(MDHIP_EVALUE, "vm_eval_reduce_cols: unaligned output");
+  if (sweep_cols(pr, rop, L, L->rows, L->inner, true)) return MDHIP_OK;
   return md_fail(MDHIP_EVALUE, "vm_eval_reduce_cols: shape not covered by the one-pass kernel");
 }
+
+// ---- the runners ----
+// Launch the generated kernel of a plan: nothing here depends on the reduce functor or the compute type. `out`: where a reduction
+// writes (its result, or the partial rows of a split tiled pass); `outs`: what an evaluation writes (nullptr: nothing);
+// `partial`: the plan's scratch where the kernel itself folds it (RED_ALL, SWEEP).
+static int run_generated(const VmLaunch &L, void *out, void *const *outs, void *partial) {
+  if (L.form == VM_EVAL_AXES) {
+    jit::JAxArgs A;
+    jit::fill_args(&A, L.D, L.imm, L.n_imm);
+    for (int l = 0; l < L.D.n_leaves; ++l)
+      for (int j = 0; j < 3; ++j) A.st[l][j] = L.G.st[l][j];
+    for (int k = 0; k < L.n; ++k) A.outs[k] = outs[k];
+    A.rows = L.G.rows;
+    A.inner = L.G.nv << 2;
+    A.e1 = L.G.e1;
+    A.e2 = L.G.e2;
+    return jit::launch(L.fn, A, dim3((unsigned)L.grid));
+  }
+  jit::JArgs A;
+  jit::fill_args(&A, L.D, L.imm, L.n_imm);
+  A.out = out;
+  A.partial = partial;
+  dim3 grid((unsigned)L.grid);
+  switch (L.form) {
+    case VM_EVAL_FAST:
+      jit::args_stream(&A, L.rows, L.inner, (int)L.grid);
+      for (int k = 0; k < L.n; ++k) A.outs[k] = outs[k];
+      break;
+    case VM_RED_ALL:
+      jit::args_stream(&A, L.rows, L.inner, (int)L.grid);
+      A.tickets = md_tickets();
+      break;
+    case VM_COLS_STRIPS:
+      jit::args_shape(&A, L.n_red, L.n_out, L.n_out, L.n_red, L.NB);
+      if (outs) A.outs[0] = outs[0];
+      A.tickets = md_tickets();
+      if (L.batch) jit::args_batch(&A, L.B, L.D.n_leaves);
+      grid.y = (unsigned)L.outer;
+      break;
+    case VM_COLS_TILED:
+      jit::args_shape(&A, L.n_red, L.n_out, L.n_out, L.n_red, L.chunk);
+      grid.y = (unsigned)L.splits;
+      break;
+    case VM_COLS_BATCHED:
+      jit::args_shape(&A, L.n_red, L.n_out, L.n_out, L.n_red, L.chunk);
+      jit::args_batch(&A, L.B, L.D.n_leaves);
+      grid.y = (unsigned)L.outer;
+      break;
+    case VM_ROWS:
+      jit::args_shape(&A, L.rows, L.inner, L.n_out, L.n_red, L.chunk);
+      break;
+    default:
+      return vm_unplanned(L);
+  }
+  return jit::launch(L.fn, A, grid);
+}
+
+// the strips form: generated only, so with nothing of <R, T>. `eval_out` != nullptr: where the evaluated value goes.
+static int run_strips(const VmLaunch &L, void *out, void *eval_out) {
+  MdScratch scratch;
+  void *partial;
+  MD_TRY(scratch.get(L.partial_bytes, &partial));
+  void *outs[1] = {eval_out};
+  return run_generated(L, out, outs, partial);
+}
+
+template <class T, class To> static int run_eval(const VmLaunch &L, const mdhip_array *out) {
+  if (L.form == VM_NONE) return MDHIP_OK;
+  if (L.fn) { void *outs[1] = {out->data}; return run_generated(L, nullptr, outs, nullptr); }
+  hipStream_t st = md_stream();
+  To *o = (To *)out->data;
+  switch (L.form) {
+    case VM_EVAL_FAST:
+      k_vm_eval_fast<T, To><<<(unsigned)L.grid, MD_BLOCK, 0, st>>>(L.D, o, L.rows, L.inner);
+      return MD_LAUNCH_CHECK("vm_eval(fast)");
+    case VM_EVAL_AXES:
+      k_vm_eval_axes<T, To><<<(unsigned)L.grid, MD_BLOCK, 0, st>>>(L.D, L.G, o);
+      return MD_LAUNCH_CHECK("vm_eval(axes)");
+    case VM_EVAL_GENERIC:
+      k_vm_eval_generic<T, To><<<(unsigned)L.grid, MD_BLOCK, 0, st>>>(L.D, L.it, o);
+      return MD_LAUNCH_CHECK("vm_eval(generic)");
+    default:
+      return vm_unplanned(L);
+  }
+}
+
+template <class R, class T> static int run_reduce(const VmLaunch &L, const mdhip_array *out) {
+  if (L.form == VM_COLS_STRIPS) return run_strips(L, out->data, nullptr);
+  MdScratch scratch;
+  void *partial;
+  MD_TRY(scratch.get(L.partial_bytes, &partial));
+  hipStream_t st = md_stream();
+  T *o = (T *)out->data;
+  const unsigned bx = (unsigned)L.grid;
+  switch (L.form) {
+    case VM_RED_ALL:
+      if (L.fn) return run_generated(L, o, nullptr, partial);
+      k_vm_reduce_all<R, T><<<bx, MD_BLOCK, 0, st>>>(L.D, L.rows, L.inner, (T *)partial, md_tickets(), o);
+      return MD_LAUNCH_CHECK("vm_reduce(all)");
+    case VM_COLS_TILED: {
+      if (L.splits == 1) {
+        if (L.fn) return run_generated(L, o, nullptr, nullptr);
+        k_vm_reduce_cols<R, T, true><<<dim3(bx, 1), MD_BLOCK, 0, st>>>(L.D, L.n_out, L.n_red, L.chunk, o, VmBatch{});
+        return MD_LAUNCH_CHECK("vm_reduce(cols)");
+      }
+      if (L.fn) MD_TRY(run_generated(L, partial, nullptr, nullptr));
+      else k_vm_reduce_cols<R, T, false><<<dim3(bx, (unsigned)L.splits), MD_BLOCK, 0, st>>>(L.D, L.n_out, L.n_red, L.chunk, (T *)partial, VmBatch{});
+      // second pass: a one-instruction program over the partial buffer
+      MdVmDev F;
+      memset(&F, 0, sizeof F);
+      F.n_instr = 1; F.n_leaves = 1;
+      F.code[0].ctrl = MDHIP_VM_CTRL(MDHIP_VM_PUSH, 0, 0, 0, MDHIP_VM_SRC_LEAF, 0);
+      F.leaf[0].p = partial; F.leaf[0].os = L.n_out; F.leaf[0].is = 1; F.leaf[0].dtype = md_dtype_of<T>::value;
+      const int64_t chunk2 = md_ceil_div(L.splits, 16) * 16;
+      k_vm_reduce_cols<R, T, true><<<dim3(bx, 1), MD_BLOCK, 0, st>>>(F, L.n_out, L.splits, chunk2, o, VmBatch{});
+      return MD_LAUNCH_CHECK("vm_reduce(cols,split)");
+    }
+    case VM_COLS_BATCHED:
+      if (L.fn) return run_generated(L, o, nullptr, nullptr);
+      k_vm_reduce_cols<R, T, true, true><<<dim3(bx, 1, (unsigned)L.outer), MD_BLOCK, 0, st>>>(L.D, L.n_out, L.n_red, L.chunk, o, L.B);
+      return MD_LAUNCH_CHECK("vm_reduce(cols,batched)");
+    case VM_ROWS:
+      if (L.fn) return run_generated(L, o, nullptr, nullptr);
+      k_vm_reduce_rows<R, T><<<bx, MD_BLOCK, 0, st>>>(L.D, L.n_out, L.n_red, o);
+      return MD_LAUNCH_CHECK("vm_reduce(rows)");
+    default:
+      return vm_unplanned(L);
+  }
+}
+
+static bool rop_fused(int op) { return op == MDHIP_R_SUM || op == MDHIP_R_PROD || op == MDHIP_R_MAX || op == MDHIP_R_MIN; }
 
 // compile-only probes have no launch geometry: read modes from the leaf descriptors as given
 static void probe_modes(jit::Spec *S, const mdhip_vm_program *pr) {
@@ -1105,6 +1149,18 @@ static void probe_axes(jit::Spec *S, const mdhip_vm_program *pr, bool force) {
   S->wide = (total >> 2) >= (1ll << 31) || md_opt(MD_OPT_JIT_AXES_WIDE) == 1;
 }
 
+// the end of both probes: compile the kernel of S, hand the log back
+static int probe_compile(const jit::Spec &S, char *log, size_t log_cap) {
+  std::vector<char> code;
+  std::string l;
+  const std::string name = jit::make_name(S, jit::make_key(S));
+  const int rc = jit::compile(jit::gen_source(S, name), &code, &l);
+  if (rc == 0) l = name + "\n" + l;  // the log of a successful probe starts with the kernel's name: which form was generated
+  if (log && log_cap) { strncpy(log, l.c_str(), log_cap - 1); log[log_cap - 1] = 0; }
+  if (rc != 0) return md_fail(MDHIP_ERUNTIME, "fused-kernel compilation failed: %.300s", l.c_str());
+  return MDHIP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1113,10 +1169,13 @@ int mdhip_vm_eval(const mdhip_vm_program *pr, const mdhip_array *out) {
   MD_TRY(md_vm_check(pr));
   MD_TRY(md_check_any_array(out, "vm out"));
   const bool f32 = pr->compute_dtype == MDHIP_F32;
-  if (out->dtype == MDHIP_BOOL) return f32 ? eval_typed<float, b8>(pr, out) : eval_typed<double, b8>(pr, out);
-  if (out->dtype == MDHIP_F16) return f32 ? eval_typed<float, f16>(pr, out) : eval_typed<double, f16>(pr, out);
-  if (out->dtype != pr->compute_dtype) return md_fail(MDHIP_ETYPE, "vm_eval: out dtype must be the compute dtype, bool or float16");
-  return f32 ? eval_typed<float, float>(pr, out) : eval_typed<double, double>(pr, out);
+  if (out->dtype != MDHIP_BOOL && out->dtype != MDHIP_F16 && out->dtype != pr->compute_dtype)
+    return md_fail(MDHIP_ETYPE, "vm_eval: out dtype must be the compute dtype, bool or float16");
+  VmLaunch L;
+  MD_TRY(plan_eval(pr, out, 1, nullptr, &L));
+  if (out->dtype == MDHIP_BOOL) return f32 ? run_eval<float, b8>(L, out) : run_eval<double, b8>(L, out);
+  if (out->dtype == MDHIP_F16) return f32 ? run_eval<float, f16>(L, out) : run_eval<double, f16>(L, out);
+  return f32 ? run_eval<float, float>(L, out) : run_eval<double, double>(L, out);
 }
 
 int mdhip_vm_eval_multi(const mdhip_vm_program *progs, const mdhip_array *outs, int n) {
@@ -1126,9 +1185,16 @@ int mdhip_vm_eval_multi(const mdhip_vm_program *progs, const mdhip_array *outs, 
     if (outs[k].dtype == MDHIP_F16) return md_fail(MDHIP_EVALUE, "vm_eval_multi: float16 outputs are stored by mdhip_vm_eval only");
     MD_TRY(md_check_array(&outs[k], "vm out"));
   }
-  bool done = false;
-  MD_TRY(eval_multi(progs, outs, n, &done));
-  if (done) return MDHIP_OK;
+  if (n > 1) {
+    VmLaunch L;
+    mdhip_vm_program merged;
+    MD_TRY(plan_eval(progs, outs, n, &merged, &L));
+    if (L.form != VM_NONE) {   // one launch for all (generated only)
+      void *po[4] = {};
+      for (int k = 0; k < n; ++k) po[k] = outs[k].data;
+      return run_generated(L, nullptr, po, nullptr);
+    }
+  }
   for (int k = 0; k < n; ++k) MD_TRY(mdhip_vm_eval(&progs[k], &outs[k]));  // same results, one pass each
   return MDHIP_OK;
 }
@@ -1146,14 +1212,7 @@ int mdhip_vm_jit_probe_multi(const mdhip_vm_program *progs, int n, char *log, si
     for (int l = 0; l < progs[k].n_leaves; ++l) M.leaf_mode[M.leaf_map[k][l]] = one.leaf_mode[M.leaf_map[k][l]];
   }
   probe_axes(&M, &merged, false);
-  std::vector<char> code;
-  std::string l;
-  const std::string name = jit::make_name(M, jit::make_key(M));
-  const int rc = jit::compile(jit::gen_source(M, name), &code, &l);
-  if (rc == 0) l = name + "\n" + l;  // the log of a successful probe starts with the kernel's name: which form was generated
-  if (log && log_cap) { strncpy(log, l.c_str(), log_cap - 1); log[log_cap - 1] = 0; }
-  if (rc != 0) return md_fail(MDHIP_ERUNTIME, "fused-kernel compilation failed: %.300s", l.c_str());
-  return MDHIP_OK;
+  return probe_compile(M, log, log_cap);
 }
 
 int mdhip_vm_jit_probe(const mdhip_vm_program *pr, int kind, int reduce_op, int out_is_bool, char *log, size_t log_cap) {
@@ -1174,14 +1233,7 @@ int mdhip_vm_jit_probe(const mdhip_vm_program *pr, int kind, int reduce_op, int 
   S.store = kind == 4;
   S.Q = 4;
   S.RU = 2;
-  std::vector<char> code;
-  std::string l;
-  const std::string name = jit::make_name(S, jit::make_key(S));
-  const int rc = jit::compile(jit::gen_source(S, name), &code, &l);
-  if (rc == 0) l = name + "\n" + l;  // the log of a successful probe starts with the kernel's name: which form was generated
-  if (log && log_cap) { strncpy(log, l.c_str(), log_cap - 1); log[log_cap - 1] = 0; }
-  if (rc != 0) return md_fail(MDHIP_ERUNTIME, "fused-kernel compilation failed: %.300s", l.c_str());
-  return MDHIP_OK;
+  return probe_compile(S, log, log_cap);
 }
 
 int mdhip_vm_eval_reduce_cols(const mdhip_vm_program *pr, int op, const mdhip_array *out_eval, const mdhip_array *out_red) {
@@ -1192,17 +1244,10 @@ int mdhip_vm_eval_reduce_cols(const mdhip_vm_program *pr, int op, const mdhip_ar
   MD_TRY(md_check_array(out_red, "vm out"));
   if (out_eval->dtype != pr->compute_dtype || out_red->dtype != pr->compute_dtype)
     return md_fail(MDHIP_ETYPE, "vm_eval_reduce_cols: both outputs must have the compute dtype");
-#define MD_VMER(R)                                                                                        \
-  return pr->compute_dtype == MDHIP_F32 ? eval_reduce_cols_typed<R, float>(pr, op, out_eval, out_red)     \
-                                        : eval_reduce_cols_typed<R, double>(pr, op, out_eval, out_red)
-  switch (op) {
-    case MDHIP_R_SUM: MD_VMER(RSum);
-    case MDHIP_R_PROD: MD_VMER(RProd);
-    case MDHIP_R_MAX: MD_VMER(RMax);
-    case MDHIP_R_MIN: MD_VMER(RMin);
-  }
-#undef MD_VMER
-  return md_fail(MDHIP_EVALUE, "vm_eval_reduce_cols: reduce op %d is not fused", op);
+  if (!rop_fused(op)) return md_fail(MDHIP_EVALUE, "vm_eval_reduce_cols: reduce op %d is not fused", op);
+  VmLaunch L;
+  MD_TRY(plan_eval_reduce_cols(pr, op, out_eval, out_red, &L));
+  return run_strips(L, out_red->data, out_eval->data);
 }
 
 int mdhip_vm_jit_stats(int64_t stats[2]) {
@@ -1216,17 +1261,17 @@ int mdhip_vm_reduce(const mdhip_vm_program *pr, int op, const mdhip_array *shape
   MD_TRY(md_check_array(shape_like, "vm shape"));
   MD_TRY(md_check_array(out, "vm out"));
   if (out->dtype != pr->compute_dtype) return md_fail(MDHIP_ETYPE, "vm_reduce: out dtype must be the compute dtype");
-#define MD_VMR(R)                                                                                         \
-  return pr->compute_dtype == MDHIP_F32 ? reduce_typed<R, float>(pr, op, shape_like, out, mask)           \
-                                        : reduce_typed<R, double>(pr, op, shape_like, out, mask)
+  if (!rop_fused(op)) return md_fail(MDHIP_EVALUE, "vm_reduce: reduce op %d is not fused", op);
+  VmLaunch L;
+  MD_TRY(plan_reduce(pr, op, shape_like, out, mask, &L));
+#define MD_VMR(R) return pr->compute_dtype == MDHIP_F32 ? run_reduce<R, float>(L, out) : run_reduce<R, double>(L, out)
   switch (op) {
     case MDHIP_R_SUM: MD_VMR(RSum);
     case MDHIP_R_PROD: MD_VMR(RProd);
     case MDHIP_R_MAX: MD_VMR(RMax);
-    case MDHIP_R_MIN: MD_VMR(RMin);
+    default: MD_VMR(RMin);
   }
 #undef MD_VMR
-  return md_fail(MDHIP_EVALUE, "vm_reduce: reduce op %d is not fused", op);
 }
 
 }  // extern "C"

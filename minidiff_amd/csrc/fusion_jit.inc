@@ -961,14 +961,54 @@ template <class Args> static int launch(hipFunction_t fn, Args &A, dim3 grid) {
   return md_hip_check(hipModuleLaunchKernel(fn, grid.x, grid.y, 1, MD_BLOCK, 1, 1, 0, md_stream(), nullptr, cfg), "fused kernel launch");
 }
 
-static void fill_args(JArgs *A, const mdhip_vm_program *pr, const MdVmDev &D) {
+// ---- what the launch planners and runners of fusion.hip share -------------------------------------------------------------
+// The common part of a Spec for ONE program on the (rows, inner) geometry of D. false: no generated kernel is wanted (option
+// jit = 0, or fewer than jit_min elements in all) — the interpreter runs.
+static bool spec_for(Spec *S, int kind, const mdhip_vm_program *pr, const MdVmDev &D, int64_t rows, int64_t total, int rop = MDHIP_R_SUM,
+                     bool batch = false) {
+  if (!enabled() || total < min_elems()) return false;
+  S->kind = kind;
+  S->batch = batch;
+  spec_single(S, pr);
+  spec_modes(S, D, rows);
+  S->rop = rop;
+  return true;
+}
+
+// A launch that streams more than this many bytes loads (and an EVAL stores) non-temporally: Spec::nt, part of the kernel's key
+constexpr int64_t NT_BYTES = (int64_t)320 << 20;
+// What a launch streams through its leaves: `elems` elements of every leaf read with unit inner stride. `row_wise`: only of
+// those that also advance from row to row (os != 0) — the forms that walk rows (SWEEP, RED_ROWS) load a row-invariant vector
+// once (LM_ROWINV) or re-read it from the caches, the streaming forms (EVAL, RED_ALL) count every vector leaf. On more than one
+// row that is exactly SWEEP's LM_VEC, which its launcher used to test; the two predicates are NOT interchangeable: a leaf that
+// changes sides changes `nt`, and with it the kernel.
+static int64_t streamed_bytes(const MdVmDev &D, int64_t elems, bool row_wise) {
+  int64_t bytes = 0;
+  for (int l = 0; l < D.n_leaves; ++l)
+    if (D.leaf[l].is && (!row_wise || D.leaf[l].os)) bytes += elems * (int64_t)md_dtype_size(D.leaf[l].dtype);
+  return bytes;
+}
+
+// Kernel arguments: the D.n_leaves leaves as the planner left them in D and n_imm immediates (a single program: one per
+// instruction; merged programs: their shared array), everything else 0. Args: JArgs or JAxArgs. (The axes form does not read
+// leaf.os; axes_geometry leaves it 0 in D, so it is 0 here as well. In the same way spec_for's spec_modes is idle for the axes
+// form: spec_axes sets the mode of every leaf after it.)
+template <class Args> static void fill_args(Args *A, const MdVmDev &D, const double *imm, int n_imm) {
   memset(A, 0, sizeof *A);
-  for (int l = 0; l < pr->n_leaves; ++l) {
+  for (int l = 0; l < D.n_leaves; ++l) {
     A->leaf[l].p = D.leaf[l].p;
     A->leaf[l].os = D.leaf[l].os;
     A->leaf[l].is = D.leaf[l].is;
   }
-  for (int i = 0; i < pr->n_instr; ++i) A->imm[i] = pr->imm[i];
+  for (int i = 0; i < n_imm; ++i) A->imm[i] = imm[i];
+}
+// .. the shape group of the reductions over columns or rows
+static void args_shape(JArgs *A, int64_t rows, int64_t inner, int64_t n_out, int64_t n_red, int64_t chunk) {
+  A->rows = rows; A->inner = inner; A->n_out = n_out; A->n_red = n_red; A->chunk = chunk;
+}
+// .. and the batch strides of the batched column reductions
+static void args_batch(JArgs *A, const VmBatch &B, int n_leaves) {
+  for (int l = 0; l < n_leaves; ++l) A->bo[l] = B.bs[l];
 }
 // Shape of a generated EVAL kernel: vector groups per lane and trip, blocks per CU (options jit_u / jit_blocks force: experiments)
 static void eval_shape(Spec *S) {
@@ -985,17 +1025,19 @@ static int eval_blocks(const Spec &S) {
   for (int l = 0; l < S.n_leaves; ++l) streams += S.leaf_mode[l] == LM_VEC;
   return streams >= 4 ? 2 : streams == 3 ? 4 : 8;
 }
-// geometry of the streaming forms (EVAL / RED_ALL): grid size and the position advance per trip
-static int stream_grid(JArgs *A, int64_t rows, int64_t inner, int blocks_per_cu = 8) {
+// geometry of the streaming forms (EVAL / RED_ALL): grid size ..
+static int stream_grid(int64_t rows, int64_t inner, int blocks_per_cu = 8) {
   const int64_t nv = inner >> 2;
   const int cap = md_max_blocks();  // (MDHIP_MAX_BLOCKS overrides the per-form choice: experiments)
-  const int grid = md_grid_for(rows * nv + (rows == 1 ? 4 : 0), MD_BLOCK, cap != MD_NUM_CUS * 8 ? cap : MD_NUM_CUS * blocks_per_cu);
-  const int64_t gs = (int64_t)grid * MD_BLOCK;
+  return md_grid_for(rows * nv + (rows == 1 ? 4 : 0), MD_BLOCK, cap != MD_NUM_CUS * 8 ? cap : MD_NUM_CUS * blocks_per_cu);
+}
+// .. and, in the arguments, the position advance per trip of that grid
+static void args_stream(JArgs *A, int64_t rows, int64_t inner, int grid) {
+  const int64_t nv = inner >> 2, gs = (int64_t)grid * MD_BLOCK;
   A->rows = rows;
   A->inner = inner;
   A->dq = nv > 0 ? gs / nv : 0;
   A->dr = nv > 0 ? gs % nv : 0;
-  return grid;
 }
 
 static int axes_grid(const Spec &S, const VmAxes &G) {
@@ -1006,36 +1048,15 @@ static int axes_grid(const Spec &S, const VmAxes &G) {
 // (option jit_axes_wide = 1 forces the 64-bit form: tests), non-temporal by the streamed bytes. `out_elem_bytes`: all outputs together.
 static void spec_axes(Spec *S, const MdVmDev &D, const VmAxes &G, int64_t out_elem_bytes) {
   const int64_t total = G.rows * G.nv * 4;
-  int64_t bytes = total * out_elem_bytes;
   S->axes = G.e0 != 1 ? 4 : 3;
   for (int l = 0; l < S->n_leaves; ++l) {
-    if (D.leaf[l].is) {
-      S->leaf_mode[l] = LM_VEC;
-      bytes += total * (int64_t)md_dtype_size(S->leaf_dtype[l]);
-    } else {
-      S->leaf_mode[l] = (G.st[l][0] | G.st[l][1] | G.st[l][2]) == 0 ? LM_CONST : LM_ROWB;
-    }
+    if (D.leaf[l].is) S->leaf_mode[l] = LM_VEC;
+    else S->leaf_mode[l] = (G.st[l][0] | G.st[l][1] | G.st[l][2]) == 0 ? LM_CONST : LM_ROWB;
   }
-  S->nt = bytes > ((int64_t)320 << 20);
+  S->nt = total * out_elem_bytes + streamed_bytes(D, total, false) > NT_BYTES;
   eval_shape(S);
   // 32-bit index arithmetic while the largest value the trip loop forms, vector count + U grid strides, stays below 2^31
   S->wide = G.rows * G.nv + (int64_t)S->U * axes_grid(*S, G) * MD_BLOCK >= (1ll << 31) || md_opt(MD_OPT_JIT_AXES_WIDE) == 1;
-}
-static int launch_axes(hipFunction_t fn, const Spec &S, const MdVmDev &D, const VmAxes &G, const double *imm, void *const *outs) {
-  JAxArgs A;
-  memset(&A, 0, sizeof A);
-  for (int l = 0; l < S.n_leaves; ++l) {
-    A.leaf[l].p = D.leaf[l].p;
-    A.leaf[l].is = D.leaf[l].is;
-    for (int j = 0; j < 3; ++j) A.st[l][j] = G.st[l][j];
-  }
-  for (int i = 0; i < S.n_imm; ++i) A.imm[i] = imm[i];
-  for (int k = 0; k < S.n; ++k) A.outs[k] = outs[k];
-  A.rows = G.rows;
-  A.inner = G.nv << 2;
-  A.e1 = G.e1;
-  A.e2 = G.e2;
-  return launch(fn, A, dim3((unsigned)axes_grid(S, G)));
 }
 
 }  // namespace jit

@@ -11,6 +11,8 @@ extern "C" int mdhip_free(void *);
 
 enum MdRound { MD_FLOOR, MD_CEIL };
 
+static inline int64_t md_ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
 // The band count: `target` blocks in all over `per_band` strip-blocks per band (NS * outer), rounded as the caller says; then
 // <= 64 bands (the last block of a strip holds all its partial rows in registers), a band holds >= rows_per_band rows, >= 1.
 // A forced count (an option) goes in as target with per_band 1. What differs from caller to caller — the ticket fit, the

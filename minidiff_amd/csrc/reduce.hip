@@ -924,8 +924,6 @@ __global__ void __launch_bounds__(MD_BLOCK) k_anyall_flat(const T *__restrict__ 
 // launch form in a RedLaunch; they allocate nothing and launch nothing. run_reduce / run_arg are one switch over the form: allocate
 // what the description names, launch, check, free. The order of the tests in a planner is the route: the first form whose
 // predicate holds is taken, and where one form shadows another the comment at it says why.
-static int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
-
 constexpr int RED_RB = 8;   // rows per batch of k_reduce_cols_strips
 constexpr int ARG_RB = 4;   // .. of k_arg_cols_strips (rocprofv3 at one block per CU: 26.6 us with 4 rows per batch, 28.4 with 8)
 
@@ -999,7 +997,7 @@ static RedLaunch plan_reduce(const MdRedPlan &pl, const mdhip_array *x, const md
   // the whole of a contiguous array: truth values from 16-B vectors of the array's own type
   if (t.anyall && n_out == 1 && row_contig && n_red >= (1 << 16) && x_al &&
       (x->dtype == MDHIP_BOOL || x->dtype == MDHIP_I32 || x->dtype == MDHIP_I64 || x->dtype == MDHIP_F32 || x->dtype == MDHIP_F64)) {
-    L.blocks = ceil_div(n_red * (int64_t)md_dtype_size(x->dtype), 64 * 1024);   // >= 64 KiB per block
+    L.blocks = md_ceil_div(n_red * (int64_t)md_dtype_size(x->dtype), 64 * 1024);   // >= 64 KiB per block
     if (L.blocks > 4 * MD_NUM_CUS) L.blocks = 4 * MD_NUM_CUS;
     if (L.blocks < 1) L.blocks = 1;
     L.partial_bytes = L.blocks > 1 ? (size_t)L.blocks * sizeof(unsigned) : 0;
@@ -1015,7 +1013,7 @@ static RedLaunch plan_reduce(const MdRedPlan &pl, const mdhip_array *x, const md
     for (int k = 0; k < pl.nk; ++k) aligned = aligned && (pl.kx[k] % V) == 0;
     if (wave_on && row_contig && typed && aligned && n_red >= 32 && n_red <= 64 * V * 8 && n_out >= 1024 && n_out < (1ll << 32)) {
       const int64_t nvec = n_red / V;
-      L.blocks = ceil_div(n_out, 4);
+      L.blocks = md_ceil_div(n_out, 4);
       L.NV = nvec <= 64 ? 1 : nvec <= 128 ? 2 : nvec <= 256 ? 4 : 8;
       return red_pick(L, RED_ROWS_WAVE, "reduce(rows,wave)");
     }
@@ -1023,7 +1021,7 @@ static RedLaunch plan_reduce(const MdRedPlan &pl, const mdhip_array *x, const md
   // (rows of the accumulator's own 4- / 8-byte type from 256 elements on keep the block kernel's peeled 16-B loads)
   const bool typed_vec = asz >= 4 && typed;
   if (row_contig && n_red >= 16 && n_red <= 4096 && (!typed_vec || n_red < 256) && n_out >= 256 && md_opt(MD_OPT_ROWS_WAVE) != 0) {
-    L.blocks = ceil_div(n_out, MD_BLOCK / 64);
+    L.blocks = md_ceil_div(n_out, MD_BLOCK / 64);
     if (L.blocks > 8 * MD_NUM_CUS) L.blocks = 8 * MD_NUM_CUS;
     return red_pick(L, RED_ROWS_WAVE_ANY, "reduce(rows,wave,any type)");
   }
@@ -1041,7 +1039,7 @@ static RedLaunch plan_reduce(const MdRedPlan &pl, const mdhip_array *x, const md
       const bool strips_ok = stats ? pl.nk == 1 && pl.nr == 1 && pl.ko[0] == 1 && pl.kx[0] == 1 && (n_out % SV) == 0 && (pl.rx[0] % SV) == 0 && x_al && out_al : vec_ok;
       if (t.cheap && strips_ok && n_red >= 512) {
         const int nb_force = (int)md_opt(MD_OPT_COLS_NB);
-        const int64_t NS = ceil_div(n_out, 64 * SV);
+        const int64_t NS = md_ceil_div(n_out, 64 * SV);
         // one block per CU (two per CU ran 15 % slower, half a block per CU 20 %: profiles/r3_reduce_lab.txt); option cols_nb
         // forces the count (still clamped)
         const int64_t NB = nb_force > 0 ? md_strips_bands(1, nb_force, MD_FLOOR, n_red, 4 * RED_RB) : md_strips_bands(NS, MD_NUM_CUS, MD_FLOOR, n_red, 4 * RED_RB);
@@ -1057,7 +1055,7 @@ static RedLaunch plan_reduce(const MdRedPlan &pl, const mdhip_array *x, const md
       if (t.cheap && pl.nk == 2 && pl.nr == 1 && pl.kx[1] == 1 && pl.ko[1] == 1 && pl.ko[0] == pl.kshape[1] && (typed || stats) && (pl.kshape[1] % SV) == 0 &&
           (pl.rx[0] % SV) == 0 && (pl.kx[0] % SV) == 0 && x_al && out_al && pl.kshape[0] <= 65535 && pl.kshape[1] >= 256 && n_red >= 64) {
         const int64_t outer = pl.kshape[0], inner = pl.kshape[1];
-        const int64_t NS = ceil_div(inner, 64 * SV);
+        const int64_t NS = md_ceil_div(inner, 64 * SV);
         const int64_t NB = md_strips_bands(NS * outer, MD_NUM_CUS, MD_FLOOR, n_red, 4 * RED_RB);   // one block per CU over all the batches
         // tickets that do not fit: decline, as the plain form
         if (NB == 1 || NS * outer * MD_TICKET_PAD <= MD_TICKET_WORDS) {
@@ -1068,25 +1066,25 @@ static RedLaunch plan_reduce(const MdRedPlan &pl, const mdhip_array *x, const md
       }
       // (the tiled kernels from here on serve what the strips forms do not cover: narrow / ragged / short problems)
       if (vec_ok) {
-        L.blocks = ceil_div(n_out, 64 * V);
+        L.blocks = md_ceil_div(n_out, 64 * V);
         int64_t splits = 1024 / L.blocks;
         if (splits > n_red / 64) splits = n_red / 64;
         if (splits > 65535) splits = 65535;
         if (splits < 1) splits = 1;
-        L.chunk = ceil_div(ceil_div(n_red, splits), 16) * 16;
-        L.splits = ceil_div(n_red, L.chunk);
+        L.chunk = md_ceil_div(md_ceil_div(n_red, splits), 16) * 16;
+        L.splits = md_ceil_div(n_red, L.chunk);
         if (L.splits == 1) return red_pick(L, RED_COLS_VEC, "reduce(cols,vec)");
         L.partial_bytes = (size_t)(L.splits * n_out) * asz;
         return red_pick(L, RED_COLS_VEC_SPLIT, "reduce(cols,vec,split)");
       }
     }
-    L.blocks = ceil_div(n_out, MD_BLOCK);
+    L.blocks = md_ceil_div(n_out, MD_BLOCK);
     int64_t splits = 1024 / L.blocks;
     if (splits > n_red / 32) splits = n_red / 32;
     if (splits > 65535) splits = 65535;
     if (splits < 1) splits = 1;
-    L.chunk = ceil_div(n_red > 0 ? n_red : 1, splits);
-    L.splits = ceil_div(n_red > 0 ? n_red : 1, L.chunk);
+    L.chunk = md_ceil_div(n_red > 0 ? n_red : 1, splits);
+    L.splits = md_ceil_div(n_red > 0 ? n_red : 1, L.chunk);
     if (L.splits == 1) return red_pick(L, RED_COLS, "reduce(cols)");
     L.partial_bytes = (size_t)(L.splits * n_out) * asz;
     return red_pick(L, RED_COLS_SPLIT, "reduce(cols,split)");
@@ -1095,7 +1093,7 @@ static RedLaunch plan_reduce(const MdRedPlan &pl, const mdhip_array *x, const md
     // ~1024 blocks in total (4 per CU; option rows_blocks overrides: experiments); each block should still see >= 4096 items
     const int64_t total_blocks = md_opt(MD_OPT_ROWS_BLOCKS) > 0 ? md_opt(MD_OPT_ROWS_BLOCKS) : 1024;
     int64_t splits = total_blocks / n_out;
-    const int64_t max_splits = ceil_div(n_red, 4096);
+    const int64_t max_splits = md_ceil_div(n_red, 4096);
     if (splits > max_splits) splits = max_splits;
     if (splits < 1) splits = 1;
     L.splits = splits;
@@ -1196,7 +1194,7 @@ static int run_reduce(const RedLaunch &L, const MdRedPlan &pl, const mdhip_array
       if constexpr (!VEC) return red_unplanned(L);
       else {
         k_reduce_cols_vec<R, Tacc, Tacc, false><<<dim3((unsigned)L.blocks, (unsigned)L.splits), MD_BLOCK, 0, st>>>((const Tacc *)x->data, n_out, n_red, pl.rx[0], L.chunk, partial);
-        const int64_t chunk2 = ceil_div(L.splits, 16) * 16;
+        const int64_t chunk2 = md_ceil_div(L.splits, 16) * 16;
         k_reduce_cols_vec<R, Tacc, To, true><<<dim3((unsigned)L.blocks, 1), MD_BLOCK, 0, st>>>((const Tacc *)partial, n_out, L.splits, n_out, chunk2, o);
       }
       break;
@@ -1273,7 +1271,7 @@ static RedLaunch plan_arg(const MdRedPlan &pl, const mdhip_array *x, int64_t tsz
     const int64_t arg_blocks = md_opt(MD_OPT_ARG_BLOCKS) > 0 ? (int)md_opt(MD_OPT_ARG_BLOCKS) : MD_NUM_CUS;   // one block per CU, as the column sums (rocprofv3: 26.6 us against 38.0 with four per CU); the knob is for experiments
     // kept axis contiguous (argmax over the rows of a row-major matrix)
     if (pl.nk == 1 && pl.nr == 1 && pl.kx[0] == 1 && pl.ko[0] == 1 && n_out >= 256 && (n_out % V) == 0 && (pl.rx[0] % V) == 0 && x_al && n_red >= 16) {
-      const int64_t bxv = ceil_div(n_out, 64 * V);
+      const int64_t bxv = md_ceil_div(n_out, 64 * V);
       if (n_red < (1ll << 31) && n_red >= 64 && bxv * MD_TICKET_PAD <= MD_TICKET_WORDS) {
         L.NS = bxv; L.outer = 1;
         L.NB = md_strips_bands(L.NS, arg_blocks, MD_CEIL, n_red, 32);
@@ -1297,7 +1295,7 @@ static RedLaunch plan_arg(const MdRedPlan &pl, const mdhip_array *x, int64_t tsz
         (pl.kshape[1] % V) == 0 && (pl.rx[0] % V) == 0 && (pl.kx[0] % V) == 0 && x_al && pl.kshape[1] >= 256 && n_red >= 64 && n_red < (1ll << 31) &&
         pl.kshape[0] <= 65535) {
       const int64_t outer = pl.kshape[0], inner = pl.kshape[1];
-      L.NS = ceil_div(inner, 64 * V); L.outer = outer;
+      L.NS = md_ceil_div(inner, 64 * V); L.outer = outer;
       L.NB = md_strips_bands(L.NS * outer, arg_blocks, MD_CEIL, n_red, 32);   // one block per CU over all the batches
       if (L.NS * outer * MD_TICKET_PAD > MD_TICKET_WORDS) L.NB = 1;   // more strips than ticket words: one band (the column sums decline instead)
       while (L.NB > 1 && L.NB * inner * 8 >= (1ll << 31)) L.NB /= 2;   // (32-bit byte offsets into a batch's partial rows, of 8-byte elements at most)
@@ -1308,11 +1306,11 @@ static RedLaunch plan_arg(const MdRedPlan &pl, const mdhip_array *x, int64_t tsz
     if (pl.nr == 1 && pl.rx[0] == 1 && n_red >= 1024 && n_out < (1ll << 30)) {
       // ~2048 blocks in total, each with >= 8192 items of its row
       int64_t splits = 2048 / n_out;
-      const int64_t max_splits = ceil_div(n_red, 8192);
+      const int64_t max_splits = md_ceil_div(n_red, 8192);
       if (splits > max_splits) splits = max_splits;
       if (splits < 1) splits = 1;
-      L.chunk = ceil_div(ceil_div(n_red, splits), V) * V;
-      L.splits = ceil_div(n_red, L.chunk);
+      L.chunk = md_ceil_div(md_ceil_div(n_red, splits), V) * V;
+      L.splits = md_ceil_div(n_red, L.chunk);
       if (L.splits == 1) return red_pick(L, ARG_ROWS_VEC, "argreduce(rows,vec)");
       L.partial_bytes = (size_t)(L.splits * n_out) * tsz;
       L.index_bytes = (size_t)(L.splits * n_out) * sizeof(int64_t);
@@ -1320,7 +1318,7 @@ static RedLaunch plan_arg(const MdRedPlan &pl, const mdhip_array *x, int64_t tsz
     }
   }
   if (pl.nr == 1 && pl.rx[0] == 1 && n_red >= 24 && (n_red < 1024 || !typed) && n_red <= 65536 && n_out >= 64) {
-    L.blocks = ceil_div(n_out, MD_BLOCK / 64);
+    L.blocks = md_ceil_div(n_out, MD_BLOCK / 64);
     if (L.blocks > 8 * MD_NUM_CUS) L.blocks = 8 * MD_NUM_CUS;
     L.typed = typed;
     return red_pick(L, ARG_ROWS_WAVE, "argreduce(rows,wave)");
@@ -1365,7 +1363,7 @@ static int run_arg(const RedLaunch &L, const MdRedPlan &pl, const mdhip_array *x
       if constexpr (!WIDE) return red_unplanned(L);
       else {
         k_arg_rows_vec<IsMax, T, false><<<(unsigned)(n_out * L.splits), MD_BLOCK, 0, st>>>(pl, (const T *)x->data, L.splits, L.chunk, (T *)pv, (int64_t *)pi);
-        k_arg_rows_finish<IsMax, T><<<(unsigned)ceil_div(n_out, MD_BLOCK), MD_BLOCK, 0, st>>>(pl, (const T *)pv, (const int64_t *)pi, L.splits, o);
+        k_arg_rows_finish<IsMax, T><<<(unsigned)md_ceil_div(n_out, MD_BLOCK), MD_BLOCK, 0, st>>>(pl, (const T *)pv, (const int64_t *)pi, L.splits, o);
       }
       break;
     case ARG_ROWS_WAVE:

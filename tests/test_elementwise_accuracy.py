@@ -378,7 +378,7 @@ def _functor_cases(dt):
 def _paths(ctx, dt):
     lazy = dt is not np.float16           # storage-only types are never leaves of a fused program
     # Interpreter legs: which of k_vm_eval_fast / _axes / _generic serves a program is decided by the operands' geometry alone (fusion.hip
-    # eval_typed): dense -> fast; a sliced (8, 32, 256) view with aligned rows of 2**16 elements -> axes; a [::2] view (inner stride 2) ->
+    # plan_eval): dense -> fast; a sliced (8, 32, 256) view with aligned rows of 2**16 elements -> axes; a [::2] view (inner stride 2) ->
     # generic. Neither FUSION_STATS nor the C-ABI tells the three apart, so the layouts are chosen by those rules and not asserted.
     scalar = float(dt(0.3))               # exactly representable in dt: a Python float operand means this value in every loop
     for name, f, hs, is_bool in _functor_cases(dt):

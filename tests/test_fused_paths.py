@@ -11,7 +11,8 @@ the C-ABI as DeviceArray._materialize and the reducers call it (lazy.build_progr
 vm_eval_multi), once with jit = 1, jit_min = 1 and once with jit = 0. The `reaches` column is confirmed by a kernel trace of the gpu
 half (profiles/README.md: fused_paths_kernel_stats.csv).
 
-Where the numbers come from (MD_BLOCK 256, MD_NUM_CUS 256; a vector group is 4 elements whatever the leaf's storage type):
+Where the numbers come from (MD_BLOCK 256, MD_NUM_CUS 256; a vector group is 4 elements whatever the leaf's storage type; the functions
+named are those of fusion.hip's launch planners plan_eval / plan_reduce, which choose the form and its numbers before anything is launched):
   md_grid_for / stream_grid     min(ceil(work / 256), cap) blocks, work = rows * nv + (4 if rows == 1: the tail lanes); the default cap
                                 is 2048 (interpreter), 256 * eval_blocks (generated EVAL: 8 / 4 / 2 per CU for <= 2 / 3 / >= 4
                                 16-byte streams) or 1024 (RED_ALL). Option max_blocks replaces every one of them: max_blocks = 3
