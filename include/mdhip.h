@@ -360,10 +360,11 @@ enum {
   MDHIP_VM_PUSH = 0, /* push rhs operand (leaf or const) */
   MDHIP_VM_UNARY,    /* s0 = f(s0), op = MDHIP_U_* */
   MDHIP_VM_BINARY,   /* op = MDHIP_B_*; operands: see below */
-  MDHIP_VM_WHERE     /* s0 = s2 ? s1 : s0, pops 2 */
+  MDHIP_VM_WHERE,    /* s0 = s2 ? s1 : s0, pops 2 */
+  MDHIP_VM_ROWRED    /* staged programs only (below): ends a stage, the one value on the stack reduced over the row */
 };
-/* operand sources of a BINARY (and the rhs of PUSH) */
-enum { MDHIP_VM_SRC_STACK = 0, MDHIP_VM_SRC_LEAF = 1, MDHIP_VM_SRC_CONST = 2 };
+/* operand sources of a BINARY (and the rhs of PUSH); SRC_ROW: a row register of a staged program (below) */
+enum { MDHIP_VM_SRC_STACK = 0, MDHIP_VM_SRC_LEAF = 1, MDHIP_VM_SRC_CONST = 2, MDHIP_VM_SRC_ROW = 3 };
 /* ctrl word: kind[0:2] op[3:7] lhs_src[8:9] lhs_leaf[10:12] rhs_src[13:14] rhs_leaf[15:17] round16[18].
  * BINARY: value = op(lhs, rhs). Both STACK: lhs = s1, rhs = s0, pops one. One STACK:
  * it is s0, replaced in place (the common "x = op(x, leaf|const)" costs no stack traffic).
@@ -377,6 +378,20 @@ enum { MDHIP_VM_SRC_STACK = 0, MDHIP_VM_SRC_LEAF = 1, MDHIP_VM_SRC_CONST = 2 };
  * half loops compute in float32 and round once per call. Refused (MDHIP_EVALUE) under compute_dtype F64 and on PUSH / WHERE,
  * which compute nothing. */
 #define MDHIP_VM_RND16 (1u << 18)
+/* STAGED programs (mdhip_vm_eval and mdhip_vm_jit_probe kind 10 only; every other entry point, the interpreter kernels and the
+ * CPU test double return MDHIP_EVALUE for them). "Reduce each row, then use that row's statistic in a chain over the same row" —
+ * softmax, its gradient, a mean / variance layer norm — in ONE launch that holds the row in registers across the stages.
+ * The program is stage 0, ROWRED -> r0, stage 1, ROWRED -> r1, .., final stage. A stage is an ordinary postfix sequence that
+ * starts on an empty stack. MDHIP_VM_ROWRED ends it: the stack must hold exactly ONE value, which is reduced over the row with
+ * op = MDHIP_R_SUM | PROD | MAX | MIN; the result becomes row register k = the rhs_leaf field (at most MDHIP_VM_ROW_REGS
+ * registers, written in the order 0, 1, .., each once) and the stack is empty afterwards. imm[pc] of a ROWRED is the row length
+ * n_red in elements — the trailing axes of `out` whose extents multiply to it are the row; 0: the last axis — and is the same in
+ * every ROWRED of a program. MDHIP_VM_SRC_ROW as the rhs of a PUSH or as either operand of a BINARY reads the row register named
+ * by the leaf-index field, written by an EARLIER stage. The final stage leaves one value, which is stored. MDHIP_VM_RND16 on a
+ * ROWRED is refused. Geometry: that of mdhip_vm_reduce's third form below, with n_red <= 2048, n_out >= 2 and a dense, 16-byte
+ * aligned `out` of the compute dtype; anything else returns MDHIP_EVALUE and the caller composes the stages from mdhip_vm_reduce
+ * and mdhip_vm_eval, which give the same bits (each stage combines in the order of that form's wave-per-row kernel). */
+#define MDHIP_VM_ROW_REGS 4
 typedef struct mdhip_vm_program {
   int32_t n_instr, n_leaves, compute_dtype, _pad;
   uint32_t ctrl[MDHIP_VM_MAX_INSTR];
@@ -431,7 +446,8 @@ int mdhip_vm_reduce(const mdhip_vm_program *prog, int reduce_op, const mdhip_arr
  * the program's own leaf descriptors, 6 = row reduce with a wave per row, 7 = row
  * reduce with a block per row, 8 / 9 = the batched column reduces of a middle axis
  * (8 strips, 9 tiled) on a 3-D program whose axis 1 is the reduced one, read modes from
- * its leaf descriptors; out_is_bool: 1 a BOOL out, 2 a FLOAT16 out (kinds 0 and 5); needs no device; on success `log` starts
+ * its leaf descriptors, 10 = a STAGED program (rows kept in registers; vector groups per lane from the row length of its
+ * ROWREDs, else from the last extent of its first leaf); out_is_bool: 1 a BOOL out, 2 a FLOAT16 out (kinds 0 and 5); needs no device; on success `log` starts
  * with the name the kernel would carry), and counters {kernels compiled, kernels
  * launched}. Generated kernels are named k_fused_<form>_<digest of the program
  * signature>. */

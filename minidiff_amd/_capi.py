@@ -65,8 +65,9 @@ class IndexPlan(C.Structure):
 
 
 VM_MAX_INSTR, VM_MAX_LEAVES = 48, 8
-VM_PUSH, VM_UNARY, VM_BINARY, VM_WHERE = range(4)
-VM_SRC_STACK, VM_SRC_LEAF, VM_SRC_CONST = range(3)
+VM_PUSH, VM_UNARY, VM_BINARY, VM_WHERE, VM_ROWRED = range(5)
+VM_SRC_STACK, VM_SRC_LEAF, VM_SRC_CONST, VM_SRC_ROW = range(4)
+VM_ROW_REGS = 4      # MDHIP_VM_ROW_REGS: row registers of a staged program (VM_ROWRED writes one, VM_SRC_ROW reads one)
 
 
 VM_RND16 = 1 << 18   # MDHIP_VM_RND16: the instruction's value is rounded through binary16 (UNARY / BINARY of float32 programs)

@@ -553,6 +553,7 @@ enum VmForm {
   VM_COLS_TILED,    // k_vm_reduce_cols | generated RED_COLS: one pass (splits == 1), or `splits` partial rows and a second pass
   VM_COLS_BATCHED,  // .. with the batch on the grid: `outer` problems in one launch, unsplit
   VM_ROWS,          // k_vm_reduce_rows | generated RED_ROWS
+  VM_ROWS_STAGED,   // generated ROWS_STAGED only: a staged program, every row held in registers across its stages
 };
 // plan_begin sets the scalars (0; outer = splits = 1); the four tables are NOT zeroed per call and hold something only where a
 // planner filled them: D in every form but VM_NONE, `it` where md_vm_build_iter ran (not on reduce_axis's path), G and B as noted.
@@ -641,16 +642,79 @@ static void plan_begin(VmLaunch *L, const mdhip_vm_program *pr) {
   L->partial_bytes = 0;
 }
 
+// Trailing-axis reductions (mdhip_vm_reduce's third form): rows up to 64 lanes x 8 groups x 4 elements go a wave per row in the
+// generated kernels, longer ones a block per row; long rows need at least a row per CU (no cross-block split yet)
+constexpr int64_t VM_ROWS_WAVE_MAX = 64 * 4 * 8;
+constexpr int64_t VM_ROWS_MIN_OUT = MD_NUM_CUS;
+// vector groups per lane of the wave-per-row kernels (RED_ROWS, ROWS_STAGED) for a row of n_red <= VM_ROWS_WAVE_MAX elements
+static int rows_wave_nv(int64_t n_red) {
+  const int64_t nvec = n_red >> 2;
+  return nvec <= 64 ? 1 : nvec <= 128 ? 2 : nvec <= 256 ? 4 : 8;
+}
+// A staged kernel holds NV groups of every vector leaf in registers through all its stages: 4 NV registers per float32 leaf and
+// lane, 8 NV per float64 one. Up to this many the compiled kernels use no scratch (DESIGN.md §4.7 has the figures); a program
+// that would hold more is refused, and the caller composes.
+constexpr int VM_STAGED_HELD_MAX = 256;
+static int staged_held(const jit::Spec &S) {
+  int vec = 0;
+  for (int l = 0; l < S.n_leaves; ++l) vec += S.leaf_mode[l] == jit::LM_VEC;
+  return vec * S.NV * (S.f32 ? 4 : 8);
+}
+
+// A program whose operands are all dense or fully broadcast collapses to ONE axis; the column reductions want it as
+// (R rows, C columns) again: dense leaves advance C elements per row, broadcast ones none.
+static bool uncollapse_2d(const MdVmIter &it, int n_leaves, MdVmDev *D, int64_t R, int64_t C, int64_t *rows, int64_t *inner) {
+  if (it.ndim == 2 && *rows == R && *inner == C) return true;
+  if (it.ndim != 1 || *rows != 1 || *inner != R * C || (C & 3)) return false;
+  for (int l = 0; l < n_leaves; ++l) D->leaf[l].os = D->leaf[l].is ? C : 0;
+  *rows = R;
+  *inner = C;
+  return true;
+}
+
+// Plan a STAGED program (include/mdhip.h) into `out`: the (n_out, n_red) geometry of mdhip_vm_reduce's third form with rows a wave
+// holds, generated kernel only. Every refusal is MDHIP_EVALUE: the caller composes the stages from mdhip_vm_reduce and mdhip_vm_eval.
+static int plan_staged(const mdhip_vm_program *pr, const mdhip_array *out, int64_t n_red, VmLaunch *L) {
+  if (out->dtype != pr->compute_dtype) return md_fail(MDHIP_EVALUE, "vm_eval: a staged program stores the compute dtype only");
+  const int nd = out->ndim;
+  if (nd < 1) return md_fail(MDHIP_EVALUE, "vm_eval: a staged program needs an axis to reduce");
+  if (n_red == 0) n_red = out->shape[nd - 1];
+  int64_t p = 1;
+  for (int d = nd - 1; d >= 0 && p < n_red; --d) p *= out->shape[d];
+  if (p != n_red || n_red < 4 || (n_red & 3)) return md_fail(MDHIP_EVALUE, "vm_eval: rows of %lld elements are not trailing axes of whole 16-byte groups", (long long)n_red);
+  if (n_red > VM_ROWS_WAVE_MAX) return md_fail(MDHIP_EVALUE, "vm_eval: rows of %lld elements are longer than a wave holds (%lld)", (long long)n_red, (long long)VM_ROWS_WAVE_MAX);
+  MD_TRY(md_vm_build_iter(&L->it, pr, out, out));
+  const int64_t total = L->it.total, n_out = total / n_red;
+  if (n_out < 2 || n_out >= (1ll << 31)) return md_fail(MDHIP_EVALUE, "vm_eval: %lld rows are not staged", (long long)n_out);
+  to_dev(pr, &L->D);
+  if (!fast_geometry(L->it, pr->n_leaves, pr, true, &L->D, &L->rows, &L->inner) || !aligned16(out->data) ||
+      !uncollapse_2d(L->it, pr->n_leaves, &L->D, n_out, n_red, &L->rows, &L->inner))
+    return md_fail(MDHIP_EVALUE, "vm_eval: a staged program needs (rows, reduced) geometry with rows of whole, aligned 16-byte groups");
+  jit::Spec S;
+  if (!jit::spec_for(&S, jit::ROWS_STAGED, pr, L->D, L->rows, total)) return md_fail(MDHIP_EVALUE, "vm_eval: a staged program runs as a generated kernel only (options jit, jit_min)");
+  S.NV = rows_wave_nv(n_red);
+  if (staged_held(S) > VM_STAGED_HELD_MAX) return md_fail(MDHIP_EVALUE, "vm_eval: the staged program would hold %d registers per lane (max %d)", staged_held(S), VM_STAGED_HELD_MAX);
+  // streamed: the stored value and the leaves that advance from row to row (a row-invariant vector is re-read from the caches)
+  S.nt = total * (int64_t)md_dtype_size(out->dtype) + jit::streamed_bytes(L->D, total, true) > jit::NT_BYTES;
+  L->fn = jit::get(S);
+  if (!L->fn) return md_fail(MDHIP_EVALUE, "vm_eval: no run-time compiler for the staged program");
+  L->form = VM_ROWS_STAGED;
+  L->n_out = n_out; L->n_red = n_red;
+  L->grid = md_ceil_div(n_out, 4);
+  return MDHIP_OK;
+}
+
 // Plan an evaluation into outs[0 .. n). n == 1 is mdhip_vm_eval: the fast, the axes or the generic form, each (but the generic one)
 // generated from jit_min elements on and interpreted below. The output's dtype says what is stored — the compute type, b8 (truth
 // values) or f16 (the chain's value rounded ONCE to binary16 in the same pass: astype(chain, float16)).
 // n > 1 is mdhip_vm_eval_multi: the programs share ONE generated launch on the fast or the axes geometry (`merged`, the caller's,
 // holds their common leaf table and immediates and lives as long as the plan), or the plan stays VM_NONE — declined, never an
 // error: the caller evaluates them one by one.
-static int plan_eval(const mdhip_vm_program *progs, const mdhip_array *outs, int n, mdhip_vm_program *merged, VmLaunch *L) {
+static int plan_eval(const mdhip_vm_program *progs, const mdhip_array *outs, int n, mdhip_vm_program *merged, VmLaunch *L, int64_t staged_n_red = -1) {
   const bool multi = n > 1;
   const mdhip_vm_program *pr = progs;   // whose leaves give the geometry: the one program, or the merged table
   plan_begin(L, pr);
+  if (staged_n_red >= 0) return plan_staged(pr, &outs[0], staged_n_red, L);   // a staged program, as mdhip_vm_eval's md_vm_check_staged found it
   jit::Spec S;
   if (multi) {
     if (!jit::enabled() || !merge_programs(progs, n, &S, merged)) return MDHIP_OK;
@@ -707,22 +771,6 @@ static int plan_eval(const mdhip_vm_program *progs, const mdhip_array *outs, int
   L->grid = md_grid_for(total);
   L->form = VM_EVAL_GENERIC;
   return MDHIP_OK;
-}
-
-// Trailing-axis reductions (mdhip_vm_reduce's third form): rows up to 64 lanes x 8 groups x 4 elements go a wave per row in the
-// generated kernels, longer ones a block per row; long rows need at least a row per CU (no cross-block split yet)
-constexpr int64_t VM_ROWS_WAVE_MAX = 64 * 4 * 8;
-constexpr int64_t VM_ROWS_MIN_OUT = MD_NUM_CUS;
-
-// A program whose operands are all dense or fully broadcast collapses to ONE axis; the column reductions want it as
-// (R rows, C columns) again: dense leaves advance C elements per row, broadcast ones none.
-static bool uncollapse_2d(const MdVmIter &it, int n_leaves, MdVmDev *D, int64_t R, int64_t C, int64_t *rows, int64_t *inner) {
-  if (it.ndim == 2 && *rows == R && *inner == C) return true;
-  if (it.ndim != 1 || *rows != 1 || *inner != R * C || (C & 3)) return false;
-  for (int l = 0; l < n_leaves; ++l) D->leaf[l].os = D->leaf[l].is ? C : 0;
-  *rows = R;
-  *inner = C;
-  return true;
 }
 
 // Strip geometry for a (n_red x n_out) program (the generated SWEEP kernel, fusion_jit.inc): NS strips of 256 columns x NB
@@ -945,8 +993,7 @@ static int plan_reduce(const mdhip_vm_program *pr, int rop, const mdhip_array *s
     if (jit::spec_for(&S, jit::RED_ROWS, pr, D, rows, it.total, rop)) {
       // streamed: the leaves that advance from row to row (a row-invariant vector is re-read from the caches)
       S.nt = jit::streamed_bytes(D, it.total, true) > jit::NT_BYTES;
-      const int64_t nvec = n_red >> 2;   // wave per row: 1 / 2 / 4 / 8 vector groups per lane; block per row (NV 0) above
-      S.NV = n_red > VM_ROWS_WAVE_MAX ? 0 : nvec <= 64 ? 1 : nvec <= 128 ? 2 : nvec <= 256 ? 4 : 8;
+      S.NV = n_red > VM_ROWS_WAVE_MAX ? 0 : rows_wave_nv(n_red);   // wave per row: 1 / 2 / 4 / 8 vector groups per lane; block per row (NV 0) above
       L->fn = jit::get(S);
       if (L->fn) L->grid = S.NV ? md_ceil_div(n_out, 4) : n_out;
     }
@@ -1018,6 +1065,10 @@ static int run_generated(const VmLaunch &L, void *out, void *const *outs, void *
       break;
     case VM_ROWS:
       jit::args_shape(&A, L.rows, L.inner, L.n_out, L.n_red, L.chunk);
+      break;
+    case VM_ROWS_STAGED:
+      jit::args_shape(&A, L.rows, L.inner, L.n_out, L.n_red, 0);
+      A.outs[0] = outs[0];
       break;
     default:
       return vm_unplanned(L);
@@ -1166,13 +1217,18 @@ static int probe_compile(const jit::Spec &S, char *log, size_t log_cap) {
 extern "C" {
 
 int mdhip_vm_eval(const mdhip_vm_program *pr, const mdhip_array *out) {
-  MD_TRY(md_vm_check(pr));
+  int64_t staged_n_red = -1;   // >= 0: a staged program (rows kept in registers across the stages: plan_staged, or MDHIP_EVALUE and the caller composes)
+  if (md_vm_is_staged(pr)) {
+    MD_TRY(md_vm_check_staged(pr, nullptr, &staged_n_red));
+  } else {
+    MD_TRY(md_vm_check(pr));
+  }
   MD_TRY(md_check_any_array(out, "vm out"));
   const bool f32 = pr->compute_dtype == MDHIP_F32;
   if (out->dtype != MDHIP_BOOL && out->dtype != MDHIP_F16 && out->dtype != pr->compute_dtype)
     return md_fail(MDHIP_ETYPE, "vm_eval: out dtype must be the compute dtype, bool or float16");
   VmLaunch L;
-  MD_TRY(plan_eval(pr, out, 1, nullptr, &L));
+  MD_TRY(plan_eval(pr, out, 1, nullptr, &L, staged_n_red));
   if (out->dtype == MDHIP_BOOL) return f32 ? run_eval<float, b8>(L, out) : run_eval<double, b8>(L, out);
   if (out->dtype == MDHIP_F16) return f32 ? run_eval<float, f16>(L, out) : run_eval<double, f16>(L, out);
   return f32 ? run_eval<float, float>(L, out) : run_eval<double, double>(L, out);
@@ -1216,6 +1272,20 @@ int mdhip_vm_jit_probe_multi(const mdhip_vm_program *progs, int n, char *log, si
 }
 
 int mdhip_vm_jit_probe(const mdhip_vm_program *pr, int kind, int reduce_op, int out_is_bool, char *log, size_t log_cap) {
+  if (kind == 10) {   // a staged program: NV from the row length its ROWREDs name, else from the last extent of its first leaf
+    if (!md_vm_is_staged(pr)) return md_fail(MDHIP_EVALUE, "jit probe: kind 10 takes a staged program (one with a ROWRED)");
+    int64_t n_red;
+    MD_TRY(md_vm_check_staged(pr, nullptr, &n_red));
+    if (n_red == 0 && pr->n_leaves > 0 && pr->leaves[0].ndim > 0) n_red = pr->leaves[0].shape[pr->leaves[0].ndim - 1];
+    if (n_red < 4 || (n_red & 3) || n_red > VM_ROWS_WAVE_MAX) return md_fail(MDHIP_EVALUE, "jit probe: rows of %lld elements are not staged", (long long)n_red);
+    jit::Spec S;
+    S.kind = jit::ROWS_STAGED;
+    jit::spec_single(&S, pr);
+    probe_modes(&S, pr);
+    S.NV = rows_wave_nv(n_red);
+    if (staged_held(S) > VM_STAGED_HELD_MAX) return md_fail(MDHIP_EVALUE, "jit probe: the staged program would hold %d registers per lane (max %d)", staged_held(S), VM_STAGED_HELD_MAX);
+    return probe_compile(S, log, log_cap);
+  }
   MD_TRY(md_vm_check(pr));
   if (kind < 0 || kind > 9)
     return md_fail(MDHIP_EVALUE, "jit probe: kind must be 0 (eval), 1 (reduce all), 2 (reduce columns, tiled), 3 (reduce columns, sweep), 4 (eval + reduce columns), 5 (eval over three / four axes), 6 (reduce rows, a wave per row), 7 (reduce rows, a block per row), 8 (reduce a middle axis, batched sweep) or 9 (reduce a middle axis, batched tiled)");

@@ -170,7 +170,7 @@ static const char *reduce_name(int op) {
 //   LM_ROWINV (sweep kernels only) unit inner stride, row stride 0 (the bias row): the lane's column
 //             vectors are loaded once, before the row loop
 enum { LM_VEC = 0, LM_ROWB = 1, LM_CONST = 2, LM_ROWINV = 3 };
-enum Kind { EVAL = 0, RED_ALL = 1, RED_COLS = 2, SWEEP = 3, RED_ROWS = 4 };
+enum Kind { EVAL = 0, RED_ALL = 1, RED_COLS = 2, SWEEP = 3, RED_ROWS = 4, ROWS_STAGED = 5 };
 
 struct Spec {
   int kind = EVAL;
@@ -191,6 +191,7 @@ struct Spec {
   int axes = 0;                     // EVAL: 0 the (rows, inner) form | 3, 4 that many collapsed axes (fusion.hip's axes_geometry)
   bool wide = false;                // EVAL over axes: 64-bit vector index (2^31 vectors and more), else 32-bit
   int NV = 0;                       // RED_ROWS: 1, 2, 4, 8 vector groups per lane, a wave per row | 0 a block per row
+                                    // ROWS_STAGED (a staged program: its stages are cut at the ROWREDs of pr[0]): 1, 2, 4, 8
   bool batch = false;               // RED_COLS / SWEEP: `outer` independent (n_red, n_out) problems, the batch on blockIdx.y (a middle axis reduced)
 };
 
@@ -242,11 +243,15 @@ static void scan_trig(const mdhip_vm_program *pr, const int *leaf_map, TrigUse *
 }
 
 // body<k>(): program k as scalar SSA over one element; leaf values (and their hoisted sin / cos) arrive as arguments
-static std::string gen_body(const Spec &S, int k, const TrigUse &tu) {
+// (a staged program: body<b> is the stage [pc0, pc1) of program k, and the n_regs row registers written before it arrive as r0, ..)
+static std::string gen_body(const Spec &S, int k, const TrigUse &tu, int b = -1, int pc0 = 0, int pc1 = -1, int n_regs = 0) {
   const mdhip_vm_program *pr = S.pr[k];
+  if (b < 0) b = k;
+  if (pc1 < 0) pc1 = pr->n_instr;
   std::ostringstream o;
-  o << "__device__ __forceinline__ T body" << k << "(const JArgs &A";
+  o << "__device__ __forceinline__ T body" << b << "(const JArgs &A";
   for (int l = 0; l < S.n_leaves; ++l) o << ", const T l" << l;
+  for (int r = 0; r < n_regs; ++r) o << ", const T r" << r;
   for (int l = 0; l < S.n_leaves; ++l) {
     if (tu.s[l]) o << ", const T sn" << l;
     if (tu.c[l]) o << ", const T cs" << l;
@@ -255,10 +260,11 @@ static std::string gen_body(const Spec &S, int k, const TrigUse &tu) {
   std::vector<std::string> st;
   auto operand = [&](uint32_t src, uint32_t leaf, int pc) -> std::string {
     if (src == MDHIP_VM_SRC_LEAF) return "l" + std::to_string(S.leaf_map[k][leaf]);
+    if (src == MDHIP_VM_SRC_ROW) return "r" + std::to_string(leaf);
     o << "  const T c" << pc << " = (T)A.imm[" << S.imm_slot[k][pc] << "];\n";
     return "c" + std::to_string(pc);
   };
-  for (int pc = 0; pc < pr->n_instr; ++pc) {
+  for (int pc = pc0; pc < pc1; ++pc) {
     const uint32_t c = pr->ctrl[pc];
     const uint32_t kd = MD_VM_KIND(c), op = MD_VM_OP(c), ls = MD_VM_LS(c), rs = MD_VM_RS(c);
     const bool r16 = (c & MDHIP_VM_RND16) != 0;  // the instruction's value goes through binary16 (md_vm.h: md_vm_round16)
@@ -268,7 +274,8 @@ static std::string gen_body(const Spec &S, int k, const TrigUse &tu) {
     } else if (kd == MDHIP_VM_UNARY) {
       std::string x = st.back();
       st.pop_back();
-      if ((op == MDHIP_U_SIN || op == MDHIP_U_COS) && x.size() >= 2 && x[0] == 'l' && x.find_first_not_of("0123456789", 1) == std::string::npos) {
+      if ((op == MDHIP_U_SIN || op == MDHIP_U_COS) && x.size() >= 2 && x[0] == 'l' && x.find_first_not_of("0123456789", 1) == std::string::npos &&
+          (op == MDHIP_U_SIN ? tu.s : tu.c)[std::stoi(x.substr(1))]) {
         const std::string h = (op == MDHIP_U_SIN ? "sn" : "cs") + x.substr(1);  // hoisted
         if (r16) {  // the hoisted value is shared with unflagged uses: round it where this instruction takes it
           o << "  const T t" << pc << " = jr16(" << h << ");\n";
@@ -528,16 +535,19 @@ static std::string kind_tag(const Spec &S) {
     case RED_ALL: return "redall";
     case RED_COLS: return S.batch ? "redcolsb" : "redcols";
     case RED_ROWS: return S.NV ? "redrowsw" + std::to_string(S.NV) : "redrowsb";
+    case ROWS_STAGED: return "rowsres" + std::to_string(S.NV);
   }
   return S.store ? "evalcols" : S.batch ? "sweepb" : "sweepcols";
 }
 
 static std::string gen_source(const Spec &S, const std::string &kname) {
-  TrigUse tu;
-  for (int k = 0; k < S.n; ++k) scan_trig(S.pr[k], S.leaf_map[k], &tu);
+  TrigUse tu;   // (a staged program hoists nothing: a held sin / cos would cost registers through every stage)
+  if (S.kind != ROWS_STAGED)
+    for (int k = 0; k < S.n; ++k) scan_trig(S.pr[k], S.leaf_map[k], &tu);
   std::ostringstream o;
   gen_prelude(o, S, kname);
-  for (int k = 0; k < S.n; ++k) o << gen_body(S, k, tu);
+  if (S.kind != ROWS_STAGED)
+    for (int k = 0; k < S.n; ++k) o << gen_body(S, k, tu);
   const LeafText LT{S, tu};
   auto emit_outputs = [&](const std::string &sfx, const std::string &off, const char *ind) {
     std::ostringstream e;
@@ -700,6 +710,61 @@ static std::string gen_source(const Spec &S, const std::string &kname) {
 }
 )";
     }
+  } else if (S.kind == ROWS_STAGED) {
+    // A staged program (include/mdhip.h: stage, ROWRED -> r0, stage, ROWRED -> r1, .., final stage) on the geometry of the wave-per-row
+    // reduction above: a wave per row, four rows per block, lane l holds the vector groups l + 64 g, g < NV, of every vector leaf —
+    // loaded once, all loads ahead of the first use. Each stage is evaluated on the held values and combined EXACTLY as
+    // redrowsw<NV> combines: four accumulators over the groups in order, merged pairwise, the 64-lane tree; lane 0's result then goes
+    // to every lane (through a scalar register: a row statistic costs no vector register). The final stage is evaluated on the same
+    // values and stored as 16-byte vectors. One read of the operands, one write, no statistic in memory.
+    const unsigned vecm = 1u << LM_VEC, rowb = 1u << LM_ROWB;
+    const mdhip_vm_program *pr = S.pr[0];
+    std::vector<int> cut;     // pc of every ROWRED
+    for (int pc = 0; pc < pr->n_instr; ++pc)
+      if (MD_VM_KIND(pr->ctrl[pc]) == MDHIP_VM_ROWRED) cut.push_back(pc);
+    const int ns = (int)cut.size();
+    for (int s = 0; s <= ns; ++s) o << gen_body(S, 0, tu, s, s ? cut[s - 1] + 1 : 0, s < ns ? cut[s] : pr->n_instr, s);
+    o << R"(__device__ __forceinline__ float jbcast(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
+__device__ __forceinline__ double jbcast(double v) {
+  union { double f; int w[2]; } u; u.f = v;
+  u.w[0] = __builtin_amdgcn_readfirstlane(u.w[0]); u.w[1] = __builtin_amdgcn_readfirstlane(u.w[1]);
+  return u.f;
+}
+)";
+    o << "extern \"C\" __global__ void __launch_bounds__(256) KNAME(JArgs A) {\n"
+         "  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;\n"
+         "  const long long row = (long long)blockIdx.x * 4 + w;\n"
+         "  if (row >= A.n_out) return;  // (whole waves: no barrier below, and every lane of a live wave is active)\n"
+         "  const long long nv = A.n_red >> 2;\n"
+      << LT.pro() << LT.vec("row", "0", "_r", rowb, "  ");
+    for (int g = 0; g < S.NV; ++g) {
+      const std::string sfx = "_" + std::to_string(g);
+      o << "  const bool ok" << sfx << " = lane + " << 64 * g << " < nv;\n"
+        << "  const long long c" << sfx << " = (ok" << sfx << " ? (long long)(lane + " << 64 * g << ") : 0ll) << 2;\n"
+        << LT.vec("row", "c" + sfx, sfx, vecm, "  ");
+    }
+    auto regs = [](int n) {
+      std::string r;
+      for (int k = 0; k < n; ++k) r += ", r" + std::to_string(k);
+      return r;
+    };
+    for (int s = 0; s < ns; ++s) {
+      const std::string R = reduce_name((int)MD_VM_OP(pr->ctrl[cut[s]]));
+      o << "  T r" << s << ";\n  {\n    T a[4];\n#pragma unroll\n    for (int j = 0; j < 4; ++j) a[j] = " << R << "::template identity<T>();\n";
+      for (int g = 0; g < S.NV; ++g) {
+        const std::string sfx = "_" + std::to_string(g);
+        o << "    if (ok" << sfx << ") {\n#pragma unroll\n      for (int j = 0; j < 4; ++j) a[j] = " << R << "::combine(a[j], body" << s << "(A" << LT.args(sfx, "j", "_r") << regs(s) << "));\n    }\n";
+      }
+      o << "    T acc = " << R << "::combine(" << R << "::combine(a[0], a[1]), " << R << "::combine(a[2], a[3]));\n"
+           "#pragma unroll\n    for (int d = 32; d > 0; d >>= 1) acc = " << R << "::combine(acc, jshfl(acc, d));\n"
+           "    r" << s << " = jbcast(acc);  // lane 0 holds the row's value: to every lane\n  }\n";
+    }
+    for (int g = 0; g < S.NV; ++g) {
+      const std::string sfx = "_" + std::to_string(g);
+      o << "  if (ok" << sfx << ") {\n    JVec<T, 4> o;\n#pragma unroll\n    for (int j = 0; j < 4; ++j) o.v[j] = body" << ns << "(A" << LT.args(sfx, "j", "_r") << regs(ns) << ");\n"
+        << "    jst(reinterpret_cast<JVec<T, 4> *>((T *)A.outs[0] + row * A.n_red + c" << sfx << "), o);\n  }\n";
+    }
+    o << "}\n";
   } else if (S.kind == RED_COLS) {
     // tiled: block = 64 column groups x 4 row lanes, rows split over gridDim.y; two rows in flight per lane
     // (batched: gridDim.y is the batch, rows unsplit — the form below the strips kernel's floor of 512 reduced rows)
@@ -897,15 +962,20 @@ static int compile(const std::string &src, std::vector<char> *code, std::string 
   if (!rtc_load()) { if (log) *log = "libhiprtc not available"; return -1; }
   rtcProgram prog = nullptr;
   if (RTC.Create(&prog, src.c_str(), "mdhip_fused.hip", 0, nullptr, nullptr) != 0) { if (log) *log = "hiprtcCreateProgram failed"; return -1; }
-  const char *opts[] = {"--offload-arch=gfx950", "-O3", "-std=c++17"};
-  const int rc = RTC.Compile(prog, 3, opts);
-  if (rc != 0) {
+  // (option jit_verbose = 2: the compiler's resource remarks — registers, scratch, occupancy of the kernel — come back in the log
+  // of a successful compilation too: how the probe shows that a form does not spill)
+  const bool usage = md_opt(MD_OPT_JIT_VERBOSE) >= 2;
+  const char *opts[] = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-Rpass-analysis=kernel-resource-usage"};
+  const int rc = RTC.Compile(prog, usage ? 4 : 3, opts);
+  if (rc != 0 || usage) {
     if (log && RTC.GetLogSize && RTC.GetLog) {
       size_t n = 0;
       RTC.GetLogSize(prog, &n);
       log->assign(n, '\0');
       if (n) RTC.GetLog(prog, &(*log)[0]);
     }
+  }
+  if (rc != 0) {
     RTC.Destroy(&prog);
     return -1;
   }

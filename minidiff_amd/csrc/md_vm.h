@@ -192,18 +192,30 @@ struct MdVmFetchDirect {
 };
 
 // ---- validation + geometry, shared by both builds ---------------------------------
-static inline int md_vm_check(const mdhip_vm_program *pr) {
+// One checker. staged == false is md_vm_check: kind 4 and source 3 are refused (the interpreters, the CPU double's among them, would
+// run the unknown kind as WHERE). staged == true is md_vm_check_staged, for a STAGED program (include/mdhip.h: one that holds a
+// MDHIP_VM_ROWRED): only the product's mdhip_vm_eval and mdhip_vm_jit_probe ask md_vm_is_staged first and then check that way.
+// *n_regs: the row registers written; *n_red: the row length the ROWREDs name (0: the last axis).
+static inline int md_vm_check_impl(const mdhip_vm_program *pr, bool staged, int *n_regs, int64_t *n_red) {
   if (!pr) return md_fail(MDHIP_EVALUE, "vm: null program");
   if (pr->n_instr < 1 || pr->n_instr > MDHIP_VM_MAX_INSTR) return md_fail(MDHIP_EVALUE, "vm: %d instructions (max %d)", pr->n_instr, MDHIP_VM_MAX_INSTR);
   if (pr->n_leaves < 0 || pr->n_leaves > MDHIP_VM_MAX_LEAVES) return md_fail(MDHIP_EVALUE, "vm: %d leaves (max %d)", pr->n_leaves, MDHIP_VM_MAX_LEAVES);
   if (pr->compute_dtype != MDHIP_F32 && pr->compute_dtype != MDHIP_F64) return md_fail(MDHIP_ETYPE, "vm: compute dtype must be float32 or float64");
-  int depth = 0;
+  int depth = 0, regs = 0;
+  double row = -1.0;
   for (int pc = 0; pc < pr->n_instr; ++pc) {
     const uint32_t c = pr->ctrl[pc];
     const uint32_t k = MD_VM_KIND(c), op = MD_VM_OP(c), ls = MD_VM_LS(c), rs = MD_VM_RS(c);
     if (ls == MDHIP_VM_SRC_LEAF && (int)MD_VM_LL(c) >= pr->n_leaves) return md_fail(MDHIP_EVALUE, "vm: leaf index out of range at %d", pc);
     if (rs == MDHIP_VM_SRC_LEAF && (int)MD_VM_RL(c) >= pr->n_leaves) return md_fail(MDHIP_EVALUE, "vm: leaf index out of range at %d", pc);
-    if (ls > MDHIP_VM_SRC_CONST || rs > MDHIP_VM_SRC_CONST) return md_fail(MDHIP_EVALUE, "vm: bad operand source at %d", pc);
+    if (!staged) {
+      if (ls > MDHIP_VM_SRC_CONST || rs > MDHIP_VM_SRC_CONST) return md_fail(MDHIP_EVALUE, "vm: bad operand source at %d", pc);
+    } else {
+      // a row register is read by a PUSH (rhs) or a BINARY, and only once an earlier stage has written it
+      if (ls == MDHIP_VM_SRC_ROW && (k != MDHIP_VM_BINARY || (int)MD_VM_LL(c) >= regs)) return md_fail(MDHIP_EVALUE, "vm: row register read before it is written at %d", pc);
+      if (rs == MDHIP_VM_SRC_ROW && ((k != MDHIP_VM_BINARY && k != MDHIP_VM_PUSH) || (int)MD_VM_RL(c) >= regs))
+        return md_fail(MDHIP_EVALUE, "vm: row register read before it is written at %d", pc);
+    }
     if (c & MDHIP_VM_RND16) {
       if (pr->compute_dtype != MDHIP_F32) return md_fail(MDHIP_EVALUE, "vm: round-to-binary16 needs a float32 program (at %d)", pc);
       if (k != MDHIP_VM_UNARY && k != MDHIP_VM_BINARY) return md_fail(MDHIP_EVALUE, "vm: round-to-binary16 on an instruction that computes nothing (at %d)", pc);
@@ -227,14 +239,37 @@ static inline int md_vm_check(const mdhip_vm_program *pr) {
         if (depth < 3) return md_fail(MDHIP_EVALUE, "vm: where needs 3 operands at %d", pc);
         depth -= 2;
         break;
+      case MDHIP_VM_ROWRED:   // ends a stage: the one value on the stack, reduced over the row into the next register
+        if (!staged) return md_fail(MDHIP_EVALUE, "vm: unknown instruction kind %u", k);
+        if (depth != 1) return md_fail(MDHIP_EVALUE, "vm: ROWRED at %d finds %d values on the stack (one is reduced)", pc, depth);
+        if (op != MDHIP_R_SUM && op != MDHIP_R_PROD && op != MDHIP_R_MAX && op != MDHIP_R_MIN) return md_fail(MDHIP_EVALUE, "vm: reduce op %u is not fused (at %d)", op, pc);
+        if (regs >= MDHIP_VM_ROW_REGS || (int)MD_VM_RL(c) != regs) return md_fail(MDHIP_EVALUE, "vm: ROWRED at %d writes register %u (registers 0 .. %d, in order)", pc, MD_VM_RL(c), MDHIP_VM_ROW_REGS - 1);
+        if (ls != MDHIP_VM_SRC_STACK || rs != MDHIP_VM_SRC_STACK) return md_fail(MDHIP_EVALUE, "vm: ROWRED takes its operand from the stack (at %d)", pc);
+        if (row >= 0.0 && pr->imm[pc] != row) return md_fail(MDHIP_EVALUE, "vm: the ROWREDs of a program name one row length (at %d)", pc);
+        row = pr->imm[pc];
+        if (!(row >= 0.0 && row < 2147483648.0) || row != (double)(int64_t)row) return md_fail(MDHIP_EVALUE, "vm: bad row length at %d", pc);
+        ++regs;
+        depth = 0;
+        break;
       default: return md_fail(MDHIP_EVALUE, "vm: unknown instruction kind %u", k);
     }
     if (depth > MDHIP_VM_STACK) return md_fail(MDHIP_EVALUE, "vm: stack depth %d exceeds %d", depth, MDHIP_VM_STACK);
   }
+  if (staged && regs == 0) return md_fail(MDHIP_EVALUE, "vm: not a staged program");
   if (depth != 1) return md_fail(MDHIP_EVALUE, "vm: program leaves %d values on the stack", depth);
   // a leaf has any of the twelve dtypes: it is read in its own storage type and converted to the compute dtype on load
   for (int l = 0; l < pr->n_leaves; ++l) MD_TRY(md_check_any_array(&pr->leaves[l], "vm leaf"));
+  if (n_regs) *n_regs = regs;
+  if (n_red) *n_red = (int64_t)row;
   return MDHIP_OK;
+}
+static inline int md_vm_check(const mdhip_vm_program *pr) { return md_vm_check_impl(pr, false, nullptr, nullptr); }
+static inline int md_vm_check_staged(const mdhip_vm_program *pr, int *n_regs, int64_t *n_red) { return md_vm_check_impl(pr, true, n_regs, n_red); }
+static inline bool md_vm_is_staged(const mdhip_vm_program *pr) {
+  if (!pr || pr->n_instr < 1 || pr->n_instr > MDHIP_VM_MAX_INSTR) return false;
+  for (int pc = 0; pc < pr->n_instr; ++pc)
+    if (MD_VM_KIND(pr->ctrl[pc]) == MDHIP_VM_ROWRED) return true;
+  return false;
 }
 
 // Collapsed iteration space over (leaves..., out); same merge rule as md_build_iter.

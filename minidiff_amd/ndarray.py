@@ -97,6 +97,24 @@ def lazy_float16_enabled() -> bool:
     return _LAZY_F16
 
 
+# Sub-switch of lazy mode (acts only while it is on): a float32 / float64 sum / prod / max / min over the trailing axes with
+# keepdims=True stays pending (a ROWRED node, minidiff_amd/lazy.py), and a chain over the same rows that consumes it — softmax,
+# its gradient, a mean / variance layer norm — runs as ONE launch that holds each row in registers (a staged program,
+# include/mdhip.h). Off: such a reduction runs when it is called, and the chain behind it reads its result from memory.
+_LAZY_ROWS = os.environ.get("MDHIP_LAZY_ROWS", "0") == "1"
+
+
+def set_lazy_rows(flag: bool) -> bool:
+    """Switch the recording of trailing-axis reductions in lazy mode on/off; returns the previous setting."""
+    global _LAZY_ROWS
+    prev, _LAZY_ROWS = _LAZY_ROWS, py_bool(flag)
+    return prev
+
+
+def lazy_rows_enabled() -> bool:
+    return _LAZY_ROWS
+
+
 # Precision of float32 matmul (library option gemm_products, csrc/md_options.h): how many bfloat16 plane products a float32 product
 # may be formed from on the bf16 matrix cores. "highest" (6, the default) is float32 accuracy; "high" (3 products of two rounded
 # planes per operand, ~2^-16 per term) and "medium" (1 product of one, ~2^-8) are permissions, not promises: a product the reduced
@@ -139,7 +157,7 @@ def get_matmul_precision() -> str:
 
 
 # launches issued for pending expressions (tests assert that fusion really happened)
-FUSION_STATS = {"vm_eval": 0, "vm_reduce": 0, "vm_reduce_rows": 0, "vm_reduce_axis": 0, "vm_eval_multi": 0, "vm_eval_reduce_cols": 0, "deferred_cols": 0, "gemm_deferred": 0, "gemm_epilogue": 0}
+FUSION_STATS = {"vm_eval": 0, "vm_reduce": 0, "vm_reduce_rows": 0, "vm_reduce_axis": 0, "vm_eval_multi": 0, "vm_eval_reduce_cols": 0, "vm_eval_rows": 0, "deferred_cols": 0, "gemm_deferred": 0, "gemm_epilogue": 0}
 
 _DTYPE_CODES = {
     np.dtype(np.bool_): _capi.BOOL,
@@ -330,6 +348,12 @@ class DeviceArray(_fp.ArrayBase if _fp is not None else object):
                 leaf._dependents.append(weakref.ref(arr))
                 continue
             _register_reader(b, arr)
+        if expr.rows:   # row statistics below: once one is materialised, this array reads its block
+            for r in expr.rows.values():
+                if r.value is None:
+                    r.users.append(weakref.ref(arr))
+                elif id(r.value) not in expr.leaves:
+                    _register_reader(r.value._buf, arr)
         return arr
 
     @staticmethod
@@ -362,6 +386,16 @@ class DeviceArray(_fp.ArrayBase if _fp is not None else object):
                 if d is not None and d._expr is not None:
                     _register_reader(self._buf, d)
             return
+        if e.rows is not None or e.kind == _lz.ROWRED:
+            if e.kind == _lz.ROWRED:   # a row statistic read alone: today's reduction; this array takes its block
+                _settle_node(e)
+                if self._expr is not None:   # (materialised before this array became its owner)
+                    self._buf, self._expr, self._cdesc = e.value._buf, None, None
+                return
+            if _lz.live_rows(e) and (self._tasks or not self._eval_rows(e)):
+                _settle_rows(e)    # refused (or another shape than the rows'): the statistics first, then the chain over them as leaves
+            if self._expr is None:
+                return
         prog, keep = _lz.build_program(e, self.shape)
         self._buf = _Buffer(_prod(self.shape) * self.dtype.itemsize)
         self._expr = None
@@ -404,6 +438,25 @@ class DeviceArray(_fp.ArrayBase if _fp is not None else object):
             self._tasks = saved_tasks
             raise
         del keep
+
+    def _eval_rows(self, e) -> py_bool:
+        """A chain with pending row statistics below it, over the shape they were recorded on: ONE launch of the staged program
+        (rows held in registers). False: the library refused — the caller composes."""
+        if self.shape != _lz.live_rows(e)[0].args[1] or _FLOAT_DT.get(self.dtype) != e.cdt or not self.size:
+            return False
+        prog, keep = _lz.build_program(e, self.shape)
+        self._buf = _Buffer(_prod(self.shape) * self.dtype.itemsize)
+        self._expr = None
+        try:
+            _lib().vm_eval(prog, self.desc())
+        except BaseException as exc:
+            self._buf, self._expr, self._cdesc = None, e, None
+            if isinstance(exc, ValueError):
+                return False
+            raise
+        FUSION_STATS["vm_eval_rows"] += 1
+        del keep
+        return True
 
     def _live_tasks(self):
         ts, self._tasks = self._tasks, None
@@ -1011,6 +1064,60 @@ def _as_expr(x, cdt, c16=False):
     return _lz.const(x, cdt)
 
 
+_CDT_NP = {_capi.F32: np.dtype(np.float32), _capi.F64: np.dtype(np.float64)}
+
+
+def _settle_node(r):
+    """Materialise the pending row statistic r by the route the reduction takes with MDHIP_LAZY_ROWS off — the statistics below
+    it first —: r becomes a leaf of every program that holds it, and the array it is the value of becomes concrete."""
+    if r.value is not None:
+        return
+    if r.rows:
+        for q in r.rows.values():
+            _settle_node(q)
+    # over the RECORDED expression: the operand array may have been materialised and written in place since (a concrete operand was
+    # recorded as a leaf, and this node reads its block: _before_write evaluates the node ahead of such a write)
+    child, dt = r.args[0], _CDT_NP[r.cdt]
+    if child.kind == _lz.LEAF and child.args.dtype == dt:
+        a = child.args
+    else:
+        own = child.owner
+        a = DeviceArray._pending(child, r.args[1], dt)
+        child.owner = own
+    val = _reduce_now(r.code, a, r.args[2], True, a.dtype)
+    r.value, r.leaves = val, {id(val): val}
+    owner = r.owner() if r.owner is not None else None
+    if owner is not None and owner._expr is r:
+        owner._buf, owner._expr, owner._cdesc = val._buf, None, None
+    users, r.users = r.users, None
+    for u in users:
+        arr = u()
+        if arr is not None and arr._expr is not None:
+            _register_reader(val._buf, arr)
+
+
+def _settle_rows(e):
+    for r in _lz.live_rows(e):
+        _settle_node(r)
+
+
+def _rows_fit(parts, shape) -> py_bool:
+    """May a chain of `shape` over `parts` keep their pending row statistics as registers? They must all have been recorded over ONE
+    (shape, mask), and the chain runs over that shape or over its keepdims shape (per-row scalar arithmetic: s / n, sqrt(v + eps))."""
+    key = None
+    for p in parts:
+        if p.rows is not None or p.kind == _lz.ROWRED:
+            for r in _lz.live_rows(p):
+                k = r.args[1], r.args[2]
+                if key is None:
+                    key = k
+                elif k != key:
+                    return False
+    if key is None or shape == key[0]:
+        return True
+    return shape == tuple(1 if (key[1] >> i) & 1 else n for i, n in enumerate(key[0]))
+
+
 def _lazy_node(kind, code, operands, cdt, shape, odt, f16=False):
     """Build a pending result, materialising the largest pending operand(s) while the
     program would not fit the interpreter. f16: the call is a float16 loop on the float32 carrier — scalars are float16
@@ -1018,6 +1125,9 @@ def _lazy_node(kind, code, operands, cdt, shape, odt, f16=False):
     while True:
         parts = [_as_expr(x, cdt, f16) for x in operands]
         e = _lz.combine(kind, code, parts, cdt, f16 and kind != _lz.WHERE and odt == _F16_DT)
+        if e.rows is not None and _lz.live_rows(e) and not (_rows_fit(parts, shape) and _lz.fits(e)):
+            _settle_rows(e)     # another shape, rows of two kinds, or over the limits with the stages counted: the statistics become leaves
+            continue
         if _lz.fits(e):
             return DeviceArray._pending(e, shape, odt)
         big = None
@@ -1484,7 +1594,7 @@ def astype(a, dtype, copy=True, **kw):
             res = DeviceArray._pending(e, a.shape, dtype)
             e.owner = own
             return res
-        if e is not None and dtype == np.float16 and e.kind != _lz.GEMM and _FLOAT_DT.get(a.dtype) == e.cdt:
+        if e is not None and dtype == np.float16 and e.kind != _lz.GEMM and e.kind != _lz.ROWRED and e.rows is None and _FLOAT_DT.get(a.dtype) == e.cdt:
             res = _eval_as_float16(a, e)
             if res is not None:
                 return res
@@ -1809,13 +1919,54 @@ def _reduce_axes(axis, a):
     return axis
 
 
-def _reduce(code, a, axis, keepdims, out_dtype):
+def _reduce(code, a, axis, keepdims, out_dtype, plain=False):
+    """`plain`: the call gave neither dtype= nor out= (what MDHIP_LAZY_ROWS records)."""
     a = asarray(a)
     axis = _reduce_axes(axis, a)
     axes = normalize_axes(axis, a.ndim)
     mask = 0
     for ax in axes:
         mask |= 1 << ax
+    e = a._expr
+    if _LAZY_ROWS and _LAZY and plain and keepdims:
+        res = _record_rows(code, a, mask)
+        if res is not None:
+            return res
+    if e is not None and (e.rows is not None or e.kind == _lz.ROWRED):
+        _settle_rows(e)      # not recorded: today's route, over today's operands
+    return _reduce_now(code, a, mask, keepdims, out_dtype, axes)
+
+
+def _record_rows(code, a, mask):
+    """MDHIP_LAZY_ROWS: a float32 / float64 sum / prod / max / min over the trailing axes with keepdims=True — rows of at most
+    2048 elements, the geometry _trailing_rows admits — is not launched: the result is pending, a ROWRED node over the operand's
+    expression (a concrete operand is a leaf). None: not such a reduction, or its stage would not fit a program."""
+    cdt = _FLOAT_DT.get(a.dtype)
+    if cdt is None or code > _capi.R_MIN or a.size < _LAZY_MIN or not _trailing_rows(a.shape, mask):
+        return None
+    n_red = 1
+    for i, n in enumerate(a.shape):
+        if (mask >> i) & 1:
+            n_red *= n
+    if n_red > _ROWS_WAVE_MAX:
+        return None
+    e = a._expr
+    if e is not None and e.kind != _lz.GEMM and e.cdt != cdt:
+        return None
+    child = _as_expr(a, cdt)
+    if child.rows is not None or child.kind == _lz.ROWRED:
+        live = _lz.live_rows(child)
+        if live and (live[0].args[1] != a.shape or live[0].args[2] != mask):
+            return None      # statistics of other rows below: they are materialised first (the caller settles them)
+    node = _lz.rowred(child, code, a.shape, mask, n_red, cdt)
+    n, leaves, regs = _lz.cost(node)
+    if n + child.n + 1 >= _lz.MAX_INSTR or child.depth > _lz.MAX_DEPTH or leaves + regs + 1 > _lz.MAX_LEAVES or regs + 1 > _lz.MAX_ROWS:
+        return None
+    kshape = tuple(1 if (mask >> i) & 1 else n for i, n in enumerate(a.shape))
+    return DeviceArray._pending(node, kshape, a.dtype)
+
+
+def _reduce_now(code, a, mask, keepdims, out_dtype, axes=None):
     kshape = tuple(1 if (mask >> i) & 1 else n for i, n in enumerate(a.shape))
     if a._expr is not None:
         fused = _fused_reduce(code, a, mask, kshape, np.dtype(out_dtype))
@@ -1825,6 +1976,8 @@ def _reduce(code, a, axis, keepdims, out_dtype):
                 fused = fused._view(fused._offset, fshape, _c_strides(fshape))
             return fused
     if a.size >= _RESHAPE_REDUCE_MIN and a.ndim >= 2:
+        if axes is None:
+            axes = tuple(i for i in range(a.ndim) if (mask >> i) & 1)
         staged = _staged_reduce(code, a, axes, mask, keepdims, kshape, out_dtype)
         if staged is not None:
             return staged
@@ -2125,25 +2278,25 @@ def _sum_dtype(a_dtype, dtype):
 def sum(a, axis=None, dtype=None, out=None, keepdims=False, **kw):
     _defaults_only("sum", kw)
     a = asarray(a)
-    return _finish_out(_reduce(_capi.R_SUM, a, axis, keepdims, _sum_dtype(a.dtype, dtype)), out, "add")
+    return _finish_out(_reduce(_capi.R_SUM, a, axis, keepdims, _sum_dtype(a.dtype, dtype), dtype is None and out is None), out, "add")
 
 
 def prod(a, axis=None, dtype=None, out=None, keepdims=False, **kw):
     _defaults_only("prod", kw)
     a = asarray(a)
-    return _finish_out(_reduce(_capi.R_PROD, a, axis, keepdims, _sum_dtype(a.dtype, dtype)), out, "multiply")
+    return _finish_out(_reduce(_capi.R_PROD, a, axis, keepdims, _sum_dtype(a.dtype, dtype), dtype is None and out is None), out, "multiply")
 
 
 def max(a, axis=None, out=None, keepdims=False, **kw):
     _defaults_only("max", kw)
     a = asarray(a)
-    return _finish_out(_reduce(_capi.R_MAX, a, axis, keepdims, a.dtype), out, "maximum")
+    return _finish_out(_reduce(_capi.R_MAX, a, axis, keepdims, a.dtype, out is None), out, "maximum")
 
 
 def min(a, axis=None, out=None, keepdims=False, **kw):
     _defaults_only("min", kw)
     a = asarray(a)
-    return _finish_out(_reduce(_capi.R_MIN, a, axis, keepdims, a.dtype), out, "minimum")
+    return _finish_out(_reduce(_capi.R_MIN, a, axis, keepdims, a.dtype, out is None), out, "minimum")
 
 
 def any(a, axis=None, out=None, keepdims=False, **kw):
@@ -2208,6 +2361,8 @@ def mean(a, axis=None, dtype=None, out=None, keepdims=False, **kw):
         # an integer dtype= : NumPy divides with casting='unsafe' back into the integer sum (the quotient truncates toward zero)
         with np.errstate(all="ignore"):
             return _finish_out(astype(_binary(np.true_divide, _capi.B_TRUE_DIV, s, n), s.dtype), out, "mean")
+    if s._expr is not None:     # a pending row sum (MDHIP_LAZY_ROWS): the quotient joins its chain
+        return _finish_out(_binary(np.true_divide, _capi.B_TRUE_DIV, s, n), out, "mean")
     return _finish_out(_binary(np.true_divide, _capi.B_TRUE_DIV, s, n, out=s), out, "mean")
 
 
@@ -3111,7 +3266,7 @@ def materialize_many(arrays):
             pending.append(a)
     groups = {}
     for a in pending:
-        if a._expr.kind != _lz.GEMM and a.size and a.dtype in _FLOAT_DT and _FLOAT_DT[a.dtype] == a._expr.cdt and not a._tasks:  # (owed reductions ride on a single evaluation)
+        if a._expr.kind != _lz.GEMM and a._expr.kind != _lz.ROWRED and a._expr.rows is None and a.size and a.dtype in _FLOAT_DT and _FLOAT_DT[a.dtype] == a._expr.cdt and not a._tasks:  # (owed reductions ride on a single evaluation)
             groups.setdefault((a.shape, a._expr.cdt), []).append(a)
     for group in groups.values():
         while len(group) >= 2:
