@@ -388,9 +388,11 @@ enum { MDHIP_VM_SRC_STACK = 0, MDHIP_VM_SRC_LEAF = 1, MDHIP_VM_SRC_CONST = 2, MD
  * n_red in elements — the trailing axes of `out` whose extents multiply to it are the row; 0: the last axis — and is the same in
  * every ROWRED of a program. MDHIP_VM_SRC_ROW as the rhs of a PUSH or as either operand of a BINARY reads the row register named
  * by the leaf-index field, written by an EARLIER stage. The final stage leaves one value, which is stored. MDHIP_VM_RND16 on a
- * ROWRED is refused. Geometry: that of mdhip_vm_reduce's third form below, with n_red <= 2048, n_out >= 2 and a dense, 16-byte
- * aligned `out` of the compute dtype; anything else returns MDHIP_EVALUE and the caller composes the stages from mdhip_vm_reduce
- * and mdhip_vm_eval, which give the same bits (each stage combines in the order of that form's wave-per-row kernel). */
+ * ROWRED is refused. Geometry: that of mdhip_vm_reduce's third form below, with n_red <= 8192, n_out >= 2 and a dense, 16-byte
+ * aligned `out` of the compute dtype. Rows of up to 2048 elements run a wave per row; longer ones a block per row, and only from
+ * 256 rows on (the floor below which mdhip_vm_reduce refuses such rows). Anything else returns MDHIP_EVALUE and the caller
+ * composes the stages from mdhip_vm_reduce and mdhip_vm_eval, which give the same bits (each stage combines in the order of
+ * that form's wave-per-row kernel, or of its block-per-row kernel above 2048). */
 #define MDHIP_VM_ROW_REGS 4
 typedef struct mdhip_vm_program {
   int32_t n_instr, n_leaves, compute_dtype, _pad;

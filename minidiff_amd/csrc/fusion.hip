@@ -646,19 +646,23 @@ static void plan_begin(VmLaunch *L, const mdhip_vm_program *pr) {
 // generated kernels, longer ones a block per row; long rows need at least a row per CU (no cross-block split yet)
 constexpr int64_t VM_ROWS_WAVE_MAX = 64 * 4 * 8;
 constexpr int64_t VM_ROWS_MIN_OUT = MD_NUM_CUS;
+// a staged program holds rows up to 256 lanes x 8 groups x 4 elements, a block per row above VM_ROWS_WAVE_MAX
+constexpr int64_t VM_ROWS_STAGED_MAX = 256 * 4 * 8;
 // vector groups per lane of the wave-per-row kernels (RED_ROWS, ROWS_STAGED) for a row of n_red <= VM_ROWS_WAVE_MAX elements
 static int rows_wave_nv(int64_t n_red) {
   const int64_t nvec = n_red >> 2;
   return nvec <= 64 ? 1 : nvec <= 128 ? 2 : nvec <= 256 ? 4 : 8;
 }
-// A staged kernel holds NV groups of every vector leaf in registers through all its stages: 4 NV registers per float32 leaf and
-// lane, 8 NV per float64 one. Up to this many the compiled kernels use no scratch (DESIGN.md §4.7 has the figures); a program
+// vector groups per lane of the block-per-row staged kernel for a row of VM_ROWS_WAVE_MAX < n_red <= VM_ROWS_STAGED_MAX elements: 3 .. 8
+static int rows_block_g(int64_t n_red) { return (int)md_ceil_div(n_red >> 2, (int64_t)256); }
+// A staged kernel holds NV (a block per row: G) groups of every vector leaf in registers through all its stages: 4 NV registers
+// per float32 leaf and lane, 8 NV per float64 one. Up to this many the compiled kernels use no scratch (DESIGN.md §4.7 has the figures); a program
 // that would hold more is refused, and the caller composes.
 constexpr int VM_STAGED_HELD_MAX = 256;
 static int staged_held(const jit::Spec &S) {
   int vec = 0;
   for (int l = 0; l < S.n_leaves; ++l) vec += S.leaf_mode[l] == jit::LM_VEC;
-  return vec * S.NV * (S.f32 ? 4 : 8);
+  return vec * (S.G ? S.G : S.NV) * (S.f32 ? 4 : 8);
 }
 
 // A program whose operands are all dense or fully broadcast collapses to ONE axis; the column reductions want it as
@@ -673,7 +677,9 @@ static bool uncollapse_2d(const MdVmIter &it, int n_leaves, MdVmDev *D, int64_t 
 }
 
 // Plan a STAGED program (include/mdhip.h) into `out`: the (n_out, n_red) geometry of mdhip_vm_reduce's third form with rows a wave
-// holds, generated kernel only. Every refusal is MDHIP_EVALUE: the caller composes the stages from mdhip_vm_reduce and mdhip_vm_eval.
+// holds, or a block (then from VM_ROWS_MIN_OUT rows on: below that floor mdhip_vm_reduce refuses long rows, the composed route
+// takes the eager kernels, whose order is another, and staged and composed would differ), generated kernel only.
+// Every refusal is MDHIP_EVALUE: the caller composes the stages from mdhip_vm_reduce and mdhip_vm_eval.
 static int plan_staged(const mdhip_vm_program *pr, const mdhip_array *out, int64_t n_red, VmLaunch *L) {
   if (out->dtype != pr->compute_dtype) return md_fail(MDHIP_EVALUE, "vm_eval: a staged program stores the compute dtype only");
   const int nd = out->ndim;
@@ -682,17 +688,20 @@ static int plan_staged(const mdhip_vm_program *pr, const mdhip_array *out, int64
   int64_t p = 1;
   for (int d = nd - 1; d >= 0 && p < n_red; --d) p *= out->shape[d];
   if (p != n_red || n_red < 4 || (n_red & 3)) return md_fail(MDHIP_EVALUE, "vm_eval: rows of %lld elements are not trailing axes of whole 16-byte groups", (long long)n_red);
-  if (n_red > VM_ROWS_WAVE_MAX) return md_fail(MDHIP_EVALUE, "vm_eval: rows of %lld elements are longer than a wave holds (%lld)", (long long)n_red, (long long)VM_ROWS_WAVE_MAX);
+  if (n_red > VM_ROWS_STAGED_MAX) return md_fail(MDHIP_EVALUE, "vm_eval: rows of %lld elements are longer than a block holds (%lld)", (long long)n_red, (long long)VM_ROWS_STAGED_MAX);
+  const bool block = n_red > VM_ROWS_WAVE_MAX;   // a block per row
   MD_TRY(md_vm_build_iter(&L->it, pr, out, out));
   const int64_t total = L->it.total, n_out = total / n_red;
   if (n_out < 2 || n_out >= (1ll << 31)) return md_fail(MDHIP_EVALUE, "vm_eval: %lld rows are not staged", (long long)n_out);
+  if (block && n_out < VM_ROWS_MIN_OUT) return md_fail(MDHIP_EVALUE, "vm_eval: %lld rows of %lld elements are not staged (a block per row from %lld rows on)", (long long)n_out, (long long)n_red, (long long)VM_ROWS_MIN_OUT);
   to_dev(pr, &L->D);
   if (!fast_geometry(L->it, pr->n_leaves, pr, true, &L->D, &L->rows, &L->inner) || !aligned16(out->data) ||
       !uncollapse_2d(L->it, pr->n_leaves, &L->D, n_out, n_red, &L->rows, &L->inner))
     return md_fail(MDHIP_EVALUE, "vm_eval: a staged program needs (rows, reduced) geometry with rows of whole, aligned 16-byte groups");
   jit::Spec S;
   if (!jit::spec_for(&S, jit::ROWS_STAGED, pr, L->D, L->rows, total)) return md_fail(MDHIP_EVALUE, "vm_eval: a staged program runs as a generated kernel only (options jit, jit_min)");
-  S.NV = rows_wave_nv(n_red);
+  if (block) S.G = rows_block_g(n_red);
+  else S.NV = rows_wave_nv(n_red);
   if (staged_held(S) > VM_STAGED_HELD_MAX) return md_fail(MDHIP_EVALUE, "vm_eval: the staged program would hold %d registers per lane (max %d)", staged_held(S), VM_STAGED_HELD_MAX);
   // streamed: the stored value and the leaves that advance from row to row (a row-invariant vector is re-read from the caches)
   S.nt = total * (int64_t)md_dtype_size(out->dtype) + jit::streamed_bytes(L->D, total, true) > jit::NT_BYTES;
@@ -700,7 +709,7 @@ static int plan_staged(const mdhip_vm_program *pr, const mdhip_array *out, int64
   if (!L->fn) return md_fail(MDHIP_EVALUE, "vm_eval: no run-time compiler for the staged program");
   L->form = VM_ROWS_STAGED;
   L->n_out = n_out; L->n_red = n_red;
-  L->grid = md_ceil_div(n_out, 4);
+  L->grid = block ? n_out : md_ceil_div(n_out, 4);
   return MDHIP_OK;
 }
 
@@ -1277,12 +1286,13 @@ int mdhip_vm_jit_probe(const mdhip_vm_program *pr, int kind, int reduce_op, int 
     int64_t n_red;
     MD_TRY(md_vm_check_staged(pr, nullptr, &n_red));
     if (n_red == 0 && pr->n_leaves > 0 && pr->leaves[0].ndim > 0) n_red = pr->leaves[0].shape[pr->leaves[0].ndim - 1];
-    if (n_red < 4 || (n_red & 3) || n_red > VM_ROWS_WAVE_MAX) return md_fail(MDHIP_EVALUE, "jit probe: rows of %lld elements are not staged", (long long)n_red);
+    if (n_red < 4 || (n_red & 3) || n_red > VM_ROWS_STAGED_MAX) return md_fail(MDHIP_EVALUE, "jit probe: rows of %lld elements are not staged", (long long)n_red);
     jit::Spec S;
     S.kind = jit::ROWS_STAGED;
     jit::spec_single(&S, pr);
     probe_modes(&S, pr);
-    S.NV = rows_wave_nv(n_red);
+    if (n_red > VM_ROWS_WAVE_MAX) S.G = rows_block_g(n_red);   // a block per row
+    else S.NV = rows_wave_nv(n_red);
     if (staged_held(S) > VM_STAGED_HELD_MAX) return md_fail(MDHIP_EVALUE, "jit probe: the staged program would hold %d registers per lane (max %d)", staged_held(S), VM_STAGED_HELD_MAX);
     return probe_compile(S, log, log_cap);
   }

@@ -192,6 +192,7 @@ struct Spec {
   bool wide = false;                // EVAL over axes: 64-bit vector index (2^31 vectors and more), else 32-bit
   int NV = 0;                       // RED_ROWS: 1, 2, 4, 8 vector groups per lane, a wave per row | 0 a block per row
                                     // ROWS_STAGED (a staged program: its stages are cut at the ROWREDs of pr[0]): 1, 2, 4, 8
+  int G = 0;                        // ROWS_STAGED: 0 a wave per row (NV) | 3 .. 8 a block per row, that many vector groups per lane (NV is 0)
   bool batch = false;               // RED_COLS / SWEEP: `outer` independent (n_red, n_out) problems, the batch on blockIdx.y (a middle axis reduced)
 };
 
@@ -535,7 +536,7 @@ static std::string kind_tag(const Spec &S) {
     case RED_ALL: return "redall";
     case RED_COLS: return S.batch ? "redcolsb" : "redcols";
     case RED_ROWS: return S.NV ? "redrowsw" + std::to_string(S.NV) : "redrowsb";
-    case ROWS_STAGED: return "rowsres" + std::to_string(S.NV);
+    case ROWS_STAGED: return S.G ? "rowsresb" + std::to_string(S.G) : "rowsres" + std::to_string(S.NV);
   }
   return S.store ? "evalcols" : S.batch ? "sweepb" : "sweepcols";
 }
@@ -731,16 +732,31 @@ __device__ __forceinline__ double jbcast(double v) {
   return u.f;
 }
 )";
-    o << "extern \"C\" __global__ void __launch_bounds__(256) KNAME(JArgs A) {\n"
-         "  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;\n"
-         "  const long long row = (long long)blockIdx.x * 4 + w;\n"
-         "  if (row >= A.n_out) return;  // (whole waves: no barrier below, and every lane of a live wave is active)\n"
-         "  const long long nv = A.n_red >> 2;\n"
-      << LT.pro() << LT.vec("row", "0", "_r", rowb, "  ");
-    for (int g = 0; g < S.NV; ++g) {
+    // S.G (rows longer than a wave holds): a BLOCK per row, the grid exactly n_out blocks, lane t of 256 holds the groups t + 256 g,
+    // g < G. Each stage combines EXACTLY as redrowsb above combines: its loop puts lane t's group g into the accumulator set
+    // a[g & 1] in ascending g (the pair loop takes g, g + 1; its tail is an even group, into a[0]) — unrolled here over the held
+    // groups — then the same merge of the two sets, the 64-lane tree, and the four wave partials through LDS as (s0 . s1) . (s2 . s3).
+    // Every lane forms that last combine itself, from the stage's own four LDS words after ONE barrier (same operands, same order:
+    // same bits), so no second barrier guards the words against the next stage. No lane returns early: the grid has no idle block,
+    // and a lane without a live group still takes part in every tree and barrier.
+    const int NG = S.G ? S.G : S.NV, LW = S.G ? 256 : 64;   // groups per lane, lanes per row
+    const char *ln = S.G ? "(int)threadIdx.x" : "lane";
+    if (S.G)
+      o << "extern \"C\" __global__ void __launch_bounds__(256) KNAME(JArgs A) {\n"
+           "  __shared__ T smem[" << (ns > 0 ? ns : 1) << "][4];\n"
+           "  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;\n"
+           "  const long long row = blockIdx.x, nv = A.n_red >> 2;  // (the grid is n_out blocks: every block has a row)\n";
+    else
+      o << "extern \"C\" __global__ void __launch_bounds__(256) KNAME(JArgs A) {\n"
+           "  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;\n"
+           "  const long long row = (long long)blockIdx.x * 4 + w;\n"
+           "  if (row >= A.n_out) return;  // (whole waves: no barrier below, and every lane of a live wave is active)\n"
+           "  const long long nv = A.n_red >> 2;\n";
+    o << LT.pro() << LT.vec("row", "0", "_r", rowb, "  ");
+    for (int g = 0; g < NG; ++g) {
       const std::string sfx = "_" + std::to_string(g);
-      o << "  const bool ok" << sfx << " = lane + " << 64 * g << " < nv;\n"
-        << "  const long long c" << sfx << " = (ok" << sfx << " ? (long long)(lane + " << 64 * g << ") : 0ll) << 2;\n"
+      o << "  const bool ok" << sfx << " = " << ln << " + " << LW * g << " < nv;\n"
+        << "  const long long c" << sfx << " = (ok" << sfx << " ? (long long)(" << ln << " + " << LW * g << ") : 0ll) << 2;\n"
         << LT.vec("row", "c" + sfx, sfx, vecm, "  ");
     }
     auto regs = [](int n) {
@@ -748,7 +764,21 @@ __device__ __forceinline__ double jbcast(double v) {
       for (int k = 0; k < n; ++k) r += ", r" + std::to_string(k);
       return r;
     };
-    for (int s = 0; s < ns; ++s) {
+    if (S.G) for (int s = 0; s < ns; ++s) {
+      const std::string R = reduce_name((int)MD_VM_OP(pr->ctrl[cut[s]]));
+      auto cmb = [&](const std::string &x, const std::string &y) { return R + "::combine(" + x + ", " + y + ")"; };
+      o << "  T r" << s << ";\n  {\n    T a[2][4];\n#pragma unroll\n    for (int u = 0; u < 2; ++u)\n#pragma unroll\n      for (int j = 0; j < 4; ++j) a[u][j] = " << R << "::template identity<T>();\n";
+      for (int g = 0; g < NG; ++g) {
+        const std::string sfx = "_" + std::to_string(g), acc = "a[" + std::to_string(g & 1) + "][j]";
+        o << "    if (ok" << sfx << ") {\n#pragma unroll\n      for (int j = 0; j < 4; ++j) " << acc << " = " << cmb(acc, "body" + std::to_string(s) + "(A" + LT.args(sfx, "j", "_r") + regs(s) + ")") << ";\n    }\n";
+      }
+      o << "    T acc = " << cmb(cmb(cmb("a[0][0]", "a[1][0]"), cmb("a[0][1]", "a[1][1]")), cmb(cmb("a[0][2]", "a[1][2]"), cmb("a[0][3]", "a[1][3]"))) << ";\n"
+           "#pragma unroll\n    for (int d = 32; d > 0; d >>= 1) acc = " << R << "::combine(acc, jshfl(acc, d));\n"
+           "    if (lane == 0) smem[" << s << "][w] = acc;\n    __syncthreads();\n"
+           "    r" << s << " = jbcast(" << cmb(cmb("smem[" + std::to_string(s) + "][0]", "smem[" + std::to_string(s) + "][1]"), cmb("smem[" + std::to_string(s) + "][2]", "smem[" + std::to_string(s) + "][3]"))
+        << ");  // every lane holds the row's value: through a scalar register\n  }\n";
+    }
+    else for (int s = 0; s < ns; ++s) {
       const std::string R = reduce_name((int)MD_VM_OP(pr->ctrl[cut[s]]));
       o << "  T r" << s << ";\n  {\n    T a[4];\n#pragma unroll\n    for (int j = 0; j < 4; ++j) a[j] = " << R << "::template identity<T>();\n";
       for (int g = 0; g < S.NV; ++g) {
@@ -759,7 +789,7 @@ __device__ __forceinline__ double jbcast(double v) {
            "#pragma unroll\n    for (int d = 32; d > 0; d >>= 1) acc = " << R << "::combine(acc, jshfl(acc, d));\n"
            "    r" << s << " = jbcast(acc);  // lane 0 holds the row's value: to every lane\n  }\n";
     }
-    for (int g = 0; g < S.NV; ++g) {
+    for (int g = 0; g < NG; ++g) {
       const std::string sfx = "_" + std::to_string(g);
       o << "  if (ok" << sfx << ") {\n    JVec<T, 4> o;\n#pragma unroll\n    for (int j = 0; j < 4; ++j) o.v[j] = body" << ns << "(A" << LT.args(sfx, "j", "_r") << regs(ns) << ");\n"
         << "    jst(reinterpret_cast<JVec<T, 4> *>((T *)A.outs[0] + row * A.n_red + c" << sfx << "), o);\n  }\n";
@@ -936,6 +966,7 @@ static std::string make_key(const Spec &S) {
   std::ostringstream k;
   k << S.kind << ':' << (int)S.f32 << (int)S.out_bool << (int)S.nt << (int)S.nt_store << (int)S.store << ':' << S.rop << ':' << S.Q << ':' << S.RU << ':' << S.U << ':' << S.n << ':' << S.axes << (int)S.wide << ':' << S.NV;
   if (S.batch) k << 'b';
+  if (S.G) k << 'g' << S.G;   // (the wave form's key is what it was)
   if (S.out_f16) k << 'h';
   for (int p = 0; p < S.n; ++p) {
     k << '/';

@@ -115,6 +115,47 @@ def lazy_rows_enabled() -> bool:
     return _LAZY_ROWS
 
 
+# The longest row (in elements) that MDHIP_LAZY_ROWS records. 2048, the default, is what a wave holds (k_fused_rowsres<NV>); up to
+# 8192 the staged program runs a block per row (k_fused_rowsresb<G>, fusion.hip: VM_ROWS_STAGED_MAX). Longer rows are opt-in on
+# their own, so that the default is exactly the route without this setting.
+_LAZY_ROWS_MAX_LO, _LAZY_ROWS_MAX_HI = 2048, 8192
+
+
+def _checked_rows_max(n) -> int:
+    try:
+        v = None if isinstance(n, py_bool) else operator.index(n)
+    except TypeError:
+        v = None
+    if v is None or not _LAZY_ROWS_MAX_LO <= v <= _LAZY_ROWS_MAX_HI:
+        raise ValueError(f"lazy rows max must be an integer in {_LAZY_ROWS_MAX_LO} .. {_LAZY_ROWS_MAX_HI}, got {n!r}")
+    return v
+
+
+def _rows_max_from_env() -> int:
+    text = os.environ.get("MDHIP_LAZY_ROWS_MAX")
+    if text is None:
+        return _LAZY_ROWS_MAX_LO
+    try:
+        n = int(text)
+    except ValueError:
+        raise ValueError(f"MDHIP_LAZY_ROWS_MAX must be an integer in {_LAZY_ROWS_MAX_LO} .. {_LAZY_ROWS_MAX_HI}, got {text!r}") from None
+    return _checked_rows_max(n)
+
+
+_LAZY_ROWS_MAX = _rows_max_from_env()
+
+
+def set_lazy_rows_max(n: int) -> int:
+    """Set the longest row, in elements (2048 .. 8192), that MDHIP_LAZY_ROWS records; returns the previous value."""
+    global _LAZY_ROWS_MAX
+    prev, _LAZY_ROWS_MAX = _LAZY_ROWS_MAX, _checked_rows_max(n)
+    return prev
+
+
+def lazy_rows_max() -> int:
+    return _LAZY_ROWS_MAX
+
+
 # Precision of float32 matmul (library option gemm_products, csrc/md_options.h): how many bfloat16 plane products a float32 product
 # may be formed from on the bf16 matrix cores. "highest" (6, the default) is float32 accuracy; "high" (3 products of two rounded
 # planes per operand, ~2^-16 per term) and "medium" (1 product of one, ~2^-8) are permissions, not promises: a product the reduced
@@ -1939,8 +1980,8 @@ def _reduce(code, a, axis, keepdims, out_dtype, plain=False):
 
 def _record_rows(code, a, mask):
     """MDHIP_LAZY_ROWS: a float32 / float64 sum / prod / max / min over the trailing axes with keepdims=True — rows of at most
-    2048 elements, the geometry _trailing_rows admits — is not launched: the result is pending, a ROWRED node over the operand's
-    expression (a concrete operand is a leaf). None: not such a reduction, or its stage would not fit a program."""
+    lazy_rows_max() elements (2048 unless raised), the geometry _trailing_rows admits — is not launched: the result is pending, a
+    ROWRED node over the operand's expression (a concrete operand is a leaf). None: not such a reduction, or its stage would not fit a program."""
     cdt = _FLOAT_DT.get(a.dtype)
     if cdt is None or code > _capi.R_MIN or a.size < _LAZY_MIN or not _trailing_rows(a.shape, mask):
         return None
@@ -1948,7 +1989,7 @@ def _record_rows(code, a, mask):
     for i, n in enumerate(a.shape):
         if (mask >> i) & 1:
             n_red *= n
-    if n_red > _ROWS_WAVE_MAX:
+    if n_red > _LAZY_ROWS_MAX:
         return None
     e = a._expr
     if e is not None and e.kind != _lz.GEMM and e.cdt != cdt:

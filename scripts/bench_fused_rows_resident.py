@@ -2,6 +2,7 @@
 """Lazy mode: chains that continue past a row reduction, with MDHIP_LAZY_ROWS (ndarray.set_lazy_rows) off and on in ONE process.
 
   python scripts/bench_fused_rows_resident.py [--batches 20] [--reps 10] [--out-prefix profiles/fused_resident] [--trace]
+  python scripts/bench_fused_rows_resident.py --long [--out-prefix profiles/fused_resident_long]
 
 Cases (float32): softmax forward and the softmax gradient p * (g - sum(g * p)) on (8192, 2048) and (65536, 256), a mean / variance
 layer norm with (C,) gamma and beta on (16384, 1024). A call builds the chain and forces its result into memory.
@@ -13,6 +14,9 @@ kernels per call, and on / off. <prefix>_before.txt gets the switch-off lines, <
 --trace: a few calls of every arm and nothing else, for
   rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python scripts/bench_fused_rows_resident.py --trace
 (the staged kernels are named k_fused_rowsres<NV>_.., the composed route's k_fused_redrowsw<NV>_.. and k_fused_eval_..).
+--long: the long rows instead (float32): layer norm on (8192, 4096) and (4096, 8192), softmax and the softmax gradient on
+(8192, 4096). The switch is on in both arms; they differ in ndarray.set_lazy_rows_max: 2048 (`_before`: such rows are not recorded,
+the composed route) against 8192 (`_after`: a block per row, k_fused_rowsresb<G>_..). Same method, same columns.
 No GPU: an error, not a fallback."""
 import argparse
 import ctypes as C
@@ -43,12 +47,25 @@ def layer_norm(x, gamma, beta):
     return nd.add(nd.multiply(nd.true_divide(d, nd.sqrt(nd.add(v, 1e-5))), gamma), beta)
 
 
-def cases(rng):
+def cases(rng, long_rows):
     """(name, fused bytes, call)"""
     def f(*s):
         return nd.asarray(rng.standard_normal(s).astype(np.float32))
 
     out = []
+    if long_rows:
+        for R, Cn in ((8192, 4096), (4096, 8192)):
+            x, gamma, beta = f(R, Cn), f(Cn), f(Cn)
+            out.append((f"layer norm {R}x{Cn}", 2 * R * Cn * 4 + 8 * Cn, lambda x=x, gamma=gamma, beta=beta: nd.materialize(layer_norm(x, gamma, beta))))
+        R, Cn = 8192, 4096
+        x, g = f(R, Cn), f(R, Cn)
+        prev = nd.set_lazy_rows(False)
+        p = nd.materialize(softmax(x))
+        nd.set_lazy_rows(prev)
+        n = R * Cn * 4
+        out.append((f"softmax {R}x{Cn}", 2 * n, lambda: nd.materialize(softmax(x))))
+        out.append((f"softmax gradient {R}x{Cn}", 3 * n, lambda: nd.materialize(softmax_grad(p, g))))
+        return out
     for R, Cn in ((8192, 2048), (65536, 256)):
         x, g = f(R, Cn), f(R, Cn)
         prev = nd.set_lazy_rows(False)
@@ -69,10 +86,18 @@ def main():
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--out-prefix", default=None)
     ap.add_argument("--trace", action="store_true")
+    ap.add_argument("--long", action="store_true", help="rows of 4096 / 8192: set_lazy_rows_max 2048 against 8192, the switch on")
     a = ap.parse_args()
     lib = _capi.load()
     nd.set_lazy(True)
     before, after = [], []
+
+    def arm(flag):
+        if a.long:
+            nd.set_lazy_rows(True)
+            nd.set_lazy_rows_max(8192 if flag else 2048)
+        else:
+            nd.set_lazy_rows(flag)
 
     def say(lines, text):
         print(text, flush=True)
@@ -93,17 +118,18 @@ def main():
         lib.vm_jit_stats(st)
         return int(st[1])
 
+    names = ("on, MDHIP_LAZY_ROWS_MAX 2048", "on, MDHIP_LAZY_ROWS_MAX 8192") if a.long else ("off", "on")
     head = f"# library {lib.target}; lazy mode, MDHIP_LAZY_ROWS %s; {a.batches} batches of {a.reps} back-to-back calls, the two arms in turn; us per call"
     cols = f"# {'case':32s} {'call: median (min - max)':>32s} {'GB/s, fused bytes':>18s} {'generated launches':>19s}"
-    say(before, head % "off")
+    say(before, head % names[0])
     say(before, cols)
-    say(after, head % "on")
-    say(after, cols + "   staged kernel alone: median (min - max)   on / off")
+    say(after, head % names[1])
+    say(after, cols + "   staged kernel alone: median (min - max)   " + ("8192 / 2048" if a.long else "on / off"))
     e0, e1 = event(), event()
-    for name, nbytes, fn in cases(np.random.default_rng(0)):
+    for name, nbytes, fn in cases(np.random.default_rng(0), a.long):
         if a.trace:
             for flag in (False, True):
-                nd.set_lazy_rows(flag)
+                arm(flag)
                 for _ in range(5):
                     fn()
             lib.sync()
@@ -111,7 +137,7 @@ def main():
             continue
         call, launches, kern, vals = {False: [], True: []}, {}, [], {}
         for flag in (False, True):      # warm both arms (code objects, the allocator's blocks); results agree
-            nd.set_lazy_rows(flag)
+            arm(flag)
             l0, r0 = launched(), nd.FUSION_STATS["vm_eval_rows"]
             vals[flag] = fn().get()
             launches[flag] = launched() - l0
@@ -123,7 +149,7 @@ def main():
         lib.sync()
         for _ in range(a.batches):
             for flag in (False, True):
-                nd.set_lazy_rows(flag)
+                arm(flag)
                 lib.event_record(e0)
                 for _ in range(a.reps):
                     fn()
