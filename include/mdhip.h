@@ -215,7 +215,15 @@ int mdhip_graph_destroy(void *graph);
 int mdhip_unary(int op, const mdhip_array *x, const mdhip_array *out);
 /* out = x converted element by element (C conversion rules = numpy.ndarray.astype's unsafe casting; to bool: x != 0;
  * binary16 <-> wider floats with round-to-nearest-even), ANY pair of the 12 dtypes above, any strides (<= 8-D): the one
- * kernel behind the storage-only dtypes — `astype`, strided copies, and the promote / demote steps around wide arithmetic.
+ * entry behind the storage-only dtypes — `astype`, copies, and the promote / demote steps around wide arithmetic.
+ * Contract: source -> the carrier the SOURCE picks (int64: bool and signed integers, uint64: unsigned, double: floats) ->
+ * destination; a float goes into an integer through 64 bits and truncates (out-of-range values wrap from 64 bits), float64 ->
+ * float16 rounds once, a float16 NaN comes out canonical (payload dropped, sign kept). Two routes with the same bits on every
+ * input pattern: from 2^14 elements on, 16-byte vector kernels (csrc/narrow.hip) — a stream form for x and out dense over the
+ * collapsed space, each on its own vector alignment, and an axes form for two to four collapsed axes with unit inner stride on
+ * both sides (x16[:, :480]), the inner extent a multiple of the elements per lane (16 B of the narrower side, at most 8 where
+ * one side is 8 bytes wide), outer strides and bases on each side's vector alignment; everything else — smaller, strided,
+ * misaligned — one element per lane (k_convert). Option convert_vec = 0: the latter for every call; counter convert_vec_runs.
  * Replaces numpy.py:188-200's dtypes as used through `astype` (reference: minidiff/tensor.py:105, backend/numpy.py:19). */
 int mdhip_convert(const mdhip_array *x, const mdhip_array *out);
 /* out = op(a, b) with NumPy broadcasting already applied by the caller:
@@ -223,7 +231,13 @@ int mdhip_convert(const mdhip_array *x, const mdhip_array *out);
  * compute_dtype = the ufunc loop dtype NumPy resolves (np.<op>.resolve_dtypes). */
 int mdhip_binary(int op, const mdhip_array *a, const mdhip_array *b,
                  const mdhip_array *out, int compute_dtype);
-/* out = cond ? a : b            (reference: numpy.py:95, definitions.py:555-559) */
+/* out = cond ? a : b            (reference: numpy.py:95, definitions.py:555-559)
+ * A storage-only out whose branches are arrays of out's own dtype or scalars (not both scalars), under a bool array cond, from
+ * 2^14 elements on: a selection of the STORED bits in 16-byte vectors (NaN payloads and -0.0 come out as they went in) — a
+ * stream form (everything dense; cond on 16 / element-size bytes, branches and out on 16) and an axes form (two to four
+ * collapsed axes; cond and each branch contiguous or broadcast along the inner one, out dense). A non-bool cond, branches of
+ * two dtypes, a wide out with a narrow branch: the generic kernel, through the carrier of out's dtype (float16 through float32:
+ * a signalling NaN comes out quiet). Option where_vec = 0: the generic kernel for every such call; counter where_vec_runs. */
 int mdhip_where(const mdhip_array *cond, const mdhip_array *a, const mdhip_array *b,
                 const mdhip_array *out);
 /* fill out with a scalar (ones/zeros/full families, numpy.py:98-103) */

@@ -706,8 +706,9 @@ template <class T> __global__ void __launch_bounds__(MD_BLOCK) k_arange(T *out, 
 
 // ------------------------------------------------------------- any -> any conversion ----
 // The kernel behind the storage-only dtypes (include/mdhip.h: int8/16, uint8/16/32/64, float16): loads through the source's
-// carrier (int64 / uint64 / double), stores with the destination's conversion; the dtype switches are wave-uniform. Off the
-// BASELINE paths (nothing there uses a narrow type): one generic strided walk.
+// carrier (int64 / uint64 / double), stores with the destination's conversion; the dtype switches are wave-uniform. One generic
+// strided walk: what narrow.hip's vector kernels (k_nw_convert, k_nw_convert_axes) decline — small, strided, misaligned calls —
+// and the definition of the bits they produce.
 template <class C>
 __global__ void __launch_bounds__(MD_BLOCK) k_convert(MdIter it, const void *x, int xdt, void *out, int odt) {
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -724,6 +725,7 @@ __global__ void __launch_bounds__(MD_BLOCK) k_convert(MdIter it, const void *x, 
 int md_narrow_unary(int op, const mdhip_array *x, const mdhip_array *out);
 int md_narrow_binary(int op, const mdhip_array *a, const mdhip_array *b, const mdhip_array *out, int cdt);
 int md_narrow_where(const mdhip_array *c, const mdhip_array *a, const mdhip_array *b, const mdhip_array *out);
+int md_narrow_convert(const MdIter &it, const mdhip_array *x, const mdhip_array *out);   // -1: declined
 static inline bool md_narrow_code(int dt) { return dt >= MDHIP_NUM_DTYPES && dt < MDHIP_NUM_ALL_DTYPES; }
 static inline bool md_narrow_arr(const mdhip_array *a) { return a && !a->is_scalar && md_narrow_code(a->dtype); }
 
@@ -741,6 +743,8 @@ int mdhip_convert(const mdhip_array *x, const mdhip_array *out) {
   const mdhip_array *ops[2] = {x, out};
   MD_TRY(md_build_iter(&it, 2, ops, out));
   if (it.total == 0) return MDHIP_OK;
+  const int rc = md_narrow_convert(it, x, out);   // dense and sliced operands from 2**14 elements on: 16-B vectors, the same bits
+  if (rc != -1) return rc;
   const int grid = md_grid_for(it.total);
   switch (md_dtype_carrier(x->dtype)) {
     case 2: k_convert<double><<<grid, MD_BLOCK, 0, md_stream()>>>(it, x->data, x->dtype, out->data, out->dtype); break;

@@ -60,7 +60,11 @@
   X(ARG_BATCHED, "arg_batched", 1, 'x')                /* 0: argmax / argmin over a middle axis keep the block / thread kernels (A/B) */ \
   X(VAR_BATCHED, "var_batched", 1, 'x')                /* 0: mdhip_var refuses a middle axis, the caller composes (A/B) */      \
   X(VAR_NARROW, "var_narrow", 1, 'x')                  /* 0: mdhip_var refuses float16 / small-integer x, the caller promotes and composes (A/B) */ \
-  X(GATHER_RUNS, "gather_runs", 1, 'x')                                                                                    \
+  X(CONVERT_VEC, "convert_vec", 1, 'x')                /* 0: mdhip_convert keeps the one-element k_convert for every call (A/B) */ \
+  X(WHERE_VEC, "where_vec", 1, 'x')                    /* 0: `where` with a storage-only result keeps k_nw_where_generic for every call (A/B) */ \
+  X(CONVERT_VEC_RUNS, "convert_vec_runs", 0, 'x')      /* a COUNTER, as gemm_narrow_thin_runs: the host adds 1 for every launch it ISSUES of k_nw_convert / k_nw_convert_axes */ \
+  X(WHERE_VEC_RUNS, "where_vec_runs", 0, 'x')          /* a COUNTER: the host adds 1 for every launch it ISSUES of k_nw_where / k_nw_where_axes */ \
+  X(GATHER_RUNS, "gather_runs", 1, 'x')                                                                                   \
   X(SCATTER_CENSUS, "scatter_census", 1, 'x')                                                                                   \
   X(SCATTER_SORTED, "scatter_sorted", 1, 'x')          /* 0: element-granular duplicates by bid / apply rounds (A/B) */
 
